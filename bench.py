@@ -22,6 +22,12 @@ The posterior gate reported with the number is evaluated over at least POSTERIOR
 At N = 1 the line also carries `configs`: the other BASELINE configurations that fit one GPU (cfg3, cfg5's per-GPU
 share, cfg5 whole, cfg2 / cfg5 burn-in), each a few hundred generations timed OUTSIDE the headline's region.
 Prints ONE JSON line (rank 0).
+
+A plain run measures the headline and nothing else: set-up, pre-heat, burn-in, warm-up, the K timed generations.
+--full adds everything measured or checked beside it: the posterior moments and gates, the event-pair cross-check, the
+measured copy rate, `configs`, `cpu_baseline` and, at N > 1, the exchange alternatives (--no-moments, --no-other-configs,
+--no-cpu-baseline and --no-exchange-alternatives leave parts of it out).
+--dump-outputs DIR writes what the timed generations computed, as of the last one, to DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -386,6 +392,29 @@ def measured_copy_bandwidth(torch, dev):
     e1.record()
     e1.synchronize()
     return 2.0 * n * 8 * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(eng, path):
+    """--dump-outputs: what a caller of the timed path receives after its last generation -- the chain state, the cached ln-likes, the
+    history rows that generation appended and their ln-likes, p_cr and the acceptance counts -- as float64 .npy files.  The inputs are
+    seeded, so two builds given the same arguments can be compared file for file.  Above DUMP_MAX_BYTES in all (large --chains-per-gpu
+    or many ranks) the row arrays are cut to a fixed, seeded sample of their rows."""
+    h = eng.history_rows()
+    st = eng.stats()
+    arrays = dict(state=eng.get_state(), ln_like=eng.get_loglike(),
+                  history_last_step=eng.get_history(h - 1, h)[0], ln_like_history_last_step=eng.get_loglike_history(h - 1, h)[0],
+                  p_cr=np.asarray(st["p_cr"], dtype=np.float64),
+                  acceptance_counts=np.array([st["local_n_accepted"], st["local_n_rejected"]], dtype=np.float64))
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES and a.shape[0] > 1024:
+            keep = max(1, int(a.shape[0] * 0.9 * DUMP_MAX_BYTES / total))
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1130,8 +1159,14 @@ def main(argv=None):
     ap.add_argument("--exchange", default=None, help="N > 1: push (default) | replay | rows | dense")
     ap.add_argument("--share-gpu", action="store_true", help="REHEARSAL ONLY (never a benchmark number): the N ranks share GPU 0 (push exchange "
                     "between processes, no RCCL: it refuses two ranks on one device; torch.distributed over gloo) -- runs every line of the N > 1 path on a one-GPU box")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (posterior, cross-checks, other "
+                    "configurations, CPU baseline, exchange alternatives); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed generations computed (state, ln-likes, the last "
+                    "generation's history rows, p_cr, acceptance counts) to DIR/<name>.npy, float64")
     args = ap.parse_args(argv)
     globals()["BURNIN_GEN"] = max(0, int(args.burnin_gens))      # (every use below reads the module attribute)
+    if not args.full:
+        args.no_moments = args.no_other_configs = args.no_cpu_baseline = args.no_exchange_alternatives = True
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -1347,6 +1382,8 @@ def main(argv=None):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         value = n_chains * args.steps / el
+        if args.dump_outputs and rank == 0:
+            dump_outputs(eng, args.dump_outputs)
 
         # ---- dominant kernel (phase_fused_kernel): 2 launches per generation, back to back on one queue; at
         # N = 1 nothing else runs in the region, so event time / launches is its average launch duration
@@ -1359,7 +1396,7 @@ def main(argv=None):
         # test surface (include/bipymc_hip_test.h): it runs on the test variant of the library -- the same sources, same kernels (steady-state flavour,
         # launched on the HIP stream) -- never on the sampler whose generations are the number
         pair_ms, pair_n = 0.0, 1
-        if world == 1 and not use_dist:
+        if world == 1 and not use_dist and args.full:
             try:
                 pe = HipEngine(algo=L.ALGO_DREAM, n_chains=n_chains, dim=DIM, target_id=tid, target_params=tparams, seed=42, device=local_rank,
                                del_pairs=DEL_PAIRS, burnin_gen=0, n_cr_gen=N_CR_GEN, n_cr=3, lib=L.load_test())
@@ -1460,7 +1497,7 @@ def main(argv=None):
                              fence_scope={"push-agent": "agent", "push": "system"}.get(left[0]))
     out = None
     if rank == 0:
-        copy_gbs = measured_copy_bandwidth(torch, local_rank) if torch is not None else None
+        copy_gbs = measured_copy_bandwidth(torch, local_rank) if torch is not None and args.full else None
         out = {
             "metric": "chain-updates/sec" if not args.share_gpu else "REHEARSAL (ranks share one GPU): not a benchmark number",
             "value": value, "unit": "chain-updates/s",
@@ -1537,7 +1574,7 @@ def main(argv=None):
         if rank == 0:
             out["exchange_alternatives"] = alts
     elif dist is not None and rank == 0:
-        out["exchange_alternatives"] = [dict(skipped="--no-exchange-alternatives")]
+        out["exchange_alternatives"] = [dict(skipped="--no-exchange-alternatives" if args.full else "measured under --full only")]
     watch.enter("teardown")
     if dist is not None:
         watch.pending("dist.barrier before bpm_destroy")

@@ -7,6 +7,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 import bench
 
 STUB = r"""
@@ -368,3 +370,47 @@ def test_exchange_alternatives_are_timed_beside_the_headline_and_never_fatal():
     # a headline that already ran dense has nothing to add
     alts = bench.exchange_alternatives(_AltEngine(good=["dense"]), _StubDist(), 1, X0, 3, lambda: _StubEngine(), make_rccl, "dense", lambda x: x, 1, gens=5, burn=2)
     assert len(alts) == 1 and "headline itself" in alts[0]["skipped"]
+
+
+class _DumpEngine(object):
+    """what dump_outputs reads of a sampler: state, ln-likes, history, stats"""
+    def __init__(self, n, d):
+        rs = np.random.RandomState(5)
+        self.X, self.ll, self.H = rs.normal(size=(n, d)), rs.normal(size=n), rs.normal(size=(3, n, d))
+
+    def history_rows(self):
+        return self.H.shape[0]
+
+    def stats(self):
+        return dict(p_cr=np.array([0.2, 0.3, 0.5]), local_n_accepted=7, local_n_rejected=9)
+
+    def get_state(self):
+        return self.X
+
+    def get_loglike(self):
+        return self.ll
+
+    def get_history(self, g_lo, g_hi):
+        return self.H[g_lo:g_hi]
+
+    def get_loglike_history(self, g_lo, g_hi):
+        return self.H[g_lo:g_hi, :, 0]
+
+
+def test_dump_outputs_writes_the_last_generation_as_float64(tmp_path, monkeypatch):
+    e = _DumpEngine(64, 5)
+    bench.dump_outputs(e, str(tmp_path / "out"))
+    got = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert sorted(got) == ["acceptance_counts", "history_last_step", "ln_like", "ln_like_history_last_step", "p_cr", "state"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["state"], e.X) and np.array_equal(got["ln_like"], e.ll) and np.array_equal(got["history_last_step"], e.H[-1])
+    assert np.array_equal(got["ln_like_history_last_step"], e.H[-1, :, 0]) and got["acceptance_counts"].tolist() == [7.0, 9.0]
+    # above the size limit: the large arrays become the same seeded sample of rows, run after run; the small ones stay whole
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    e = _DumpEngine(4000, 2)
+    for run in ("a", "b"):
+        bench.dump_outputs(e, str(tmp_path / run))
+    total = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    a, b = (np.load(str(tmp_path / r / "state.npy")) for r in ("a", "b"))
+    assert total < 25000 and 0 < a.shape[0] < 4000 and np.array_equal(a, b)
+    assert np.load(str(tmp_path / "a" / "p_cr.npy")).shape == (3,)

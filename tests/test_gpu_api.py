@@ -349,6 +349,28 @@ def test_bench_runs_without_torch_and_without_burn_in_for_the_kernel_trace():
     assert r2.returncode != 0                    # (the ranks of a world meet through torch.distributed: refused, on every rank)
 
 
+def test_plain_bench_run_is_the_headline_and_dumps_what_the_timed_generations_computed(tmp_path):
+    """`bench.py --steps K --warmup W` without --full measures the headline and nothing beside it; --dump-outputs writes the state the K timed
+    generations ended in (the state whose hash the line carries), its ln-likes and the history rows the last of them appended."""
+    import hashlib
+    import subprocess
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", out],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["metric"] == "chain-updates/sec" and line["steps"] == 30 and line["value"] > 1e8 and line["dtype"] == "f64"
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / 8192 - 1.0) < 1e-9
+    assert "configs" not in line and "cpu_baseline" not in line and line["posterior"]["evaluated"] is False
+    assert line["roofline"]["measured_copy_GBps"] is None and line["roofline"]["avg_launch_us_event_pairs"] is None
+    X, ll = np.load(os.path.join(out, "state.npy")), np.load(os.path.join(out, "ln_like.npy"))
+    assert X.shape == (8192, 100) and X.dtype == np.float64 and np.all(np.isfinite(X)) and ll.shape == (8192,)
+    assert hashlib.sha256(np.ascontiguousarray(X).tobytes()).hexdigest()[:16] == line["config"]["final_state_sha256_16"]
+    assert np.array_equal(np.load(os.path.join(out, "history_last_step.npy")), X)
+    np.testing.assert_allclose(np.load(os.path.join(out, "ln_like_history_last_step.npy")), ll, rtol=1e-12, atol=0)
+
+
 def test_nan_ratio_raises_like_numpy():
     """both ln_like values -inf -> alpha NaN -> the reference's np.random.choice raises ValueError (samplers.py:336)"""
     from bipymc_amd import DeMcMpi

@@ -3,7 +3,6 @@ objects (bipymc/utils/d100_gauss.py:14-35, dblgauss_rv.py:11-32, banana_rv.py:11
 block rebuilt from their attributes and verified against the callable; everything else is a host callback
 (samplers.py:36-43)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,9 +10,6 @@ import pytest
 import _ref_lookalikes as LK
 from bipymc_amd.utils import _target as T
 from bipymc_amd.utils import banana_rv, d100_gauss, dblgauss_rv, mixture_nd
-
-REF = "/root/reference"
-
 
 def _closed_form_of(tid, blk):
     if tid == T.TARGET_GAUSS_EQUICORR:
@@ -105,27 +101,42 @@ def test_rules_that_keep_the_host_callback():
     assert T.resolve_info(ours.ln_like, {}, 8)[2] == "spec"
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "bipymc", "utils")), reason="the reference is not on this machine")
-def test_the_genuine_reference_objects_are_recognised(oracle_engine):
-    os.environ.setdefault("MPLBACKEND", "agg")
-    sys.path.insert(0, REF)
-    sys.dont_write_bytecode, old = True, sys.dont_write_bytecode
-    try:
-        from bipymc.utils import banana_rv as rb, d100_gauss as rg, dblgauss_rv as rd
-    finally:
-        sys.path.remove(REF)
-        sys.dont_write_bytecode = old
-    for obj, dim, tid, ours in ((rg.Gauss_100D(), 100, T.TARGET_GAUSS_EQUICORR, d100_gauss.Gauss_100D()),
-                                (rg.Gauss_100D(rho=0.2, dim=10), 10, T.TARGET_GAUSS_EQUICORR, d100_gauss.Gauss_100D(rho=0.2, dim=10)),
-                                (rd.BimodeGauss_2D(), 2, T.TARGET_MIXTURE_PAIRS, dblgauss_rv.BimodeGauss_2D()),
-                                (rb.Banana_2D(1, 1), 2, T.TARGET_BANANA_2D, banana_rv.Banana_2D(1, 1)),
-                                (rb.Banana_2D(), 2, T.TARGET_BANANA_2D, banana_rv.Banana_2D())):
+def _replayed_reference_object(rec, label):
+    """What the genuine reference's target object `label` shows the registry, replayed from tests/golden/reference_targets_replay.npz (recorded
+    by oracle/gen_target_replay.py): the reference's class name and module, every attribute its constructor set, bit for bit, and its own
+    ln_like at the points where the registry checks the closed form.  Any other point raises: nothing here computes a density."""
+    pts, vals = rec[label + ".points"], rec[label + ".ln_like"]
+
+    def ln_like(self, y):
+        hit = np.flatnonzero((pts == np.asarray(y, dtype=np.float64)).all(axis=1))
+        if hit.size == 0:
+            raise KeyError("no recorded ln_like of the reference's %s at %r" % (label, y))
+        return vals[hit[0]]
+    cls = type(str(rec[label + ".class"]), (object,), {"__module__": str(rec[label + ".module"]), "ln_like": ln_like})
+    obj = cls()
+    prefix = label + ".attr."
+    for k in rec:
+        if k.startswith(prefix):
+            setattr(obj, k[len(prefix):], rec[k])
+    return obj, int(rec[label + ".dim"])
+
+
+def test_the_genuine_reference_objects_are_recognised(oracle_engine, golden_dir):
+    with np.load(os.path.join(golden_dir, "reference_targets_replay.npz")) as z:
+        rec = {k: z[k] for k in z.files}
+    ours = dict(gauss100=d100_gauss.Gauss_100D(), gauss10_rho02=d100_gauss.Gauss_100D(rho=0.2, dim=10), bimodal=dblgauss_rv.BimodeGauss_2D(),
+                banana_1_1=banana_rv.Banana_2D(1, 1), banana=banana_rv.Banana_2D())
+    tids = dict(gauss100=T.TARGET_GAUSS_EQUICORR, gauss10_rho02=T.TARGET_GAUSS_EQUICORR, bimodal=T.TARGET_MIXTURE_PAIRS,
+                banana_1_1=T.TARGET_BANANA_2D, banana=T.TARGET_BANANA_2D)
+    assert sorted(str(v) for v in rec["labels"]) == sorted(ours)
+    for label in ours:
+        obj, dim = _replayed_reference_object(rec, label)
         got_tid, blk, rule = T.resolve_info(obj.ln_like, {}, dim)
-        assert (got_tid, rule) == (tid, "reference-lookalike"), type(obj)
-        np.testing.assert_allclose(blk, ours._bpm_target_spec()[1], rtol=1e-13, atol=1e-15)
+        assert (got_tid, rule) == (tids[label], "reference-lookalike"), label
+        np.testing.assert_allclose(blk, ours[label]._bpm_target_spec()[1], rtol=1e-13, atol=1e-15)
     # and the sampler class takes the device path for it (oracle engine: no GPU here)
     from bipymc_amd.dream import DreamMpi
-    s = DreamMpi(rd.BimodeGauss_2D().ln_like, np.zeros(2), n_chains=8, seed=1)
+    s = DreamMpi(_replayed_reference_object(rec, "bimodal")[0].ln_like, np.zeros(2), n_chains=8, seed=1)
     assert s.uses_device_target and s.target_rule == "reference-lookalike"
     s.run_mcmc(8 * 5)
     assert s.param_est(0)[2].shape == (8 * 5, 2)

@@ -10,7 +10,7 @@ TAG=${1:-r03}
 R=$PWD; O=$R/gpurun_out/prof_$TAG; P=$O/summary; mkdir -p $O $P
 ARGS="--steps 20 --warmup 5"
 for i in 1 2 3; do python bench.py $ARGS 2>/dev/null | tail -1 >> $O/bench_driver.jsonl; done
-python bench.py 2>/dev/null | tail -1 > $O/bench_default.jsonl
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.jsonl
 cd /tmp; export TMPDIR=/tmp
 echo "kernel trace" >> $O/progress.txt
 # (the DEFAULT invocation's 1000 timed generations, and nothing else of the steady-state kernel in the process: no pre-heat, no posterior gates -- their
