@@ -33,6 +33,7 @@
 #include "../../include/bipymc_hip.h"
 #include "kernels.h"
 #include "kernels_wide.h"
+#include "diagnostics.h"
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -575,6 +576,17 @@ struct bpm_sampler {
     int64_t phase_a_updates = 0; // host-callback: local chains already updated in an open generation
     bool proposed = false;
     bool state_set = false;
+    // convergence diagnostics (diagnostics.h, bpm_diag_*): per-half-chain means and M2 of the window of the last bpm_diag_split_moments
+    // ([2][n_local][ld] each), which bpm_diag_autocov centres with; valid while the history is what that call read (dg_epoch / dg_tabs)
+    double* dg_mean = nullptr;
+    double* dg_m2 = nullptr;
+    double* dg_out = nullptr;       // [max(3, DIAG_T) ld]: the aggregates of the split pass, then one block of lag sums
+    double* dg_part = nullptr;      // per-workgroup partials of diag_autocov_kernel
+    size_t dg_part_cap = 0;
+    bool dg_valid = false;
+    int64_t dg_g0 = 0, dg_g1 = 0, dg_n = 0, dg_tabs = 0, dg_rows = 0;
+    uint64_t dg_epoch = 0;
+    uint64_t hist_epoch = 0;        // bumped whenever the history is replaced (reset_history, bpm_set_history); generations bump t_abs
     double* om = nullptr;        // outlier check: world x [omega (n_local) | ln_like (n_local)], all-gathered in place
     double* sel = nullptr;       // outlier check: [0..3] order statistics around Q1 / Q3, [4] first argmax of omega
     unsigned char* sel_state = nullptr;   // radix-select state between the passes (SelState)
@@ -828,6 +840,7 @@ static int push_gen_sums(bpm_sampler* s, int64_t row, const double* src = nullpt
 
 // after the state matrix was (re)initialised: history := [state], moments reset
 static int reset_history(bpm_sampler* s) {
+    s->hist_epoch += 1;
     CK(eval_local_ll(s));
     s->ll_stale = false;
     s->hist_rows = 0;
@@ -929,7 +942,8 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     if (s->arena) { s->G = nullptr; s->om = nullptr; }       // (both live inside the arena)
     void* ptrs[] = {s->tb[0].chunk_count, s->tb[1].chunk_count, s->hist_tmp, s->gen_sums, s->gs_shift, s->gs_part, s->arena, s->tab_peerG, s->tab_all, s->om, s->sel, s->sel_state, s->okeys, s->olist, s->G, s->ll, s->hist, s->llhist, s->w_mean, s->tparams, s->cr_state_base, s->cr_p1, s->cr_p2[0], s->cr_p2[1], s->counters, s->acc_count,
                     s->prop_buf, s->aux_buf, s->ids_buf, s->tb[0].perm, s->tb[0].inv, s->tb[0].plan, s->tb[0].sidx, s->tb[0].plan_count,
-                    s->tb[1].perm, s->tb[1].inv, s->tb[1].plan, s->tb[1].sidx, s->tb[1].plan_count, s->gamma_tab, s->x_next, s->accbits_all, s->PK, s->xstat, s->ckpt_G, s->ckpt_ll, s->ckpt_acc, s->ckpt_counters, s->trace_i32, s->trace_f64, s->trace_mask, s->scratch};
+                    s->tb[1].perm, s->tb[1].inv, s->tb[1].plan, s->tb[1].sidx, s->tb[1].plan_count, s->gamma_tab, s->x_next, s->accbits_all, s->PK, s->xstat, s->ckpt_G, s->ckpt_ll, s->ckpt_acc, s->ckpt_counters, s->trace_i32, s->trace_f64, s->trace_mask, s->scratch,
+                    s->dg_mean, s->dg_m2, s->dg_out, s->dg_part};
     if (free_buffers)
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
@@ -2829,6 +2843,7 @@ extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_
     if (rows < 1 || !hist_local || !X) return fail("bpm_set_history: bad argument");
     if (!s->cfg.keep_history && rows > 1) return fail("bpm_set_history: sampler keeps no history");
     CK(bpm_set_state(s, X));
+    s->hist_epoch += 1;
     if (rows > 1) {
         CK(ensure_history(s, rows));
         HIPCK(hipMemsetAsync(s->hist, 0, (size_t)rows * s->n_local * s->ld * sizeof(double), s->stream));
@@ -2924,6 +2939,94 @@ extern "C" int bpm_reduce_moments(bpm_handle_t s, int64_t n_burn, double* sum, d
         HIPCK(hipStreamSynchronize(s->stream));
     }
     for (uint32_t j = 0; j < s->dim; ++j) { sum[j] = h[j]; sumsq[j] = h[s->ld + j]; shift[j] = h[2 * s->ld + j]; }
+    return 0;
+}
+
+// ---- convergence diagnostics (diagnostics.h; bipymc_amd/diagnostics.py finishes them) --------------------------------------------------
+// Split-chain moments of this rank's chains over history rows [g_lo, g_hi): per coordinate the mean of the 2 n_local half-chain means, the
+// sum of their squared deviations from it and the sum of the half-chain variances.  The per-half-chain means stay on the device for
+// bpm_diag_autocov.
+extern "C" int bpm_diag_split_moments(bpm_handle_t s, int64_t g_lo, int64_t g_hi, double* mean_of_means, double* m2_of_means,
+                                      double* sum_of_vars, int64_t* n_half_chains, int64_t* n_draws) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    s->dg_valid = false;
+    if (!mean_of_means || !m2_of_means || !sum_of_vars || !n_half_chains || !n_draws) return fail("bpm_diag_split_moments: null argument");
+    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        return fail("bpm_diag_split_moments: needs keep_history=True (a resident history of every generation)");
+    if (g_lo < 0 || g_hi < g_lo || g_hi > s->hist_rows) return fail("bpm_diag_split_moments: generation range out of bounds");
+    const int64_t n = (g_hi - g_lo) / 2;
+    if (n < 4)
+        return fail("bpm_diag_split_moments: a window of " + std::to_string((long long)(g_hi - g_lo)) + " history rows gives half-chains of " +
+                    std::to_string((long long)n) + " draws; at least 4 are needed");
+    if (n >= (int64_t)1 << 31) return fail("bpm_diag_split_moments: window too long");
+    CK(normalize_history(s, g_lo, g_hi));
+    const uint64_t row_d = (uint64_t)s->n_local * s->ld;
+    if (!s->dg_mean) {
+        CK(dev_alloc(&s->dg_mean, 2 * (size_t)row_d));
+        CK(dev_alloc(&s->dg_m2, 2 * (size_t)row_d));
+        CK(dev_alloc(&s->dg_out, (size_t)std::max(3, DIAG_T) * s->ld));
+    }
+    const uint64_t n_pairs = row_d / 2u;
+    hipLaunchKernelGGL(diag_split_moments_kernel, dim3((unsigned)((n_pairs + DIAG_THREADS - 1) / DIAG_THREADS), 2), dim3(DIAG_THREADS), 0, s->stream,
+                       (const double*)s->hist, row_d, n_pairs, (uint64_t)g_lo, (uint64_t)(g_hi - n), (uint32_t)n, s->dg_mean, s->dg_m2);
+    hipLaunchKernelGGL(diag_means_final_kernel, dim3(s->ld), dim3(DIAG_THREADS), 0, s->stream, (const double*)s->dg_mean, (const double*)s->dg_m2,
+                       2u * s->n_local, s->ld, (uint32_t)n, s->dg_out);
+    HIPCK(hipGetLastError());
+    std::vector<double> h(3 * (size_t)s->ld);
+    HIPCK(hipMemcpyAsync(h.data(), s->dg_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    for (uint32_t k = 0; k < s->dim; ++k) {
+        mean_of_means[k] = h[k];
+        m2_of_means[k] = h[s->ld + k];
+        sum_of_vars[k] = h[2 * (size_t)s->ld + k];
+    }
+    *n_half_chains = 2 * (int64_t)s->n_local;
+    *n_draws = n;
+    s->dg_g0 = g_lo; s->dg_g1 = g_hi; s->dg_n = n;
+    s->dg_tabs = s->t_abs; s->dg_rows = s->hist_rows; s->dg_epoch = s->hist_epoch;
+    s->dg_valid = true;
+    return 0;
+}
+
+// sum over this rank's half-chains of c_{j,t} (biased autocovariance about the half-chain's mean), t in [t0, t0 + n_lags):
+// out[(t - t0) * dim + k].  Window and means of the last bpm_diag_split_moments call.
+extern "C" int bpm_diag_autocov(bpm_handle_t s, int64_t t0, int32_t n_lags, double* out) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!out) return fail("bpm_diag_autocov: null argument");
+    if (!s->dg_valid) return fail("bpm_diag_autocov: call bpm_diag_split_moments first");
+    if (s->dg_epoch != s->hist_epoch || s->dg_tabs != s->t_abs || s->dg_rows != s->hist_rows || s->hist_rows != s->rows_logical)
+        return fail("bpm_diag_autocov: the history changed since bpm_diag_split_moments (a step, set_history or set_state); call it again");
+    if (t0 < 0 || n_lags < 1 || t0 + n_lags > s->dg_n)
+        return fail("bpm_diag_autocov: lags [t0, t0 + n_lags) must lie in [0, n) with n = " + std::to_string((long long)s->dg_n) +
+                    " draws per half-chain");
+    const uint64_t row_d = (uint64_t)s->n_local * s->ld;
+    const uint32_t kw = s->ld <= (uint32_t)DIAG_THREADS ? s->ld : (uint32_t)DIAG_THREADS;
+    const uint32_t n_kt = (s->ld + kw - 1) / kw, cpw = DIAG_THREADS / kw;
+    const uint32_t n_groups = (s->n_local + cpw - 1) / cpw;      // per half
+    // ~768 workgroups in all, what is resident at once (three per CU at this kernel's 138 VGPRs): each walks n_groups / nb column groups
+    const uint32_t nb = std::max(1u, std::min(n_groups, 384u / n_kt));
+    const size_t part_n = (size_t)2 * nb * DIAG_T * s->ld;
+    if (part_n > s->dg_part_cap) {
+        if (s->dg_part) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(s->dg_part)); s->dg_part = nullptr; s->dg_part_cap = 0; }
+        CK(dev_alloc(&s->dg_part, part_n));
+        s->dg_part_cap = part_n;
+    }
+    std::vector<double> h((size_t)DIAG_T * s->ld);
+    const int64_t r_lo1 = s->dg_g1 - s->dg_n;
+    for (int64_t b0 = t0; b0 < t0 + n_lags; b0 += DIAG_T) {
+        hipLaunchKernelGGL(diag_autocov_kernel, dim3(nb, n_kt, 2), dim3(DIAG_THREADS), 0, s->stream, (const double*)s->hist, row_d, s->n_local, s->ld,
+                           (uint64_t)s->dg_g0, (uint64_t)r_lo1, (uint32_t)s->dg_n, (uint32_t)b0, (const double*)s->dg_mean, kw, cpw, s->dg_part);
+        hipLaunchKernelGGL(diag_autocov_final_kernel, dim3((s->ld + DIAG_FIN_K - 1) / DIAG_FIN_K, DIAG_T), dim3(DIAG_THREADS), 0, s->stream,
+                           (const double*)s->dg_part, 2 * nb, s->ld, (uint32_t)s->dg_n, s->dg_out);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(h.data(), s->dg_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        const int64_t nl = std::min<int64_t>(DIAG_T, t0 + n_lags - b0);
+        for (int64_t l = 0; l < nl; ++l)
+            for (uint32_t k = 0; k < s->dim; ++k) out[(size_t)(b0 - t0 + l) * s->dim + k] = h[(size_t)l * s->ld + k];
+    }
     return 0;
 }
 

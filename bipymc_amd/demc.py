@@ -438,6 +438,16 @@ class DeMcMpi(object):
         S2 = np.sum([p[2] for p in parts], axis=0)
         return sh + S1 / n, np.sqrt(np.maximum(S2 / n - (S1 / n) ** 2, 0.0))
 
+    def convergence_diagnostics(self, n_burn=0, max_lag=None):
+        """Split-chain R-hat and effective sample size per coordinate over the history after n_burn super-chain rows (param_est's unit;
+        the window starts at the first whole generation), reduced on the GPU(s) without moving the history (bipymc_amd/diagnostics.py).
+        Collective: every rank calls it; every rank gets the same bits.  max_lag bounds the autocorrelation lags read (ess_capped says
+        where it ended the sum).  -> diagnostics.ConvergenceDiagnostics"""
+        from . import diagnostics as _diag
+        eng = self._engine
+        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
+        return _diag.compute(eng.diag_split_moments, eng.diag_autocov, self.comm.allgather, g0, g1, max_lag=max_lag)
+
     def super_chain_mpi(self, collection_rank=0):
         return self._super_chain(collection_rank)
 

@@ -410,6 +410,21 @@ class HipEngine(object):
         self._ck(self.lib.bpm_reduce_moments(self._h, int(n_burn), _dptr(s1), _dptr(s2), _dptr(sh), C.byref(n)))
         return int(n.value), s1, s2, sh
 
+    def diag_split_moments(self, g_lo, g_hi):
+        """-> (mean_of_means, m2_of_means, sum_of_vars, n_half_chains, n_draws): split-chain moments of this rank's chains over history rows
+        [g_lo, g_hi) (bpm_diag_split_moments; bipymc_amd/diagnostics.py finishes them)"""
+        mm = np.empty(self.dim); m2 = np.empty(self.dim); sv = np.empty(self.dim)
+        m = C.c_int64(0); n = C.c_int64(0)
+        self._ck(self.lib.bpm_diag_split_moments(self._h, int(g_lo), int(g_hi), _dptr(mm), _dptr(m2), _dptr(sv), C.byref(m), C.byref(n)))
+        return mm, m2, sv, int(m.value), int(n.value)
+
+    def diag_autocov(self, t0, n_lags):
+        """-> (n_lags, dim): sum over this rank's half-chains of the biased autocovariance at lags t0 ... t0 + n_lags - 1, on the window of the
+        last diag_split_moments call"""
+        out = np.empty((int(n_lags), self.dim))
+        self._ck(self.lib.bpm_diag_autocov(self._h, int(t0), int(n_lags), _dptr(out)))
+        return out
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

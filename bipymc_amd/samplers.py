@@ -107,6 +107,16 @@ class DeMc(object):
         """samplers.py:320-326: row g*n_chains + i = chain i at generation g."""
         return self._engine.get_history().reshape(-1, self.am_chains[0].dim).copy()
 
+    def convergence_diagnostics(self, n_burn=0, max_lag=None):
+        """Split-chain R-hat and effective sample size per coordinate over the super-chain rows after n_burn (the window starts at the
+        first whole generation), reduced on the GPU (bipymc_amd/diagnostics.py).  -> diagnostics.ConvergenceDiagnostics"""
+        from . import diagnostics as _diag
+        eng = self._engine
+        if eng is None:
+            raise RuntimeError("convergence_diagnostics: run_mcmc first")
+        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
+        return _diag.compute(eng.diag_split_moments, eng.diag_autocov, _diag.single_process_allgather, g0, g1, max_lag=max_lag)
+
     def param_est(self, n_burn):
         chain_slice = self.super_chain[n_burn:, :]                      # samplers.py:311-315
         return np.mean(chain_slice, axis=0), np.std(chain_slice, axis=0), chain_slice

@@ -291,6 +291,18 @@ int bpm_set_adapt_state(bpm_handle_t h, const double* p_cr, const double* delta_
 /* ln_like of n points (row-major (n, dim)) with the sampler's device target: what `ln_like_fn(theta)` returns for the shipped analytic
  * targets (utils/d100_gauss.py:14-35, dblgauss_rv.py:11-32, banana_rv.py:11-40) */
 int bpm_eval_loglike(bpm_handle_t h, const double* X, int32_t n, double* out);
+
+/* Split-chain moments of this rank's chains over history rows [g_lo, g_hi) (convergence diagnostics; absent from the reference).
+ * n = (g_hi - g_lo) / 2 draws per half-chain: rows [g_lo, g_lo + n) and [g_hi - n, g_hi) of every chain (the middle row of an odd window is
+ * dropped), 2 n_local half-chains.  Per coordinate (dim values each): mean of the half-chain means, sum of squared deviations of the
+ * half-chain means from it, sum of the half-chain variances (ddof 1).  Keeps the half-chain means on the device for bpm_diag_autocov.
+ * Errors: no resident history (keep_history = 0), n < 4.  bipymc_amd/diagnostics.py combines ranks and finishes R-hat and ESS. */
+int bpm_diag_split_moments(bpm_handle_t h, int64_t g_lo, int64_t g_hi, double* mean_of_means, double* m2_of_means,
+                           double* sum_of_vars, int64_t* n_half_chains, int64_t* n_draws);
+/* sum over this rank's half-chains of c_{j,t} = (1/n) sum_{i < n - t} (x_{j,i} - xbar_j)(x_{j,i+t} - xbar_j), t in [t0, t0 + n_lags),
+ * out[(t - t0) * dim + k]; window of the last bpm_diag_split_moments call, which must still describe the resident history (an error after
+ * a step, bpm_set_history or bpm_set_state); t0 + n_lags <= n. */
+int bpm_diag_autocov(bpm_handle_t h, int64_t t0, int32_t n_lags, double* out);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
