@@ -34,6 +34,7 @@
 #include "kernels.h"
 #include "kernels_wide.h"
 #include "diagnostics.h"
+#include "quantiles.h"
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -587,6 +588,14 @@ struct bpm_sampler {
     int64_t dg_g0 = 0, dg_g1 = 0, dg_n = 0, dg_tabs = 0, dg_rows = 0;
     uint64_t dg_epoch = 0;
     uint64_t hist_epoch = 0;        // bumped whenever the history is replaced (reset_history, bpm_set_history); generations bump t_abs
+    // posterior quantiles (quantiles.h, bpm_quantile_*): the window [qs_lo, qs_hi) of local super-chain rows fixed by the last
+    // bpm_quantile_begin, valid while the history is what that call saw (qs_epoch / qs_tabs / qs_rows); qs_buf holds one histogram request
+    // (histograms and NaN counts out, prefixes, coordinates and tiles in), qs_cap bytes
+    unsigned char* qs_buf = nullptr;
+    size_t qs_cap = 0;
+    bool qs_valid = false;
+    uint64_t qs_lo = 0, qs_hi = 0, qs_epoch = 0;
+    int64_t qs_tabs = 0, qs_rows = 0;
     double* om = nullptr;        // outlier check: world x [omega (n_local) | ln_like (n_local)], all-gathered in place
     double* sel = nullptr;       // outlier check: [0..3] order statistics around Q1 / Q3, [4] first argmax of omega
     unsigned char* sel_state = nullptr;   // radix-select state between the passes (SelState)
@@ -943,7 +952,7 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     void* ptrs[] = {s->tb[0].chunk_count, s->tb[1].chunk_count, s->hist_tmp, s->gen_sums, s->gs_shift, s->gs_part, s->arena, s->tab_peerG, s->tab_all, s->om, s->sel, s->sel_state, s->okeys, s->olist, s->G, s->ll, s->hist, s->llhist, s->w_mean, s->tparams, s->cr_state_base, s->cr_p1, s->cr_p2[0], s->cr_p2[1], s->counters, s->acc_count,
                     s->prop_buf, s->aux_buf, s->ids_buf, s->tb[0].perm, s->tb[0].inv, s->tb[0].plan, s->tb[0].sidx, s->tb[0].plan_count,
                     s->tb[1].perm, s->tb[1].inv, s->tb[1].plan, s->tb[1].sidx, s->tb[1].plan_count, s->gamma_tab, s->x_next, s->accbits_all, s->PK, s->xstat, s->ckpt_G, s->ckpt_ll, s->ckpt_acc, s->ckpt_counters, s->trace_i32, s->trace_f64, s->trace_mask, s->scratch,
-                    s->dg_mean, s->dg_m2, s->dg_out, s->dg_part};
+                    s->dg_mean, s->dg_m2, s->dg_out, s->dg_part, s->qs_buf};
     if (free_buffers)
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
@@ -3027,6 +3036,105 @@ extern "C" int bpm_diag_autocov(bpm_handle_t s, int64_t t0, int32_t n_lags, doub
         for (int64_t l = 0; l < nl; ++l)
             for (uint32_t k = 0; k < s->dim; ++k) out[(size_t)(b0 - t0 + l) * s->dim + k] = h[(size_t)l * s->ld + k];
     }
+    return 0;
+}
+
+// ---- posterior quantiles (quantiles.h; bipymc_amd/quantiles.py runs the select) --------------------------------------------------------
+// Fixes the window of super-chain rows >= n_burn (param_est's unit, the selection of bpm_reduce_moments: a partial first generation by chain
+// index) and returns how many of them this rank holds.  bpm_quantile_histogram then counts over that window while the history is unchanged.
+extern "C" int bpm_quantile_begin(bpm_handle_t s, int64_t n_burn, int64_t* count) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    s->qs_valid = false;
+    if (!count) return fail("bpm_quantile_begin: null argument");
+    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        return fail("bpm_quantile_begin: needs keep_history=True (a resident history of every generation)");
+    if (n_burn < 0) n_burn = 0;
+    const int64_t g0 = n_burn / s->N;
+    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
+    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
+    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));
+    const uint64_t m_lo = (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0);
+    const uint64_t m_hi = (uint64_t)s->hist_rows * s->n_local;
+    s->qs_lo = std::min(m_lo, m_hi);
+    s->qs_hi = m_hi;
+    s->qs_epoch = s->hist_epoch; s->qs_tabs = s->t_abs; s->qs_rows = s->hist_rows;
+    s->qs_valid = true;
+    *count = (int64_t)(s->qs_hi - s->qs_lo);
+    return 0;
+}
+
+// n_prefix (coordinate, prefix) slots, sorted by coordinate, prefixes of one coordinate strictly increasing; each a prefix of `prefix_bits`
+// bits (0, 8, ..., 56) of the keys.  hist[j * 256 + b]: keys of coordinate prefix_dim[j] in the window whose top bits equal prefixes[j] and
+// whose next 8 bits are b; n_nan[j] (may be null): how many of those are NaN.
+extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const int32_t* prefix_dim, const uint64_t* prefixes,
+                                      int32_t prefix_bits, uint64_t* hist, int64_t* n_nan) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!prefix_dim || !prefixes || !hist) return fail("bpm_quantile_histogram: null argument");
+    if (!s->qs_valid) return fail("bpm_quantile_histogram: call bpm_quantile_begin first");
+    if (s->qs_epoch != s->hist_epoch || s->qs_tabs != s->t_abs || s->qs_rows != s->hist_rows || s->hist_rows != s->rows_logical)
+        return fail("bpm_quantile_histogram: the history changed since bpm_quantile_begin (a step, set_history or set_state); call it again");
+    if (prefix_bits < 0 || prefix_bits > 56 || prefix_bits % 8 != 0)
+        return fail("bpm_quantile_histogram: prefix_bits must be one of 0, 8, ..., 56");
+    if (n_prefix < 1 || n_prefix > ((int64_t)1 << 24)) return fail("bpm_quantile_histogram: n_prefix out of range");
+    const uint32_t bits = (uint32_t)prefix_bits;
+    for (int64_t j = 0; j < n_prefix; ++j) {
+        if (prefix_dim[j] < 0 || (uint32_t)prefix_dim[j] >= s->dim) return fail("bpm_quantile_histogram: coordinate out of range");
+        if (bits == 0 ? prefixes[j] != 0 : (prefixes[j] >> bits) != 0)
+            return fail("bpm_quantile_histogram: a prefix has more than prefix_bits bits");
+        if (j > 0 && (prefix_dim[j] < prefix_dim[j - 1] || (prefix_dim[j] == prefix_dim[j - 1] && prefixes[j] <= prefixes[j - 1])))
+            return fail("bpm_quantile_histogram: slots must be sorted by coordinate, prefixes of a coordinate strictly increasing");
+    }
+    // tiles of at most QS_SLOTS slots over at most QS_SLOTS coordinates
+    std::vector<uint32_t> tiles;
+    for (int64_t j = 0; j < n_prefix;) {
+        const int64_t j0 = j;
+        const uint32_t k0 = (uint32_t)prefix_dim[j0];
+        while (j < n_prefix && j - j0 < QS_SLOTS && (uint32_t)prefix_dim[j] - k0 < (uint32_t)QS_SLOTS) ++j;
+        tiles.insert(tiles.end(), {(uint32_t)j0, (uint32_t)(j - j0), k0, (uint32_t)prefix_dim[j - 1] - k0 + 1u});
+    }
+    const size_t n_tiles = tiles.size() / 4;
+    const size_t np = (size_t)n_prefix;
+    // qs_buf: [hist np x 256 u64 | n_nan np u64 | prefixes np u64 | tiles n_tiles x 16 B (16-byte aligned) | coordinates np u32]
+    const size_t o_nan = np * 256 * 8, o_pv = o_nan + np * 8, o_tiles = (o_pv + np * 8 + 15) / 16 * 16, o_pk = o_tiles + n_tiles * 16,
+                 need = o_pk + np * 4;
+    if (need > s->qs_cap) {
+        if (s->qs_buf) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(s->qs_buf)); s->qs_buf = nullptr; s->qs_cap = 0; }
+        CK(dev_alloc(&s->qs_buf, need));
+        s->qs_cap = need;
+    }
+    std::vector<unsigned char> in(need - o_pv);
+    std::memcpy(in.data(), prefixes, np * 8);
+    std::memcpy(in.data() + (o_tiles - o_pv), tiles.data(), n_tiles * 16);
+    for (size_t j = 0; j < np; ++j) {
+        const uint32_t k = (uint32_t)prefix_dim[j];
+        std::memcpy(in.data() + (o_pk - o_pv) + 4 * j, &k, 4);
+    }
+    HIPCK(hipMemsetAsync(s->qs_buf, 0, o_pv, s->stream));
+    HIPCK(hipMemcpyAsync(s->qs_buf + o_pv, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
+    const uint64_t rows = s->qs_hi - s->qs_lo;
+    if (rows > 0) {
+        uint32_t kw_min = QS_SLOTS;
+        for (size_t t = 0; t < n_tiles; ++t) kw_min = std::min(kw_min, tiles[4 * t + 3]);
+        const uint64_t cpw = (uint64_t)(QS_THREADS / kw_min);
+        // ~2048 workgroups in all (four resident per CU), each at least 4 x QS_UNR row groups; a workgroup's uint32 bins stay below 2^31
+        uint64_t nby = std::max<uint64_t>(1, 2048 / n_tiles);
+        nby = std::min<uint64_t>(nby, (rows + 4 * QS_UNR * cpw - 1) / (4 * QS_UNR * cpw));
+        nby = std::max<uint64_t>(nby, (rows >> 31) + 1);
+        if (nby > 65535) return fail("bpm_quantile_histogram: window too large");
+        hipLaunchKernelGGL(qs_histogram_kernel, dim3((unsigned)n_tiles, (unsigned)nby), dim3(QS_THREADS), 0, s->stream, (const double*)s->hist,
+                           s->ld, s->qs_lo, s->qs_hi, reinterpret_cast<const uint4*>(s->qs_buf + o_tiles),
+                           reinterpret_cast<const uint32_t*>(s->qs_buf + o_pk), reinterpret_cast<const uint64_t*>(s->qs_buf + o_pv), bits,
+                           reinterpret_cast<unsigned long long*>(s->qs_buf), reinterpret_cast<unsigned long long*>(s->qs_buf + o_nan));
+        HIPCK(hipGetLastError());
+    }
+    std::vector<uint64_t> out(np * 257);
+    HIPCK(hipMemcpyAsync(out.data(), s->qs_buf, o_pv, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    std::memcpy(hist, out.data(), np * 256 * 8);
+    if (n_nan)
+        for (size_t j = 0; j < np; ++j) n_nan[j] = (int64_t)out[np * 256 + j];
     return 0;
 }
 

@@ -448,6 +448,14 @@ class DeMcMpi(object):
         g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
         return _diag.compute(eng.diag_split_moments, eng.diag_autocov, self.comm.allgather, g0, g1, max_lag=max_lag)
 
+    def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
+        """np.quantile(param_est(n_burn)[2], q, axis=0), exactly, computed on the GPU(s) without moving the history (an MSD radix select,
+        bipymc_amd/quantiles.py).  Collective: every rank calls it; every rank gets the same bits.  -> (len(q), dim), or (dim,) for a
+        scalar q"""
+        from . import quantiles as _qs
+        eng = self._engine
+        return _qs.compute(eng.quantile_begin, eng.quantile_histogram, self.comm.allgather, n_burn, q, dim=eng.dim)
+
     def super_chain_mpi(self, collection_rank=0):
         return self._super_chain(collection_rank)
 

@@ -425,6 +425,24 @@ class HipEngine(object):
         self._ck(self.lib.bpm_diag_autocov(self._h, int(t0), int(n_lags), _dptr(out)))
         return out
 
+    def quantile_begin(self, n_burn):
+        """-> this rank's number of super-chain rows >= n_burn (the window of the quantile_histogram calls that follow; bpm_quantile_begin)"""
+        n = C.c_int64(0)
+        self._ck(self.lib.bpm_quantile_begin(self._h, int(n_burn), C.byref(n)))
+        return int(n.value)
+
+    def quantile_histogram(self, prefix_dim, prefixes, bits):
+        """-> (hist (n_prefix, 256) uint64, n_nan (n_prefix,) int64): this rank's keys of the window under each (coordinate, prefix) slot by
+        their next 8 bits (bpm_quantile_histogram; bipymc_amd/quantiles.py runs the select)"""
+        pk = np.ascontiguousarray(prefix_dim, dtype=np.int32)
+        pv = np.ascontiguousarray(prefixes, dtype=np.uint64)
+        hist = np.empty((len(pk), 256), dtype=np.uint64)
+        nn = np.empty(len(pk), dtype=np.int64)
+        self._ck(self.lib.bpm_quantile_histogram(self._h, len(pk), pk.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 pv.ctypes.data_as(C.POINTER(C.c_uint64)), int(bits),
+                                                 hist.ctypes.data_as(C.POINTER(C.c_uint64)), nn.ctypes.data_as(C.POINTER(C.c_int64))))
+        return hist, nn
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

@@ -117,6 +117,15 @@ class DeMc(object):
         g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
         return _diag.compute(eng.diag_split_moments, eng.diag_autocov, _diag.single_process_allgather, g0, g1, max_lag=max_lag)
 
+    def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
+        """np.quantile(param_est(n_burn)[2], q, axis=0), exactly, computed on the GPU without moving the history (bipymc_amd/quantiles.py).
+        -> (len(q), dim), or (dim,) for a scalar q"""
+        from . import quantiles as _qs
+        eng = self._engine
+        if eng is None:
+            raise RuntimeError("param_est_quantiles: run_mcmc first")
+        return _qs.compute(eng.quantile_begin, eng.quantile_histogram, _qs.single_process_allgather, n_burn, q, dim=eng.dim)
+
     def param_est(self, n_burn):
         chain_slice = self.super_chain[n_burn:, :]                      # samplers.py:311-315
         return np.mean(chain_slice, axis=0), np.std(chain_slice, axis=0), chain_slice

@@ -303,6 +303,20 @@ int bpm_diag_split_moments(bpm_handle_t h, int64_t g_lo, int64_t g_hi, double* m
  * out[(t - t0) * dim + k]; window of the last bpm_diag_split_moments call, which must still describe the resident history (an error after
  * a step, bpm_set_history or bpm_set_state); t0 + n_lags <= n. */
 int bpm_diag_autocov(bpm_handle_t h, int64_t t0, int32_t n_lags, double* out);
+
+/* Exact quantiles of the super chain on the device (what `np.quantile(param_est(n_burn)[2], q, axis=0)` computes on the host after
+ * gathering the history, and the 5/50/95 percentiles the reference prints, mc_plot/vis_mcmc_chains.py:76): the histograms of an MSD radix
+ * select over order-preserving 64-bit keys (negative -> all bits flipped, else sign bit set, every NaN -> ~0); bipymc_amd/quantiles.py
+ * runs the select across ranks and NumPy's linear interpolation.
+ * bpm_quantile_begin fixes the window -- super-chain rows >= n_burn, a partial first generation by chain index, as bpm_reduce_moments --
+ * and returns this rank's number of rows in it.  Errors: no resident history (keep_history = 0). */
+int bpm_quantile_begin(bpm_handle_t h, int64_t n_burn, int64_t* count);
+/* n_prefix slots (prefix_dim[j], prefixes[j]), sorted by coordinate, prefixes of a coordinate strictly increasing, each of prefix_bits bits
+ * (0, 8, ..., 56).  hist[j * 256 + b] = keys of coordinate prefix_dim[j] in the window whose top prefix_bits bits are prefixes[j] and whose
+ * next 8 bits are b; n_nan[j] (may be NULL) = how many of them are NaN.  An error once the history changed since bpm_quantile_begin (a
+ * step, bpm_set_history or bpm_set_state). */
+int bpm_quantile_histogram(bpm_handle_t h, int64_t n_prefix, const int32_t* prefix_dim, const uint64_t* prefixes, int32_t prefix_bits,
+                           uint64_t* hist, int64_t* n_nan);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
