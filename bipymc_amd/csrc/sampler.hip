@@ -35,6 +35,7 @@
 #include "kernels_wide.h"
 #include "diagnostics.h"
 #include "quantiles.h"
+#include "covariance.h"
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -3135,6 +3136,101 @@ extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const in
     std::memcpy(hist, out.data(), np * 256 * 8);
     if (n_nan)
         for (size_t j = 0; j < np; ++j) n_nan[j] = (int64_t)out[np * 256 + j];
+    return 0;
+}
+
+// ---- posterior covariance (covariance.h; bipymc_amd/covariance.py chooses the centre, merges the ranks and finishes cov / corr) ---------
+// Over the window of super-chain rows >= n_burn (bpm_reduce_moments' selection): sum[k] = sum (x_k - center_k), cross[i * dim + j] = sum
+// (x_i - center_i)(x_j - center_j) (full and exactly symmetric), count = this rank's rows.  Keeps no state; every buffer is temporary.
+namespace {
+struct CovBuffers {
+    double* center = nullptr;
+    double* part = nullptr;
+    double* part1 = nullptr;
+    double* cross = nullptr;
+    double* sum = nullptr;
+    ~CovBuffers() {
+        for (double* p : {center, part, part1, cross, sum})
+            if (p) (void)hipFree(p);
+    }
+};
+template <int T>
+void cov_launch_diag(dim3 grid, hipStream_t st, const double* H, uint32_t ld, uint32_t dim, uint64_t r_lo, uint64_t r_hi, const double* c,
+                     uint32_t n_blk, double* part, double* part1) {
+    hipLaunchKernelGGL((cov_partial_kernel<T, true>), grid, dim3(64), 0, st, H, ld, dim, r_lo, r_hi, c, n_blk, part, part1);
+}
+}  // namespace
+constexpr uint32_t COV_DIM_LIMIT = 16384;      // 256 blocks of COV_BLK tiles: 32640 block pairs, below the grid's 65535
+
+extern "C" int bpm_reduce_cov(bpm_handle_t s, int64_t n_burn, const double* center, double* sum, double* cross, int64_t* count) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!center || !sum || !cross || !count) return fail("bpm_reduce_cov: null argument");
+    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        return fail("bpm_reduce_cov: needs keep_history=True (a resident history of every generation)");
+    const uint32_t dim = s->dim;
+    if (dim > COV_DIM_LIMIT)
+        return fail("bpm_reduce_cov: dim = " + std::to_string(dim) + " is beyond the supported limit of " + std::to_string(COV_DIM_LIMIT) +
+                    " coordinates");
+    if (n_burn < 0) n_burn = 0;
+    const int64_t g0 = n_burn / s->N;
+    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
+    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
+    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));      // a partial first generation is counted by chain index
+    const uint64_t r_hi = (uint64_t)s->hist_rows * s->n_local;
+    const uint64_t r_lo = std::min(r_hi, (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0));
+    const uint64_t rows = r_hi - r_lo;
+    *count = (int64_t)rows;
+    if (rows == 0) {
+        HIPCK(hipStreamSynchronize(s->stream));
+        std::fill(sum, sum + dim, 0.0);
+        std::fill(cross, cross + (size_t)dim * dim, 0.0);
+        return 0;
+    }
+    const uint32_t n_tiles = (dim + 15u) / 16u;
+    const uint32_t T = n_tiles <= (uint32_t)COV_MAX_T ? n_tiles : (uint32_t)COV_BLK;
+    const uint32_t n_blk = (n_tiles + T - 1u) / T;
+    const uint32_t n_off = n_blk * (n_blk - 1u) / 2u, n_slots = n_blk + n_off;
+    // one wavefront per workgroup: one per SIMD where the accumulators take more than half of the register file, two otherwise
+    const uint64_t n_grp = (rows + 3u) / 4u;
+    const uint32_t want = T > (uint32_t)COV_BLK ? 1024u : 2048u;
+    const uint32_t nbx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want / std::max(n_blk, std::max(n_off, 1u)),
+                                                                            (n_grp + COV_UNR - 1) / COV_UNR));
+    const size_t part_n = (size_t)n_slots * nbx * T * T * 256, part1_n = (size_t)n_blk * nbx * T * 64, cross_n = (size_t)dim * dim;
+    const size_t need = (part_n + part1_n + cross_n + 2 * (size_t)dim) * sizeof(double);
+    size_t mem_free = 0, mem_total = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free)
+        return fail("bpm_reduce_cov: dim = " + std::to_string(dim) + " needs " + std::to_string(need >> 20) +
+                    " MiB of device memory for the dim x dim result and its partial sums; " + std::to_string(mem_free >> 20) + " MiB are free");
+    CovBuffers b;
+    CK(dev_alloc(&b.center, dim));
+    CK(dev_alloc(&b.part, part_n));
+    CK(dev_alloc(&b.part1, part1_n));
+    CK(dev_alloc(&b.cross, cross_n));
+    CK(dev_alloc(&b.sum, dim));
+    HIPCK(hipMemcpyAsync(b.center, center, dim * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    const dim3 gd(nbx, n_blk);
+    const double* H = s->hist;
+    switch (T) {
+        case 1: cov_launch_diag<1>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 2: cov_launch_diag<2>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 3: cov_launch_diag<3>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 4: cov_launch_diag<4>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 5: cov_launch_diag<5>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 6: cov_launch_diag<6>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        default: cov_launch_diag<7>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+    }
+    if (n_off > 0)
+        hipLaunchKernelGGL((cov_partial_kernel<COV_BLK, false>), dim3(nbx, n_off), dim3(64), 0, s->stream, H, s->ld, dim, r_lo, r_hi,
+                           (const double*)b.center, n_blk, b.part, b.part1);
+    hipLaunchKernelGGL(cov_final_kernel, dim3(T * T, n_slots), dim3(COV_FIN_THREADS), 0, s->stream, (const double*)b.part, nbx, T, n_blk, dim,
+                       b.cross);
+    hipLaunchKernelGGL(cov_sum_final_kernel, dim3(n_tiles), dim3(256), 0, s->stream, (const double*)b.part1, nbx, T, dim, b.sum);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(cross, b.cross, cross_n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(sum, b.sum, dim * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }
 

@@ -456,6 +456,15 @@ class DeMcMpi(object):
         eng = self._engine
         return _qs.compute(eng.quantile_begin, eng.quantile_histogram, self.comm.allgather, n_burn, q, dim=eng.dim)
 
+    def param_est_cov(self, n_burn=0):
+        """Posterior mean, covariance (ddof = 1) and, through .corr(), correlation of the super-chain rows >= n_burn: what
+        np.cov(param_est(n_burn)[2], rowvar=False) computes, reduced on the GPU(s) without moving the history (an FP64 matrix-core SYRK
+        centred on the global mean, bipymc_amd/covariance.py).  Collective: every rank calls it; every rank gets the same bits.
+        -> covariance.PosteriorCovariance(mean, cov, n)"""
+        from . import covariance as _cov
+        eng = self._engine
+        return _cov.compute(eng.reduce_moments, eng.reduce_cov, self.comm.allgather, n_burn, eng.dim)
+
     def super_chain_mpi(self, collection_rank=0):
         return self._super_chain(collection_rank)
 

@@ -443,6 +443,15 @@ class HipEngine(object):
                                                  hist.ctypes.data_as(C.POINTER(C.c_uint64)), nn.ctypes.data_as(C.POINTER(C.c_int64))))
         return hist, nn
 
+    def reduce_cov(self, n_burn, center):
+        """-> (count, S1 (dim,), S2 (dim, dim)): sum (x - center) and sum (x - center)(x - center)^T over the local super-chain rows >= n_burn
+        (bpm_reduce_cov; bipymc_amd/covariance.py merges the ranks and finishes the covariance)"""
+        c = None if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(self.dim)
+        s1 = np.empty(self.dim); s2 = np.empty((self.dim, self.dim))
+        n = C.c_int64(0)
+        self._ck(self.lib.bpm_reduce_cov(self._h, int(n_burn), None if c is None else _dptr(c), _dptr(s1), _dptr(s2), C.byref(n)))
+        return int(n.value), s1, s2
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

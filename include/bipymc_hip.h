@@ -317,6 +317,15 @@ int bpm_quantile_begin(bpm_handle_t h, int64_t n_burn, int64_t* count);
  * step, bpm_set_history or bpm_set_state). */
 int bpm_quantile_histogram(bpm_handle_t h, int64_t n_prefix, const int32_t* prefix_dim, const uint64_t* prefixes, int32_t prefix_bits,
                            uint64_t* hist, int64_t* n_nan);
+/* Centred sums of the super chain on the device (posterior covariance; the reference looks at it through corner.corner over the gathered
+ * samples, mc_plot/mc_plot.py:16-29): over this rank's rows of the window of bpm_reduce_moments (super-chain rows >= n_burn, a partial first
+ * generation by chain index), sum[k] = sum (x_k - center_k) (dim values) and cross[i * dim + j] = sum (x_i - center_i)(x_j - center_j)
+ * (dim x dim, row-major, full and exactly symmetric), count = the rows.  FP64 matrix-core SYRK over the resident history; per-workgroup
+ * partial sums are added in a fixed order, so the same history gives the same bits.  Keeps no state between calls and writes nothing the
+ * samplers read.  bipymc_amd/covariance.py centres on the global mean, merges the ranks and finishes cov = (S2 - S1 S1^T / n) / (n - 1).
+ * Errors: no resident history (keep_history = 0); dim beyond 16384, or a dim x dim result and partial sums larger than the free device
+ * memory (the message names the limit). */
+int bpm_reduce_cov(bpm_handle_t h, int64_t n_burn, const double* center, double* sum, double* cross, int64_t* count);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
