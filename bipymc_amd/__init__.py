@@ -11,3 +11,4 @@ from .demc import DeMcMpi  # noqa: F401
 from .dream import DreamMpi  # noqa: F401
 from .device_likelihood import HipLikelihood  # noqa: F401
 from .covariance import PosteriorCovariance  # noqa: F401
+from .histograms import PosteriorHistograms  # noqa: F401

@@ -106,6 +106,9 @@ SIGNATURES = {
     "bpm_quantile_begin": (C.c_int, [_H, C.c_int64, _P(C.c_int64)]),
     "bpm_quantile_histogram": (C.c_int, [_H, C.c_int64, _P(C.c_int32), _P(C.c_uint64), C.c_int32, _P(C.c_uint64), _P(C.c_int64)]),
     "bpm_reduce_cov": (C.c_int, [_H, C.c_int64, _dp, _dp, _dp, _P(C.c_int64)]),
+    "bpm_hist_range": (C.c_int, [_H, C.c_int64, _dp, _dp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
+    "bpm_hist_marginals": (C.c_int, [_H, C.c_int32, _P(C.c_int32), C.c_int32, _dp, _P(C.c_int64)]),
+    "bpm_hist_pairs": (C.c_int, [_H, C.c_int32, _P(C.c_int32), C.c_int32, _dp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only
@@ -146,7 +149,7 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

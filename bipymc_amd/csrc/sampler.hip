@@ -36,6 +36,7 @@
 #include "diagnostics.h"
 #include "quantiles.h"
 #include "covariance.h"
+#include "histograms.h"
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -597,6 +598,11 @@ struct bpm_sampler {
     bool qs_valid = false;
     uint64_t qs_lo = 0, qs_hi = 0, qs_epoch = 0;
     int64_t qs_tabs = 0, qs_rows = 0;
+    // posterior histograms (histograms.h, bpm_hist_*): the window fixed by the last bpm_hist_range, valid while the history is what that
+    // call saw; every device buffer of these calls is temporary
+    bool hs_valid = false;
+    uint64_t hs_lo = 0, hs_hi = 0, hs_epoch = 0;
+    int64_t hs_tabs = 0, hs_rows = 0;
     double* om = nullptr;        // outlier check: world x [omega (n_local) | ln_like (n_local)], all-gathered in place
     double* sel = nullptr;       // outlier check: [0..3] order statistics around Q1 / Q3, [4] first argmax of omega
     unsigned char* sel_state = nullptr;   // radix-select state between the passes (SelState)
@@ -3230,6 +3236,234 @@ extern "C" int bpm_reduce_cov(bpm_handle_t s, int64_t n_burn, const double* cent
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(cross, b.cross, cross_n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(sum, b.sum, dim * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// ---- posterior histograms (histograms.h; bipymc_amd/histograms.py applies NumPy's range rules, builds the edges and merges the ranks) ----
+// The counts of the reference's corner plot (corner.corner(samples), mc_plot/mc_plot.py:16-29), taken where the history lives.
+namespace {
+struct HistBuffers {
+    unsigned char* p = nullptr;
+    ~HistBuffers() {
+        if (p) (void)hipFree(p);
+    }
+};
+int hist_window_check(bpm_sampler* s, const char* who) {
+    if (!s->hs_valid) return fail(std::string(who) + ": call bpm_hist_range first");
+    if (s->hs_epoch != s->hist_epoch || s->hs_tabs != s->t_abs || s->hs_rows != s->hist_rows || s->hist_rows != s->rows_logical)
+        return fail(std::string(who) + ": the history changed since bpm_hist_range (a step, set_history or set_state); call it again");
+    return 0;
+}
+int hist_alloc(HistBuffers& b, size_t need, const char* who, const std::string& what) {
+    size_t mem_free = 0, mem_total = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free)
+        return fail(std::string(who) + ": " + what + " need " + std::to_string(need >> 20) + " MiB of device memory; " +
+                    std::to_string(mem_free >> 20) + " MiB are free");
+    CK(dev_alloc(&b.p, need));
+    return 0;
+}
+// workgroups along the rows: about `want` in all, each at least 4 sweeps of `rows_per_sweep`, none with 2^31 rows or more
+int hist_nby(uint64_t rows, uint64_t n_tiles, uint64_t rows_per_sweep, const char* who, uint64_t* nby_out) {
+    uint64_t nby = std::max<uint64_t>(1, 2048 / n_tiles);
+    nby = std::min<uint64_t>(nby, (rows + 4 * rows_per_sweep - 1) / (4 * rows_per_sweep));
+    nby = std::max<uint64_t>(nby, (rows >> 31) + 1);
+    if (nby > 65535) return fail(std::string(who) + ": window too large");
+    *nby_out = nby;
+    return 0;
+}
+}  // namespace
+constexpr uint32_t HS_LDS_TILE = 40u * 1024u;       // edges + one copy of the counts of a marginal tile
+constexpr uint32_t HS_LDS_TOTAL = 48u * 1024u;      // ... with the extra copies
+constexpr uint32_t HS_LDS_PAIRS = 32u * 1024u;      // the 2-D counts of a pair tile
+constexpr uint32_t HS_TILE_PAIRS = 64;              // pairs per tile at most (128 distinct slots: two rows side by side in phase 1)
+
+// Fixes the window of super-chain rows >= n_burn (bpm_reduce_moments' selection) for the bpm_hist_marginals / bpm_hist_pairs calls that
+// follow and returns, per coordinate over this rank's rows: lo / hi = min / max of the values that are not NaN (+inf / -inf where there is
+// none), n_nan and n_inf = how many are NaN / infinite; count = the rows.
+extern "C" int bpm_hist_range(bpm_handle_t s, int64_t n_burn, double* lo, double* hi, int64_t* n_nan, int64_t* n_inf, int64_t* count) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    s->hs_valid = false;
+    if (!lo || !hi || !n_nan || !n_inf || !count) return fail("bpm_hist_range: null argument");
+    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        return fail("bpm_hist_range: needs keep_history=True (a resident history of every generation)");
+    if (n_burn < 0) n_burn = 0;
+    const int64_t g0 = n_burn / s->N;
+    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
+    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
+    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));      // a partial first generation is counted by chain index
+    const uint64_t m_lo = (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0);
+    const uint64_t m_hi = (uint64_t)s->hist_rows * s->n_local;
+    s->hs_lo = std::min(m_lo, m_hi);
+    s->hs_hi = m_hi;
+    s->hs_epoch = s->hist_epoch; s->hs_tabs = s->t_abs; s->hs_rows = s->hist_rows;
+    s->hs_valid = true;
+    const uint64_t rows = s->hs_hi - s->hs_lo;
+    *count = (int64_t)rows;
+    const uint32_t ld = s->ld, dim = s->dim;
+    const uint64_t k_pinf = 0xFFF0000000000000ull, k_ninf = 0x000FFFFFFFFFFFFFull;      // qs_key(+inf), qs_key(-inf)
+    std::vector<uint64_t> out((size_t)4 * ld, 0);
+    std::fill(out.begin(), out.begin() + ld, k_pinf);
+    std::fill(out.begin() + ld, out.begin() + 2 * (size_t)ld, k_ninf);
+    if (rows > 0) {
+        HistBuffers b;
+        CK(hist_alloc(b, out.size() * 8, "bpm_hist_range", "the per-coordinate results"));
+        HIPCK(hipMemcpyAsync(b.p, out.data(), out.size() * 8, hipMemcpyHostToDevice, s->stream));
+        const uint32_t kw = std::min<uint32_t>(ld, HS_THREADS), n_tiles = (ld + kw - 1) / kw;
+        uint64_t nby = 1;
+        CK(hist_nby(rows, n_tiles, (uint64_t)(HS_THREADS / kw) * HS_UNR, "bpm_hist_range", &nby));
+        hipLaunchKernelGGL(hs_range_kernel, dim3(n_tiles, (unsigned)nby), dim3(HS_THREADS), 0, s->stream, (const double*)s->hist, ld, s->hs_lo,
+                           s->hs_hi, kw, reinterpret_cast<unsigned long long*>(b.p));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(out.data(), b.p, out.size() * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+    }
+    auto unkey = [](uint64_t k) {
+        const uint64_t bits = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+        double x;
+        std::memcpy(&x, &bits, 8);
+        return x;
+    };
+    for (uint32_t k = 0; k < dim; ++k) {
+        lo[k] = unkey(out[k]);
+        hi[k] = unkey(out[(size_t)ld + k]);
+        n_nan[k] = (int64_t)out[(size_t)2 * ld + k];
+        n_inf[k] = (int64_t)out[(size_t)3 * ld + k];
+    }
+    return 0;
+}
+
+// counts[j * bins + i] = rows of the window of the last bpm_hist_range whose coordinate dims[j] lies in bin i of edges[j * (bins + 1) ...]
+// (e[i] <= x < e[i + 1], the last bin closed; NaN and values outside are counted nowhere): np.histogram's counts for these edges.
+extern "C" int bpm_hist_marginals(bpm_handle_t s, int32_t n_dims, const int32_t* dims, int32_t bins, const double* edges, int64_t* counts) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!dims || !edges || !counts) return fail("bpm_hist_marginals: null argument");
+    CK(hist_window_check(s, "bpm_hist_marginals"));
+    if (bins < 1 || bins > HS_MAX_BINS)
+        return fail("bpm_hist_marginals: bins = " + std::to_string(bins) + " is outside the supported 1 ... " + std::to_string(HS_MAX_BINS));
+    if (n_dims < 1 || (uint32_t)n_dims > s->dim) return fail("bpm_hist_marginals: n_dims must be 1 ... dim");
+    const uint32_t m = (uint32_t)n_dims, nb = (uint32_t)bins;
+    for (uint32_t j = 0; j < m; ++j) {
+        if (dims[j] < 0 || (uint32_t)dims[j] >= s->dim) return fail("bpm_hist_marginals: coordinate out of range");
+        const double* e = edges + (size_t)j * (nb + 1);
+        for (uint32_t i = 0; i <= nb; ++i)
+            if (!std::isfinite(e[i]) || (i > 0 && e[i] < e[i - 1])) return fail("bpm_hist_marginals: edges must be finite and non-decreasing");
+    }
+    const size_t n_counts = (size_t)m * nb, n_edges = (size_t)m * (nb + 1);
+    std::fill(counts, counts + n_counts, (int64_t)0);
+    const uint64_t rows = s->hs_hi - s->hs_lo;
+    if (rows == 0) return 0;
+    // [counts u64 | edges f64 | dims u32]
+    const size_t o_e = n_counts * 8, o_d = o_e + n_edges * 8, need = o_d + (size_t)m * 4;
+    HistBuffers b;
+    CK(hist_alloc(b, need, "bpm_hist_marginals", "the counts and edges"));
+    std::vector<unsigned char> in(need - o_e);
+    std::memcpy(in.data(), edges, n_edges * 8);
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t k = (uint32_t)dims[j];
+        std::memcpy(in.data() + (o_d - o_e) + 4 * (size_t)j, &k, 4);
+    }
+    HIPCK(hipMemsetAsync(b.p, 0, o_e, s->stream));
+    HIPCK(hipMemcpyAsync(b.p + o_e, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
+    // a tile: kw slots whose edges and counts fit HS_LDS_TILE; rep copies of the counts while they fit HS_LDS_TOTAL
+    const uint32_t slot_bytes = nb * 4 + (nb + 1) * 8;
+    const uint32_t kw = std::max(1u, std::min({m, (uint32_t)HS_THREADS, HS_LDS_TILE / slot_bytes}));
+    const uint32_t n_tiles = (m + kw - 1) / kw, cpw = HS_THREADS / kw;
+    const uint32_t rep = std::max(1u, std::min({8u, cpw, (HS_LDS_TOTAL - kw * (nb + 1) * 8) / (kw * nb * 4)}));
+    const uint32_t lds = kw * (nb + 1) * 8 + rep * kw * nb * 4;
+    uint64_t nby = 1;
+    CK(hist_nby(rows, n_tiles, (uint64_t)cpw * HS_UNR, "bpm_hist_marginals", &nby));
+    hipLaunchKernelGGL(hs_marginal_kernel, dim3(n_tiles, (unsigned)nby), dim3(HS_THREADS), lds, s->stream, (const double*)s->hist, s->ld,
+                       s->hs_lo, s->hs_hi, reinterpret_cast<const uint32_t*>(b.p + o_d), m, nb, reinterpret_cast<const double*>(b.p + o_e), kw,
+                       rep, reinterpret_cast<unsigned long long*>(b.p));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(counts, b.p, o_e, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// counts2d[(p * bins2d + i) * bins2d + j] = rows of that window whose coordinate dims[pair_a[p]] lies in bin i of edges2d[pair_a[p]] and
+// whose coordinate dims[pair_b[p]] lies in bin j of edges2d[pair_b[p]] (pair_a / pair_b index dims; the binning rule of the marginals):
+// np.histogram2d's counts for these edges.
+extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dims, int32_t bins2d, const double* edges2d, int64_t n_pairs,
+                              const int32_t* pair_a, const int32_t* pair_b, int64_t* counts2d) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!dims || !edges2d || !pair_a || !pair_b || !counts2d) return fail("bpm_hist_pairs: null argument");
+    CK(hist_window_check(s, "bpm_hist_pairs"));
+    if (bins2d < 1 || bins2d > HS_MAX_BINS2D)
+        return fail("bpm_hist_pairs: bins2d = " + std::to_string(bins2d) + " is outside the supported 1 ... " + std::to_string(HS_MAX_BINS2D));
+    if (n_dims < 1 || (uint32_t)n_dims > s->dim) return fail("bpm_hist_pairs: n_dims must be 1 ... dim");
+    if (n_pairs < 1 || n_pairs > ((int64_t)1 << 24))
+        return fail("bpm_hist_pairs: n_pairs = " + std::to_string(n_pairs) + " is outside the supported 1 ... 16777216");
+    const uint32_t m = (uint32_t)n_dims, nb = (uint32_t)bins2d, cells = nb * nb;
+    const size_t P = (size_t)n_pairs;
+    for (uint32_t j = 0; j < m; ++j) {
+        if (dims[j] < 0 || (uint32_t)dims[j] >= s->dim) return fail("bpm_hist_pairs: coordinate out of range");
+        const double* e = edges2d + (size_t)j * (nb + 1);
+        for (uint32_t i = 0; i <= nb; ++i)
+            if (!std::isfinite(e[i]) || (i > 0 && e[i] < e[i - 1])) return fail("bpm_hist_pairs: edges must be finite and non-decreasing");
+    }
+    for (size_t p = 0; p < P; ++p)
+        if (pair_a[p] < 0 || pair_a[p] >= n_dims || pair_b[p] < 0 || pair_b[p] >= n_dims)
+            return fail("bpm_hist_pairs: a pair names a coordinate that is not in dims");
+    const size_t n_counts = P * cells, n_edges = (size_t)m * (nb + 1);
+    const uint64_t rows = s->hs_hi - s->hs_lo;
+    // tiles of pairs in the order given: equal shares of at most tp_max pairs; each tile's distinct slots in order of first use
+    const uint32_t tp_max = std::max(1u, std::min(HS_TILE_PAIRS, HS_LDS_PAIRS / (cells * 4)));
+    const size_t n_tiles = (P + tp_max - 1) / tp_max;
+    const size_t tp = (P + n_tiles - 1) / n_tiles;
+    std::vector<uint32_t> tiles, uslot, pl(2 * P);
+    uint32_t nu_max = 1, np_max = 1;
+    std::vector<int32_t> where(m, -1);
+    for (size_t p0 = 0; p0 < P; p0 += tp) {
+        const size_t np = std::min(tp, P - p0);
+        const uint32_t u0 = (uint32_t)uslot.size();
+        for (size_t p = p0; p < p0 + np; ++p)
+            for (int side = 0; side < 2; ++side) {
+                const int32_t sl = side ? pair_b[p] : pair_a[p];
+                if (where[sl] < (int32_t)u0) {
+                    where[sl] = (int32_t)uslot.size();
+                    uslot.push_back((uint32_t)sl);
+                }
+                pl[2 * p + side] = (uint32_t)where[sl] - u0;
+            }
+        const uint32_t nu = (uint32_t)uslot.size() - u0;
+        tiles.insert(tiles.end(), {(uint32_t)p0, (uint32_t)np, u0, nu});
+        nu_max = std::max(nu_max, nu);
+        np_max = std::max(np_max, (uint32_t)np);
+    }
+    // [counts u64 | edges f64 | tiles 16 B each | pl 8 B each | uslot u32 | dims u32]
+    const size_t o_e = n_counts * 8, o_t = o_e + n_edges * 8, o_pl = o_t + n_tiles * 16, o_u = o_pl + P * 8, o_d = o_u + uslot.size() * 4,
+                 need = o_d + (size_t)m * 4;
+    HistBuffers b;
+    CK(hist_alloc(b, need, "bpm_hist_pairs",
+                  std::to_string(n_pairs) + " pairs of " + std::to_string(bins2d) + " x " + std::to_string(bins2d) + " 64-bit counts"));
+    std::fill(counts2d, counts2d + n_counts, (int64_t)0);
+    if (rows == 0) return 0;
+    std::vector<unsigned char> in(need - o_e);
+    std::memcpy(in.data(), edges2d, n_edges * 8);
+    std::memcpy(in.data() + (o_t - o_e), tiles.data(), n_tiles * 16);
+    std::memcpy(in.data() + (o_pl - o_e), pl.data(), P * 8);
+    std::memcpy(in.data() + (o_u - o_e), uslot.data(), uslot.size() * 4);
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t k = (uint32_t)dims[j];
+        std::memcpy(in.data() + (o_d - o_e) + 4 * (size_t)j, &k, 4);
+    }
+    HIPCK(hipMemsetAsync(b.p, 0, o_e, s->stream));
+    HIPCK(hipMemcpyAsync(b.p + o_e, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
+    const uint32_t lds = nu_max * (nb + 1) * 8 + np_max * cells * 4 + HS_THREADS * HS_UNR;
+    uint64_t nby = 1;
+    CK(hist_nby(rows, n_tiles, (uint64_t)(HS_THREADS / nu_max) * HS_UNR, "bpm_hist_pairs", &nby));
+    hipLaunchKernelGGL(hs_pair_kernel, dim3((unsigned)n_tiles, (unsigned)nby), dim3(HS_THREADS), lds, s->stream, (const double*)s->hist, s->ld,
+                       s->hs_lo, s->hs_hi, reinterpret_cast<const uint4*>(b.p + o_t), reinterpret_cast<const uint32_t*>(b.p + o_u),
+                       reinterpret_cast<const uint2*>(b.p + o_pl), reinterpret_cast<const uint32_t*>(b.p + o_d), nb,
+                       reinterpret_cast<const double*>(b.p + o_e), nu_max, np_max, reinterpret_cast<unsigned long long*>(b.p));
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(counts2d, b.p, o_e, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }

@@ -465,6 +465,18 @@ class DeMcMpi(object):
         eng = self._engine
         return _cov.compute(eng.reduce_moments, eng.reduce_cov, self.comm.allgather, n_burn, eng.dim)
 
+    def param_est_hist(self, n_burn=0, bins=20, range=None, dims=None, pairs=None, bins2d=None):
+        """The counts of a corner plot over the super-chain rows >= n_burn: per coordinate of `dims` (None: all) exactly
+        np.histogram(param_est(n_burn)[2][:, k], bins, range)[0], per pair of `pairs` (None: none; "all": every a < b of dims; or (a, b)
+        tuples) exactly np.histogram2d(..., bins2d, range=[ra, rb])[0], counted on the GPU(s) without moving the history
+        (bipymc_amd/histograms.py; range: None for each coordinate's (min, max), (lo, hi) for all, or one (lo, hi) per coordinate).
+        Collective: every rank calls it; every rank gets the same bits.
+        -> histograms.PosteriorHistograms(dims, edges, counts, pairs, edges2d, counts2d, n) with .density()"""
+        from . import histograms as _hs
+        eng = self._engine
+        return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, self.comm.allgather, n_burn, eng.dim, bins=bins, range=range,
+                           dims=dims, pairs=pairs, bins2d=bins2d)
+
     def super_chain_mpi(self, collection_rank=0):
         return self._super_chain(collection_rank)
 

@@ -452,6 +452,41 @@ class HipEngine(object):
         self._ck(self.lib.bpm_reduce_cov(self._h, int(n_burn), None if c is None else _dptr(c), _dptr(s1), _dptr(s2), C.byref(n)))
         return int(n.value), s1, s2
 
+    def hist_range(self, n_burn):
+        """-> (count, lo (dim,), hi (dim,), n_nan (dim,), n_inf (dim,)): over the local super-chain rows >= n_burn, the smallest and largest
+        value of every coordinate that is not NaN (+inf / -inf where there is none) and how many are NaN / infinite; fixes the window of the
+        hist_marginals / hist_pairs calls that follow (bpm_hist_range; bipymc_amd/histograms.py builds the edges and merges the ranks)"""
+        lo = np.empty(self.dim); hi = np.empty(self.dim)
+        nn = np.empty(self.dim, dtype=np.int64); ni = np.empty(self.dim, dtype=np.int64)
+        n = C.c_int64(0)
+        i64 = C.POINTER(C.c_int64)
+        self._ck(self.lib.bpm_hist_range(self._h, int(n_burn), _dptr(lo), _dptr(hi), nn.ctypes.data_as(i64), ni.ctypes.data_as(i64), C.byref(n)))
+        return int(n.value), lo, hi, nn, ni
+
+    def hist_marginals(self, dims, edges):
+        """-> (m, bins) int64: np.histogram's counts of the coordinates `dims` (m,) for the edges (m, bins + 1) over the window of the last
+        hist_range call (bpm_hist_marginals)"""
+        dm = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(len(dm), -1)
+        out = np.empty((len(dm), e.shape[1] - 1), dtype=np.int64)
+        self._ck(self.lib.bpm_hist_marginals(self._h, len(dm), dm.ctypes.data_as(C.POINTER(C.c_int32)), e.shape[1] - 1, _dptr(e),
+                                             out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def hist_pairs(self, dims, edges2d, pair_a, pair_b):
+        """-> (P, bins2d, bins2d) int64: np.histogram2d's counts of the pairs (dims[pair_a[p]], dims[pair_b[p]]) for the edges (m, bins2d + 1)
+        over the window of the last hist_range call (bpm_hist_pairs)"""
+        dm = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+        e = np.ascontiguousarray(edges2d, dtype=np.float64).reshape(len(dm), -1)
+        pa = np.ascontiguousarray(pair_a, dtype=np.int32).reshape(-1)
+        pb = np.ascontiguousarray(pair_b, dtype=np.int32).reshape(-1)
+        nb = e.shape[1] - 1
+        out = np.empty((len(pa), nb, nb), dtype=np.int64)
+        i32 = C.POINTER(C.c_int32)
+        self._ck(self.lib.bpm_hist_pairs(self._h, len(dm), dm.ctypes.data_as(i32), nb, _dptr(e), len(pa), pa.ctypes.data_as(i32),
+                                         pb.ctypes.data_as(i32), out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

@@ -136,6 +136,17 @@ class DeMc(object):
             raise RuntimeError("param_est_cov: run_mcmc first")
         return _cov.compute(eng.reduce_moments, eng.reduce_cov, _cov.single_process_allgather, n_burn, eng.dim)
 
+    def param_est_hist(self, n_burn=0, bins=20, range=None, dims=None, pairs=None, bins2d=None):
+        """The counts of a corner plot over the super-chain rows >= n_burn: np.histogram's per coordinate of `dims`, np.histogram2d's per
+        pair of `pairs`, exactly, counted on the GPU without moving the history (bipymc_amd/histograms.py).
+        -> histograms.PosteriorHistograms(dims, edges, counts, pairs, edges2d, counts2d, n) with .density()"""
+        from . import histograms as _hs
+        eng = self._engine
+        if eng is None:
+            raise RuntimeError("param_est_hist: run_mcmc first")
+        return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, _hs.single_process_allgather, n_burn, eng.dim, bins=bins,
+                           range=range, dims=dims, pairs=pairs, bins2d=bins2d)
+
     def param_est(self, n_burn):
         chain_slice = self.super_chain[n_burn:, :]                      # samplers.py:311-315
         return np.mean(chain_slice, axis=0), np.std(chain_slice, axis=0), chain_slice

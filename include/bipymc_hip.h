@@ -326,6 +326,26 @@ int bpm_quantile_histogram(bpm_handle_t h, int64_t n_prefix, const int32_t* pref
  * Errors: no resident history (keep_history = 0); dim beyond 16384, or a dim x dim result and partial sums larger than the free device
  * memory (the message names the limit). */
 int bpm_reduce_cov(bpm_handle_t h, int64_t n_burn, const double* center, double* sum, double* cross, int64_t* count);
+/* Marginal and pairwise histograms of the super chain on the device: the counts of the reference's corner plot (corner.corner(samples),
+ * mc_plot/mc_plot.py:16-29: a 1-D histogram per parameter, a 2-D histogram per pair), taken over the resident history.
+ * bpm_hist_range fixes the window of bpm_reduce_moments (super-chain rows >= n_burn, a partial first generation by chain index) and returns,
+ * per coordinate over this rank's rows of it, lo / hi = the smallest / largest value that is not NaN (+inf / -inf where there is none), n_nan
+ * and n_inf = how many values are NaN / infinite (dim values each), count = the rows.  The caller (bipymc_amd/histograms.py) merges the
+ * ranks, applies NumPy's range rules and builds the edges with np.linspace; the device receives edges only.
+ * bpm_hist_marginals: counts[j * bins + i] = rows of that window whose coordinate dims[j] lies in bin i of the bins + 1 non-decreasing edges
+ * edges[j * (bins + 1) ...]: e[i] <= x < e[i + 1], the last bin also x == e[bins]; NaN and values outside are counted nowhere -- exactly
+ * np.histogram's counts for these edges (a guessed bin is corrected against the edges).  1 <= bins <= 1024; dims: n_dims coordinates.
+ * bpm_hist_pairs: counts2d[(p * bins2d + i) * bins2d + j] = rows whose coordinate dims[pair_a[p]] lies in bin i of edges2d[pair_a[p]] and
+ * whose coordinate dims[pair_b[p]] lies in bin j of edges2d[pair_b[p]] (pair_a, pair_b index dims; edges2d: n_dims x (bins2d + 1)) -- exactly
+ * np.histogram2d's counts.  1 <= bins2d <= 64, 1 <= n_pairs <= 2^24.
+ * Counts are integers added by integer atomics: the same history gives the same bits, ranks merge by addition.  The two counting calls
+ * return an error once the history changed since bpm_hist_range (a step, bpm_set_history or bpm_set_state).  Every device buffer is
+ * temporary; nothing the samplers read is written.  Errors: no resident history (keep_history = 0); bins / bins2d / n_pairs beyond the
+ * limits, or counts and temporaries larger than the free device memory (the message names the limit). */
+int bpm_hist_range(bpm_handle_t h, int64_t n_burn, double* lo, double* hi, int64_t* n_nan, int64_t* n_inf, int64_t* count);
+int bpm_hist_marginals(bpm_handle_t h, int32_t n_dims, const int32_t* dims, int32_t bins, const double* edges, int64_t* counts);
+int bpm_hist_pairs(bpm_handle_t h, int32_t n_dims, const int32_t* dims, int32_t bins2d, const double* edges2d, int64_t n_pairs,
+                   const int32_t* pair_a, const int32_t* pair_b, int64_t* counts2d);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
