@@ -1,0 +1,56 @@
+"""The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance and
+histograms (bipymc_amd/diagnostics.py, quantiles.py, covariance.py, histograms.py), each reduced where the history lives.
+
+The contract they share.  The window is the super-chain rows >= n_burn, param_est's selection (row g * n_chains + i = chain i at generation
+g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
+because the ranks' parts travel through one allgather and are merged in rank order.
+
+A host class provides two hooks: _stats_engine(who) -> its engine (or the error of a sampler that has not run, in the name of the method
+`who`), and _stats_allgather(obj) -> [obj of every rank] in rank order.
+"""
+
+
+def check_n_burn(who, n_burn):
+    """-> int(n_burn), which must not be negative"""
+    n_burn = int(n_burn)
+    if n_burn < 0:
+        raise ValueError("%s: n_burn must be >= 0 (got %d)" % (who, n_burn))
+    return n_burn
+
+
+def empty_window(who, n_burn):
+    """the error of a window without rows (for the caller to raise)"""
+    return ValueError("%s: the window is empty (n_burn = %d is at or beyond the last super-chain row)" % (who, int(n_burn)))
+
+
+class HistoryStatistics(object):
+    def convergence_diagnostics(self, n_burn=0, max_lag=None):
+        """Split-chain R-hat and effective sample size per coordinate; the window starts at the first whole generation after n_burn.
+        max_lag bounds the autocorrelation lags read (ess_capped says where it ended the sum).  -> diagnostics.ConvergenceDiagnostics"""
+        from . import diagnostics as _diag
+        eng = self._stats_engine("convergence_diagnostics")
+        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
+        return _diag.compute(eng.diag_split_moments, eng.diag_autocov, self._stats_allgather, g0, g1, max_lag=max_lag)
+
+    def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
+        """np.quantile(param_est(n_burn)[2], q, axis=0), exactly (an MSD radix select).  -> (len(q), dim), or (dim,) for a scalar q"""
+        from . import quantiles as _qs
+        eng = self._stats_engine("param_est_quantiles")
+        return _qs.compute(eng.quantile_begin, eng.quantile_histogram, self._stats_allgather, n_burn, q, dim=eng.dim)
+
+    def param_est_cov(self, n_burn=0):
+        """Posterior mean, covariance (ddof = 1) and, through .corr(), correlation: what np.cov(param_est(n_burn)[2], rowvar=False)
+        computes (an FP64 matrix-core SYRK centred on the global mean).  -> covariance.PosteriorCovariance(mean, cov, n)"""
+        from . import covariance as _cov
+        eng = self._stats_engine("param_est_cov")
+        return _cov.compute(eng.reduce_moments, eng.reduce_cov, self._stats_allgather, n_burn, eng.dim)
+
+    def param_est_hist(self, n_burn=0, bins=20, range=None, dims=None, pairs=None, bins2d=None):
+        """The counts of a corner plot: per coordinate of `dims` (None: all) exactly np.histogram(param_est(n_burn)[2][:, k], bins,
+        range)[0], per pair of `pairs` (None: none; "all": every a < b of dims; or (a, b) tuples) exactly np.histogram2d(..., bins2d,
+        range=[ra, rb])[0].  range: None for each coordinate's (min, max), (lo, hi) for all, or one (lo, hi) per coordinate.
+        -> histograms.PosteriorHistograms(dims, edges, counts, pairs, edges2d, counts2d, n) with .density()"""
+        from . import histograms as _hs
+        eng = self._stats_engine("param_est_hist")
+        return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, self._stats_allgather, n_burn, eng.dim, bins=bins,
+                           range=range, dims=dims, pairs=pairs, bins2d=bins2d)

@@ -30,6 +30,11 @@ class SingleComm(object):
         pass
 
 
+def single_process_allgather(obj):
+    """SingleComm().allgather for a caller that has no communicator object"""
+    return [obj]
+
+
 class TorchDistComm(object):
     """torch.distributed as the control-plane communicator (gloo or nccl(=RCCL) backend)."""
 

@@ -16,6 +16,9 @@ import collections
 
 import numpy as np
 
+from ._history_stats import check_n_burn, empty_window
+from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
+
 
 class PosteriorCovariance(collections.namedtuple("PosteriorCovariance", ["mean", "cov", "n"])):
     """mean (dim,), cov (dim, dim) with ddof = 1, exactly symmetric; n rows of the window, summed over ranks"""
@@ -49,17 +52,15 @@ def compute(reduce_moments, reduce_cov, allgather, n_burn, dim):
     """The collective driver.  reduce_moments(n_burn) -> (count, S1, S2, shift) of this rank's rows (HipEngine.reduce_moments);
     reduce_cov(n_burn, center) -> (count, S1 (dim,), S2 (dim, dim)) about `center` (HipEngine.reduce_cov); allgather(obj) -> [obj of every
     rank] in rank order ([obj] for one process, single_process_allgather).  -> PosteriorCovariance, the same bits on every rank"""
-    n_burn = int(n_burn)
+    n_burn = check_n_burn("param_est_cov", n_burn)
     dim = int(dim)
-    if n_burn < 0:
-        raise ValueError("param_est_cov: n_burn must be >= 0 (got %d)" % n_burn)
     parts = [(int(p[0]), np.asarray(p[1], dtype=np.float64)) + tuple(p[2:]) for p in allgather(reduce_moments(n_burn))]
     shift = np.asarray(parts[0][3], dtype=np.float64).reshape(dim)      # (identical on every rank)
     n = sum(int(p[0]) for p in parts)
     if n < 2:
         reduce_cov(n_burn, shift)       # (a sampler without a resident history says so here rather than reporting an empty window)
         if n == 0:
-            raise ValueError("param_est_cov: the window is empty (n_burn = %d is at or beyond the last super-chain row)" % n_burn)
+            raise empty_window("param_est_cov", n_burn)
         raise ValueError("param_est_cov: a covariance needs at least 2 rows; the window after n_burn = %d holds %d" % (n_burn, n))
     tot = np.zeros(dim)
     for p in parts:
@@ -76,7 +77,3 @@ def compute(reduce_moments, reduce_cov, allgather, n_burn, dim):
             s1 = s1 + np.asarray(p[1], dtype=np.float64).reshape(dim)
             s2 = s2 + np.asarray(p[2], dtype=np.float64).reshape(dim, dim)
     return finish(n, center, s1, s2)
-
-
-def single_process_allgather(obj):
-    return [obj]

@@ -380,6 +380,17 @@ static PhaseLaunch g_commit[2][7] = {SHAPE_TABLE(launch_commit, launch_wide_comm
 static EvalLaunch g_eval_gauss[7] = SHAPE_TABLE(launch_eval, launch_eval_wide<TARGET_GAUSS>, TARGET_GAUSS COMMA);
 static EvalLaunch g_eval_mixture[7] = SHAPE_TABLE(launch_eval, launch_eval_wide<TARGET_MIXTURE>, TARGET_MIXTURE COMMA);
 
+// "The history is still what the first call of a pair saw" (bpm_diag_split_moments -> bpm_diag_autocov, bpm_quantile_begin ->
+// bpm_quantile_histogram, bpm_hist_range -> bpm_hist_marginals / bpm_hist_pairs): the first call take()s, the ones that follow check().
+struct bpm_sampler;
+struct HistorySnapshot {
+    bool valid = false;
+    uint64_t epoch = 0;
+    int64_t tabs = 0, rows = 0;
+    void take(const bpm_sampler* s);
+    int check(const bpm_sampler* s, const char* who, const char* first_call) const;
+};
+
 // ---- the sampler ------------------------------------------------------------------------
 struct bpm_sampler {
     bpm_config_t cfg{};
@@ -580,29 +591,26 @@ struct bpm_sampler {
     bool proposed = false;
     bool state_set = false;
     // convergence diagnostics (diagnostics.h, bpm_diag_*): per-half-chain means and M2 of the window of the last bpm_diag_split_moments
-    // ([2][n_local][ld] each), which bpm_diag_autocov centres with; valid while the history is what that call read (dg_epoch / dg_tabs)
+    // ([2][n_local][ld] each), which bpm_diag_autocov centres with; valid while the history is what that call read (dg_seen)
     double* dg_mean = nullptr;
     double* dg_m2 = nullptr;
     double* dg_out = nullptr;       // [max(3, DIAG_T) ld]: the aggregates of the split pass, then one block of lag sums
     double* dg_part = nullptr;      // per-workgroup partials of diag_autocov_kernel
     size_t dg_part_cap = 0;
-    bool dg_valid = false;
-    int64_t dg_g0 = 0, dg_g1 = 0, dg_n = 0, dg_tabs = 0, dg_rows = 0;
-    uint64_t dg_epoch = 0;
+    HistorySnapshot dg_seen;
+    int64_t dg_g0 = 0, dg_g1 = 0, dg_n = 0;
     uint64_t hist_epoch = 0;        // bumped whenever the history is replaced (reset_history, bpm_set_history); generations bump t_abs
     // posterior quantiles (quantiles.h, bpm_quantile_*): the window [qs_lo, qs_hi) of local super-chain rows fixed by the last
-    // bpm_quantile_begin, valid while the history is what that call saw (qs_epoch / qs_tabs / qs_rows); qs_buf holds one histogram request
+    // bpm_quantile_begin, valid while the history is what that call saw (qs_seen); qs_buf holds one histogram request
     // (histograms and NaN counts out, prefixes, coordinates and tiles in), qs_cap bytes
     unsigned char* qs_buf = nullptr;
     size_t qs_cap = 0;
-    bool qs_valid = false;
-    uint64_t qs_lo = 0, qs_hi = 0, qs_epoch = 0;
-    int64_t qs_tabs = 0, qs_rows = 0;
+    HistorySnapshot qs_seen;
+    uint64_t qs_lo = 0, qs_hi = 0;
     // posterior histograms (histograms.h, bpm_hist_*): the window fixed by the last bpm_hist_range, valid while the history is what that
-    // call saw; every device buffer of these calls is temporary
-    bool hs_valid = false;
-    uint64_t hs_lo = 0, hs_hi = 0, hs_epoch = 0;
-    int64_t hs_tabs = 0, hs_rows = 0;
+    // call saw (hs_seen); every device buffer of these calls is temporary
+    HistorySnapshot hs_seen;
+    uint64_t hs_lo = 0, hs_hi = 0;
     double* om = nullptr;        // outlier check: world x [omega (n_local) | ln_like (n_local)], all-gathered in place
     double* sel = nullptr;       // outlier check: [0..3] order statistics around Q1 / Q3, [4] first argmax of omega
     unsigned char* sel_state = nullptr;   // radix-select state between the passes (SelState)
@@ -807,6 +815,102 @@ static int normalize_history(bpm_sampler* s, int64_t r0, int64_t r1) {
         HIPCK(hipMemcpyAsync(row, s->hist_tmp, row_d * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         if (!ll_by_chain) HIPCK(hipMemcpyAsync(llrow, s->hist_tmp + row_d, (size_t)s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         s->hist_tag[(size_t)r] = -1;
+    }
+    return 0;
+}
+
+// ---- shared by the statistics of the history (bpm_reduce_moments ... bpm_hist_pairs) ---------------------------------------------------
+static int require_resident_history(const bpm_sampler* s, const char* who) {
+    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        return fail(std::string(who) + ": needs keep_history=True (a resident history of every generation)");
+    return 0;
+}
+
+// param_est's selection (demc.py:235-248): this rank's rows [lo, hi), lo <= hi, of the super chain (row g*N + i = chain i at generation g)
+// at or after n_burn (negative: 0).  A partial first generation is counted by chain index, so that row is brought into chain order first.
+static int super_chain_window(bpm_sampler* s, int64_t n_burn, uint64_t* lo, uint64_t* hi) {
+    if (n_burn < 0) n_burn = 0;
+    const int64_t g0 = n_burn / s->N;
+    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
+    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
+    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));
+    *hi = (uint64_t)s->hist_rows * s->n_local;
+    *lo = std::min(*hi, (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0));
+    return 0;
+}
+
+void HistorySnapshot::take(const bpm_sampler* s) {
+    epoch = s->hist_epoch; tabs = s->t_abs; rows = s->hist_rows;
+    valid = true;
+}
+int HistorySnapshot::check(const bpm_sampler* s, const char* who, const char* first_call) const {
+    if (!valid) return fail(std::string(who) + ": call " + first_call + " first");
+    if (epoch != s->hist_epoch || tabs != s->t_abs || rows != s->hist_rows || s->hist_rows != s->rows_logical)
+        return fail(std::string(who) + ": the history changed since " + first_call + " (a step, set_history or set_state); call it again");
+    return 0;
+}
+
+// Device memory that lives for one call: freed on every way out of it.  alloc() with a `what` first checks the free memory and names the
+// requirement in its error; without one it is dev_alloc.
+template <class T>
+struct DevTemp {
+    T* p = nullptr;
+    DevTemp() = default;
+    DevTemp(DevTemp&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevTemp(const DevTemp&) = delete;
+    DevTemp& operator=(const DevTemp&) = delete;
+    ~DevTemp() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n, const char* who = nullptr, const std::string& what = std::string()) {
+        if (who) {
+            const size_t need = n * sizeof(T);
+            size_t mem_free = 0, mem_total = 0;
+            HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+            if (need > mem_free)
+                return fail(std::string(who) + ": " + what + " need " + std::to_string(need >> 20) + " MiB of device memory; " +
+                            std::to_string(mem_free >> 20) + " MiB are free");
+        }
+        return dev_alloc(&p, n);
+    }
+};
+
+// A buffer the sampler keeps between calls (freed by bpm_destroy, which may decide to leak it), grown to `need` elements when it is smaller.
+template <class T>
+static int grow_device(bpm_sampler* s, T** p, size_t* cap, size_t need) {
+    if (need <= *cap) return 0;
+    if (*p) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(*p)); *p = nullptr; *cap = 0; }
+    CK(dev_alloc(p, need));
+    *cap = need;
+    return 0;
+}
+
+// workgroups along the rows: about 2048 in all (four resident per CU), each at least 4 sweeps of `rows_per_sweep`, none with 2^31 rows or
+// more (a workgroup's uint32 counts stay below 2^31)
+static int rows_grid(uint64_t rows, uint64_t n_tiles, uint64_t rows_per_sweep, const char* who, uint64_t* nby_out) {
+    uint64_t nby = std::max<uint64_t>(1, 2048 / n_tiles);
+    nby = std::min<uint64_t>(nby, (rows + 4 * rows_per_sweep - 1) / (4 * rows_per_sweep));
+    nby = std::max<uint64_t>(nby, (rows >> 31) + 1);
+    if (nby > 65535) return fail(std::string(who) + ": window too large");
+    *nby_out = nby;
+    return 0;
+}
+
+// n coordinates as the uint32 the kernels read
+static void stage_dims(unsigned char* dst, const int32_t* dims, size_t n) {
+    for (size_t j = 0; j < n; ++j) {
+        const uint32_t k = (uint32_t)dims[j];
+        std::memcpy(dst + 4 * j, &k, 4);
+    }
+}
+
+// the coordinates dims[0 .. n_dims) exist; each one's bins + 1 edges are finite and non-decreasing
+static int check_dims_edges(const bpm_sampler* s, const char* who, uint32_t n_dims, const int32_t* dims, uint32_t bins, const double* edges) {
+    for (uint32_t j = 0; j < n_dims; ++j) {
+        if (dims[j] < 0 || (uint32_t)dims[j] >= s->dim) return fail(std::string(who) + ": coordinate out of range");
+        const double* e = edges + (size_t)j * (bins + 1);
+        for (uint32_t i = 0; i <= bins; ++i)
+            if (!std::isfinite(e[i]) || (i > 0 && e[i] < e[i - 1])) return fail(std::string(who) + ": edges must be finite and non-decreasing");
     }
     return 0;
 }
@@ -2913,44 +3017,36 @@ extern "C" int bpm_reduce_moments(bpm_handle_t s, int64_t n_burn, double* sum, d
         HIPCK(hipMemcpyAsync(h.data() + 2 * s->ld, s->gs_shift, s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         *count = (g1 - g0) * (int64_t)s->n_local;
         if (g1 > g0) {
-            double* out = nullptr;
-            CK(dev_alloc(&out, 2 * (size_t)s->ld));
+            DevTemp<double> out;
+            CK(out.alloc(2 * (size_t)s->ld));
             hipLaunchKernelGGL(moments_final_kernel, dim3(s->ld), dim3(MOM_THREADS), 0, s->stream, (const double*)(s->gen_sums + (size_t)g0 * 2 * s->ld),
-                               (uint32_t)(g1 - g0), s->ld, out);
+                               (uint32_t)(g1 - g0), s->ld, out.p);
             HIPCK(hipGetLastError());
-            HIPCK(hipMemcpyAsync(h.data(), out, 2 * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+            HIPCK(hipMemcpyAsync(h.data(), out.p, 2 * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
             HIPCK(hipStreamSynchronize(s->stream));
-            HIPCK(hipFree(out));
         } else {
             HIPCK(hipStreamSynchronize(s->stream));
         }
         for (uint32_t j = 0; j < s->dim; ++j) { sum[j] = h[j]; sumsq[j] = h[s->ld + j]; shift[j] = h[2 * s->ld + j]; }
         return 0;
     }
-    const int64_t g0 = n_burn / s->N;
-    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
-    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
-    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));      // a partial first generation is counted by chain index
-    const uint64_t m_lo = (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0);
-    const uint64_t m_hi = (uint64_t)s->hist_rows * s->n_local;
+    uint64_t m_lo = 0, m_hi = 0;
+    CK(super_chain_window(s, n_burn, &m_lo, &m_hi));
     std::vector<double> h(3 * (size_t)s->ld, 0.0);
     HIPCK(hipMemcpyAsync(h.data() + 2 * s->ld, s->G, s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    *count = (int64_t)(m_hi > m_lo ? m_hi - m_lo : 0);
+    *count = (int64_t)(m_hi - m_lo);
     if (m_hi > m_lo) {
         // enough blocks for ~8 per CU (each thread keeps MOM_UNR 16-byte loads in flight), at least 64 rows each
         const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (m_hi - m_lo + 63) / 64));
-        double* part = nullptr;
-        double* out = nullptr;
-        CK(dev_alloc(&part, (size_t)nb * 2 * s->ld));
-        CK(dev_alloc(&out, 2 * (size_t)s->ld));
+        DevTemp<double> part, out;
+        CK(part.alloc((size_t)nb * 2 * s->ld));
+        CK(out.alloc(2 * (size_t)s->ld));
         hipLaunchKernelGGL(moments_partial_kernel, dim3(nb), dim3(MOM_THREADS), 0, s->stream, s->hist, m_lo, m_hi, s->ld,
-                           s->G, part);
-        hipLaunchKernelGGL(moments_final_kernel, dim3(s->ld), dim3(MOM_THREADS), 0, s->stream, part, nb, s->ld, out);
+                           s->G, part.p);
+        hipLaunchKernelGGL(moments_final_kernel, dim3(s->ld), dim3(MOM_THREADS), 0, s->stream, part.p, nb, s->ld, out.p);
         HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(h.data(), out, 2 * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipMemcpyAsync(h.data(), out.p, 2 * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         HIPCK(hipStreamSynchronize(s->stream));
-        HIPCK(hipFree(part));
-        HIPCK(hipFree(out));
     } else {
         HIPCK(hipStreamSynchronize(s->stream));
     }
@@ -2966,10 +3062,9 @@ extern "C" int bpm_diag_split_moments(bpm_handle_t s, int64_t g_lo, int64_t g_hi
                                       double* sum_of_vars, int64_t* n_half_chains, int64_t* n_draws) {
     CK(check_handle(s));
     CK(set_device(s));
-    s->dg_valid = false;
+    s->dg_seen.valid = false;
     if (!mean_of_means || !m2_of_means || !sum_of_vars || !n_half_chains || !n_draws) return fail("bpm_diag_split_moments: null argument");
-    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
-        return fail("bpm_diag_split_moments: needs keep_history=True (a resident history of every generation)");
+    CK(require_resident_history(s, "bpm_diag_split_moments"));
     if (g_lo < 0 || g_hi < g_lo || g_hi > s->hist_rows) return fail("bpm_diag_split_moments: generation range out of bounds");
     const int64_t n = (g_hi - g_lo) / 2;
     if (n < 4)
@@ -3000,8 +3095,7 @@ extern "C" int bpm_diag_split_moments(bpm_handle_t s, int64_t g_lo, int64_t g_hi
     *n_half_chains = 2 * (int64_t)s->n_local;
     *n_draws = n;
     s->dg_g0 = g_lo; s->dg_g1 = g_hi; s->dg_n = n;
-    s->dg_tabs = s->t_abs; s->dg_rows = s->hist_rows; s->dg_epoch = s->hist_epoch;
-    s->dg_valid = true;
+    s->dg_seen.take(s);
     return 0;
 }
 
@@ -3011,9 +3105,7 @@ extern "C" int bpm_diag_autocov(bpm_handle_t s, int64_t t0, int32_t n_lags, doub
     CK(check_handle(s));
     CK(set_device(s));
     if (!out) return fail("bpm_diag_autocov: null argument");
-    if (!s->dg_valid) return fail("bpm_diag_autocov: call bpm_diag_split_moments first");
-    if (s->dg_epoch != s->hist_epoch || s->dg_tabs != s->t_abs || s->dg_rows != s->hist_rows || s->hist_rows != s->rows_logical)
-        return fail("bpm_diag_autocov: the history changed since bpm_diag_split_moments (a step, set_history or set_state); call it again");
+    CK(s->dg_seen.check(s, "bpm_diag_autocov", "bpm_diag_split_moments"));
     if (t0 < 0 || n_lags < 1 || t0 + n_lags > s->dg_n)
         return fail("bpm_diag_autocov: lags [t0, t0 + n_lags) must lie in [0, n) with n = " + std::to_string((long long)s->dg_n) +
                     " draws per half-chain");
@@ -3024,11 +3116,7 @@ extern "C" int bpm_diag_autocov(bpm_handle_t s, int64_t t0, int32_t n_lags, doub
     // ~768 workgroups in all, what is resident at once (three per CU at this kernel's 138 VGPRs): each walks n_groups / nb column groups
     const uint32_t nb = std::max(1u, std::min(n_groups, 384u / n_kt));
     const size_t part_n = (size_t)2 * nb * DIAG_T * s->ld;
-    if (part_n > s->dg_part_cap) {
-        if (s->dg_part) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(s->dg_part)); s->dg_part = nullptr; s->dg_part_cap = 0; }
-        CK(dev_alloc(&s->dg_part, part_n));
-        s->dg_part_cap = part_n;
-    }
+    CK(grow_device(s, &s->dg_part, &s->dg_part_cap, part_n));
     std::vector<double> h((size_t)DIAG_T * s->ld);
     const int64_t r_lo1 = s->dg_g1 - s->dg_n;
     for (int64_t b0 = t0; b0 < t0 + n_lags; b0 += DIAG_T) {
@@ -3052,21 +3140,11 @@ extern "C" int bpm_diag_autocov(bpm_handle_t s, int64_t t0, int32_t n_lags, doub
 extern "C" int bpm_quantile_begin(bpm_handle_t s, int64_t n_burn, int64_t* count) {
     CK(check_handle(s));
     CK(set_device(s));
-    s->qs_valid = false;
+    s->qs_seen.valid = false;
     if (!count) return fail("bpm_quantile_begin: null argument");
-    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
-        return fail("bpm_quantile_begin: needs keep_history=True (a resident history of every generation)");
-    if (n_burn < 0) n_burn = 0;
-    const int64_t g0 = n_burn / s->N;
-    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
-    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
-    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));
-    const uint64_t m_lo = (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0);
-    const uint64_t m_hi = (uint64_t)s->hist_rows * s->n_local;
-    s->qs_lo = std::min(m_lo, m_hi);
-    s->qs_hi = m_hi;
-    s->qs_epoch = s->hist_epoch; s->qs_tabs = s->t_abs; s->qs_rows = s->hist_rows;
-    s->qs_valid = true;
+    CK(require_resident_history(s, "bpm_quantile_begin"));
+    CK(super_chain_window(s, n_burn, &s->qs_lo, &s->qs_hi));
+    s->qs_seen.take(s);
     *count = (int64_t)(s->qs_hi - s->qs_lo);
     return 0;
 }
@@ -3079,9 +3157,7 @@ extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const in
     CK(check_handle(s));
     CK(set_device(s));
     if (!prefix_dim || !prefixes || !hist) return fail("bpm_quantile_histogram: null argument");
-    if (!s->qs_valid) return fail("bpm_quantile_histogram: call bpm_quantile_begin first");
-    if (s->qs_epoch != s->hist_epoch || s->qs_tabs != s->t_abs || s->qs_rows != s->hist_rows || s->hist_rows != s->rows_logical)
-        return fail("bpm_quantile_histogram: the history changed since bpm_quantile_begin (a step, set_history or set_state); call it again");
+    CK(s->qs_seen.check(s, "bpm_quantile_histogram", "bpm_quantile_begin"));
     if (prefix_bits < 0 || prefix_bits > 56 || prefix_bits % 8 != 0)
         return fail("bpm_quantile_histogram: prefix_bits must be one of 0, 8, ..., 56");
     if (n_prefix < 1 || n_prefix > ((int64_t)1 << 24)) return fail("bpm_quantile_histogram: n_prefix out of range");
@@ -3106,18 +3182,11 @@ extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const in
     // qs_buf: [hist np x 256 u64 | n_nan np u64 | prefixes np u64 | tiles n_tiles x 16 B (16-byte aligned) | coordinates np u32]
     const size_t o_nan = np * 256 * 8, o_pv = o_nan + np * 8, o_tiles = (o_pv + np * 8 + 15) / 16 * 16, o_pk = o_tiles + n_tiles * 16,
                  need = o_pk + np * 4;
-    if (need > s->qs_cap) {
-        if (s->qs_buf) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(s->qs_buf)); s->qs_buf = nullptr; s->qs_cap = 0; }
-        CK(dev_alloc(&s->qs_buf, need));
-        s->qs_cap = need;
-    }
+    CK(grow_device(s, &s->qs_buf, &s->qs_cap, need));
     std::vector<unsigned char> in(need - o_pv);
     std::memcpy(in.data(), prefixes, np * 8);
     std::memcpy(in.data() + (o_tiles - o_pv), tiles.data(), n_tiles * 16);
-    for (size_t j = 0; j < np; ++j) {
-        const uint32_t k = (uint32_t)prefix_dim[j];
-        std::memcpy(in.data() + (o_pk - o_pv) + 4 * j, &k, 4);
-    }
+    stage_dims(in.data() + (o_pk - o_pv), prefix_dim, np);
     HIPCK(hipMemsetAsync(s->qs_buf, 0, o_pv, s->stream));
     HIPCK(hipMemcpyAsync(s->qs_buf + o_pv, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
     const uint64_t rows = s->qs_hi - s->qs_lo;
@@ -3125,11 +3194,8 @@ extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const in
         uint32_t kw_min = QS_SLOTS;
         for (size_t t = 0; t < n_tiles; ++t) kw_min = std::min(kw_min, tiles[4 * t + 3]);
         const uint64_t cpw = (uint64_t)(QS_THREADS / kw_min);
-        // ~2048 workgroups in all (four resident per CU), each at least 4 x QS_UNR row groups; a workgroup's uint32 bins stay below 2^31
-        uint64_t nby = std::max<uint64_t>(1, 2048 / n_tiles);
-        nby = std::min<uint64_t>(nby, (rows + 4 * QS_UNR * cpw - 1) / (4 * QS_UNR * cpw));
-        nby = std::max<uint64_t>(nby, (rows >> 31) + 1);
-        if (nby > 65535) return fail("bpm_quantile_histogram: window too large");
+        uint64_t nby = 1;
+        CK(rows_grid(rows, n_tiles, QS_UNR * cpw, "bpm_quantile_histogram", &nby));
         hipLaunchKernelGGL(qs_histogram_kernel, dim3((unsigned)n_tiles, (unsigned)nby), dim3(QS_THREADS), 0, s->stream, (const double*)s->hist,
                            s->ld, s->qs_lo, s->qs_hi, reinterpret_cast<const uint4*>(s->qs_buf + o_tiles),
                            reinterpret_cast<const uint32_t*>(s->qs_buf + o_pk), reinterpret_cast<const uint64_t*>(s->qs_buf + o_pv), bits,
@@ -3149,17 +3215,6 @@ extern "C" int bpm_quantile_histogram(bpm_handle_t s, int64_t n_prefix, const in
 // Over the window of super-chain rows >= n_burn (bpm_reduce_moments' selection): sum[k] = sum (x_k - center_k), cross[i * dim + j] = sum
 // (x_i - center_i)(x_j - center_j) (full and exactly symmetric), count = this rank's rows.  Keeps no state; every buffer is temporary.
 namespace {
-struct CovBuffers {
-    double* center = nullptr;
-    double* part = nullptr;
-    double* part1 = nullptr;
-    double* cross = nullptr;
-    double* sum = nullptr;
-    ~CovBuffers() {
-        for (double* p : {center, part, part1, cross, sum})
-            if (p) (void)hipFree(p);
-    }
-};
 template <int T>
 void cov_launch_diag(dim3 grid, hipStream_t st, const double* H, uint32_t ld, uint32_t dim, uint64_t r_lo, uint64_t r_hi, const double* c,
                      uint32_t n_blk, double* part, double* part1) {
@@ -3172,19 +3227,13 @@ extern "C" int bpm_reduce_cov(bpm_handle_t s, int64_t n_burn, const double* cent
     CK(check_handle(s));
     CK(set_device(s));
     if (!center || !sum || !cross || !count) return fail("bpm_reduce_cov: null argument");
-    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
-        return fail("bpm_reduce_cov: needs keep_history=True (a resident history of every generation)");
+    CK(require_resident_history(s, "bpm_reduce_cov"));
     const uint32_t dim = s->dim;
     if (dim > COV_DIM_LIMIT)
         return fail("bpm_reduce_cov: dim = " + std::to_string(dim) + " is beyond the supported limit of " + std::to_string(COV_DIM_LIMIT) +
                     " coordinates");
-    if (n_burn < 0) n_burn = 0;
-    const int64_t g0 = n_burn / s->N;
-    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
-    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
-    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));      // a partial first generation is counted by chain index
-    const uint64_t r_hi = (uint64_t)s->hist_rows * s->n_local;
-    const uint64_t r_lo = std::min(r_hi, (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0));
+    uint64_t r_lo = 0, r_hi = 0;
+    CK(super_chain_window(s, n_burn, &r_lo, &r_hi));
     const uint64_t rows = r_hi - r_lo;
     *count = (int64_t)rows;
     if (rows == 0) {
@@ -3209,71 +3258,39 @@ extern "C" int bpm_reduce_cov(bpm_handle_t s, int64_t n_burn, const double* cent
     if (need > mem_free)
         return fail("bpm_reduce_cov: dim = " + std::to_string(dim) + " needs " + std::to_string(need >> 20) +
                     " MiB of device memory for the dim x dim result and its partial sums; " + std::to_string(mem_free >> 20) + " MiB are free");
-    CovBuffers b;
-    CK(dev_alloc(&b.center, dim));
-    CK(dev_alloc(&b.part, part_n));
-    CK(dev_alloc(&b.part1, part1_n));
-    CK(dev_alloc(&b.cross, cross_n));
-    CK(dev_alloc(&b.sum, dim));
-    HIPCK(hipMemcpyAsync(b.center, center, dim * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    DevTemp<double> d_center, d_part, d_part1, d_cross, d_sum;
+    CK(d_center.alloc(dim));
+    CK(d_part.alloc(part_n));
+    CK(d_part1.alloc(part1_n));
+    CK(d_cross.alloc(cross_n));
+    CK(d_sum.alloc(dim));
+    HIPCK(hipMemcpyAsync(d_center.p, center, dim * sizeof(double), hipMemcpyHostToDevice, s->stream));
     const dim3 gd(nbx, n_blk);
     const double* H = s->hist;
     switch (T) {
-        case 1: cov_launch_diag<1>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        case 2: cov_launch_diag<2>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        case 3: cov_launch_diag<3>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        case 4: cov_launch_diag<4>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        case 5: cov_launch_diag<5>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        case 6: cov_launch_diag<6>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
-        default: cov_launch_diag<7>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, b.center, n_blk, b.part, b.part1); break;
+        case 1: cov_launch_diag<1>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        case 2: cov_launch_diag<2>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        case 3: cov_launch_diag<3>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        case 4: cov_launch_diag<4>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        case 5: cov_launch_diag<5>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        case 6: cov_launch_diag<6>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
+        default: cov_launch_diag<7>(gd, s->stream, H, s->ld, dim, r_lo, r_hi, d_center.p, n_blk, d_part.p, d_part1.p); break;
     }
     if (n_off > 0)
         hipLaunchKernelGGL((cov_partial_kernel<COV_BLK, false>), dim3(nbx, n_off), dim3(64), 0, s->stream, H, s->ld, dim, r_lo, r_hi,
-                           (const double*)b.center, n_blk, b.part, b.part1);
-    hipLaunchKernelGGL(cov_final_kernel, dim3(T * T, n_slots), dim3(COV_FIN_THREADS), 0, s->stream, (const double*)b.part, nbx, T, n_blk, dim,
-                       b.cross);
-    hipLaunchKernelGGL(cov_sum_final_kernel, dim3(n_tiles), dim3(256), 0, s->stream, (const double*)b.part1, nbx, T, dim, b.sum);
+                           (const double*)d_center.p, n_blk, d_part.p, d_part1.p);
+    hipLaunchKernelGGL(cov_final_kernel, dim3(T * T, n_slots), dim3(COV_FIN_THREADS), 0, s->stream, (const double*)d_part.p, nbx, T, n_blk, dim,
+                       d_cross.p);
+    hipLaunchKernelGGL(cov_sum_final_kernel, dim3(n_tiles), dim3(256), 0, s->stream, (const double*)d_part1.p, nbx, T, dim, d_sum.p);
     HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(cross, b.cross, cross_n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(sum, b.sum, dim * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(cross, d_cross.p, cross_n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(sum, d_sum.p, dim * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }
 
 // ---- posterior histograms (histograms.h; bipymc_amd/histograms.py applies NumPy's range rules, builds the edges and merges the ranks) ----
 // The counts of the reference's corner plot (corner.corner(samples), mc_plot/mc_plot.py:16-29), taken where the history lives.
-namespace {
-struct HistBuffers {
-    unsigned char* p = nullptr;
-    ~HistBuffers() {
-        if (p) (void)hipFree(p);
-    }
-};
-int hist_window_check(bpm_sampler* s, const char* who) {
-    if (!s->hs_valid) return fail(std::string(who) + ": call bpm_hist_range first");
-    if (s->hs_epoch != s->hist_epoch || s->hs_tabs != s->t_abs || s->hs_rows != s->hist_rows || s->hist_rows != s->rows_logical)
-        return fail(std::string(who) + ": the history changed since bpm_hist_range (a step, set_history or set_state); call it again");
-    return 0;
-}
-int hist_alloc(HistBuffers& b, size_t need, const char* who, const std::string& what) {
-    size_t mem_free = 0, mem_total = 0;
-    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
-    if (need > mem_free)
-        return fail(std::string(who) + ": " + what + " need " + std::to_string(need >> 20) + " MiB of device memory; " +
-                    std::to_string(mem_free >> 20) + " MiB are free");
-    CK(dev_alloc(&b.p, need));
-    return 0;
-}
-// workgroups along the rows: about `want` in all, each at least 4 sweeps of `rows_per_sweep`, none with 2^31 rows or more
-int hist_nby(uint64_t rows, uint64_t n_tiles, uint64_t rows_per_sweep, const char* who, uint64_t* nby_out) {
-    uint64_t nby = std::max<uint64_t>(1, 2048 / n_tiles);
-    nby = std::min<uint64_t>(nby, (rows + 4 * rows_per_sweep - 1) / (4 * rows_per_sweep));
-    nby = std::max<uint64_t>(nby, (rows >> 31) + 1);
-    if (nby > 65535) return fail(std::string(who) + ": window too large");
-    *nby_out = nby;
-    return 0;
-}
-}  // namespace
 constexpr uint32_t HS_LDS_TILE = 40u * 1024u;       // edges + one copy of the counts of a marginal tile
 constexpr uint32_t HS_LDS_TOTAL = 48u * 1024u;      // ... with the extra copies
 constexpr uint32_t HS_LDS_PAIRS = 32u * 1024u;      // the 2-D counts of a pair tile
@@ -3285,21 +3302,11 @@ constexpr uint32_t HS_TILE_PAIRS = 64;              // pairs per tile at most (1
 extern "C" int bpm_hist_range(bpm_handle_t s, int64_t n_burn, double* lo, double* hi, int64_t* n_nan, int64_t* n_inf, int64_t* count) {
     CK(check_handle(s));
     CK(set_device(s));
-    s->hs_valid = false;
+    s->hs_seen.valid = false;
     if (!lo || !hi || !n_nan || !n_inf || !count) return fail("bpm_hist_range: null argument");
-    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
-        return fail("bpm_hist_range: needs keep_history=True (a resident history of every generation)");
-    if (n_burn < 0) n_burn = 0;
-    const int64_t g0 = n_burn / s->N;
-    int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
-    first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
-    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));      // a partial first generation is counted by chain index
-    const uint64_t m_lo = (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0);
-    const uint64_t m_hi = (uint64_t)s->hist_rows * s->n_local;
-    s->hs_lo = std::min(m_lo, m_hi);
-    s->hs_hi = m_hi;
-    s->hs_epoch = s->hist_epoch; s->hs_tabs = s->t_abs; s->hs_rows = s->hist_rows;
-    s->hs_valid = true;
+    CK(require_resident_history(s, "bpm_hist_range"));
+    CK(super_chain_window(s, n_burn, &s->hs_lo, &s->hs_hi));
+    s->hs_seen.take(s);
     const uint64_t rows = s->hs_hi - s->hs_lo;
     *count = (int64_t)rows;
     const uint32_t ld = s->ld, dim = s->dim;
@@ -3308,12 +3315,12 @@ extern "C" int bpm_hist_range(bpm_handle_t s, int64_t n_burn, double* lo, double
     std::fill(out.begin(), out.begin() + ld, k_pinf);
     std::fill(out.begin() + ld, out.begin() + 2 * (size_t)ld, k_ninf);
     if (rows > 0) {
-        HistBuffers b;
-        CK(hist_alloc(b, out.size() * 8, "bpm_hist_range", "the per-coordinate results"));
+        DevTemp<unsigned char> b;
+        CK(b.alloc(out.size() * 8, "bpm_hist_range", "the per-coordinate results"));
         HIPCK(hipMemcpyAsync(b.p, out.data(), out.size() * 8, hipMemcpyHostToDevice, s->stream));
         const uint32_t kw = std::min<uint32_t>(ld, HS_THREADS), n_tiles = (ld + kw - 1) / kw;
         uint64_t nby = 1;
-        CK(hist_nby(rows, n_tiles, (uint64_t)(HS_THREADS / kw) * HS_UNR, "bpm_hist_range", &nby));
+        CK(rows_grid(rows, n_tiles, (uint64_t)(HS_THREADS / kw) * HS_UNR, "bpm_hist_range", &nby));
         hipLaunchKernelGGL(hs_range_kernel, dim3(n_tiles, (unsigned)nby), dim3(HS_THREADS), 0, s->stream, (const double*)s->hist, ld, s->hs_lo,
                            s->hs_hi, kw, reinterpret_cast<unsigned long long*>(b.p));
         HIPCK(hipGetLastError());
@@ -3341,31 +3348,23 @@ extern "C" int bpm_hist_marginals(bpm_handle_t s, int32_t n_dims, const int32_t*
     CK(check_handle(s));
     CK(set_device(s));
     if (!dims || !edges || !counts) return fail("bpm_hist_marginals: null argument");
-    CK(hist_window_check(s, "bpm_hist_marginals"));
+    CK(s->hs_seen.check(s, "bpm_hist_marginals", "bpm_hist_range"));
     if (bins < 1 || bins > HS_MAX_BINS)
         return fail("bpm_hist_marginals: bins = " + std::to_string(bins) + " is outside the supported 1 ... " + std::to_string(HS_MAX_BINS));
     if (n_dims < 1 || (uint32_t)n_dims > s->dim) return fail("bpm_hist_marginals: n_dims must be 1 ... dim");
     const uint32_t m = (uint32_t)n_dims, nb = (uint32_t)bins;
-    for (uint32_t j = 0; j < m; ++j) {
-        if (dims[j] < 0 || (uint32_t)dims[j] >= s->dim) return fail("bpm_hist_marginals: coordinate out of range");
-        const double* e = edges + (size_t)j * (nb + 1);
-        for (uint32_t i = 0; i <= nb; ++i)
-            if (!std::isfinite(e[i]) || (i > 0 && e[i] < e[i - 1])) return fail("bpm_hist_marginals: edges must be finite and non-decreasing");
-    }
+    CK(check_dims_edges(s, "bpm_hist_marginals", m, dims, nb, edges));
     const size_t n_counts = (size_t)m * nb, n_edges = (size_t)m * (nb + 1);
     std::fill(counts, counts + n_counts, (int64_t)0);
     const uint64_t rows = s->hs_hi - s->hs_lo;
     if (rows == 0) return 0;
     // [counts u64 | edges f64 | dims u32]
     const size_t o_e = n_counts * 8, o_d = o_e + n_edges * 8, need = o_d + (size_t)m * 4;
-    HistBuffers b;
-    CK(hist_alloc(b, need, "bpm_hist_marginals", "the counts and edges"));
+    DevTemp<unsigned char> b;
+    CK(b.alloc(need, "bpm_hist_marginals", "the counts and edges"));
     std::vector<unsigned char> in(need - o_e);
     std::memcpy(in.data(), edges, n_edges * 8);
-    for (uint32_t j = 0; j < m; ++j) {
-        const uint32_t k = (uint32_t)dims[j];
-        std::memcpy(in.data() + (o_d - o_e) + 4 * (size_t)j, &k, 4);
-    }
+    stage_dims(in.data() + (o_d - o_e), dims, m);
     HIPCK(hipMemsetAsync(b.p, 0, o_e, s->stream));
     HIPCK(hipMemcpyAsync(b.p + o_e, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
     // a tile: kw slots whose edges and counts fit HS_LDS_TILE; rep copies of the counts while they fit HS_LDS_TOTAL
@@ -3375,7 +3374,7 @@ extern "C" int bpm_hist_marginals(bpm_handle_t s, int32_t n_dims, const int32_t*
     const uint32_t rep = std::max(1u, std::min({8u, cpw, (HS_LDS_TOTAL - kw * (nb + 1) * 8) / (kw * nb * 4)}));
     const uint32_t lds = kw * (nb + 1) * 8 + rep * kw * nb * 4;
     uint64_t nby = 1;
-    CK(hist_nby(rows, n_tiles, (uint64_t)cpw * HS_UNR, "bpm_hist_marginals", &nby));
+    CK(rows_grid(rows, n_tiles, (uint64_t)cpw * HS_UNR, "bpm_hist_marginals", &nby));
     hipLaunchKernelGGL(hs_marginal_kernel, dim3(n_tiles, (unsigned)nby), dim3(HS_THREADS), lds, s->stream, (const double*)s->hist, s->ld,
                        s->hs_lo, s->hs_hi, reinterpret_cast<const uint32_t*>(b.p + o_d), m, nb, reinterpret_cast<const double*>(b.p + o_e), kw,
                        rep, reinterpret_cast<unsigned long long*>(b.p));
@@ -3393,7 +3392,7 @@ extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dim
     CK(check_handle(s));
     CK(set_device(s));
     if (!dims || !edges2d || !pair_a || !pair_b || !counts2d) return fail("bpm_hist_pairs: null argument");
-    CK(hist_window_check(s, "bpm_hist_pairs"));
+    CK(s->hs_seen.check(s, "bpm_hist_pairs", "bpm_hist_range"));
     if (bins2d < 1 || bins2d > HS_MAX_BINS2D)
         return fail("bpm_hist_pairs: bins2d = " + std::to_string(bins2d) + " is outside the supported 1 ... " + std::to_string(HS_MAX_BINS2D));
     if (n_dims < 1 || (uint32_t)n_dims > s->dim) return fail("bpm_hist_pairs: n_dims must be 1 ... dim");
@@ -3401,12 +3400,7 @@ extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dim
         return fail("bpm_hist_pairs: n_pairs = " + std::to_string(n_pairs) + " is outside the supported 1 ... 16777216");
     const uint32_t m = (uint32_t)n_dims, nb = (uint32_t)bins2d, cells = nb * nb;
     const size_t P = (size_t)n_pairs;
-    for (uint32_t j = 0; j < m; ++j) {
-        if (dims[j] < 0 || (uint32_t)dims[j] >= s->dim) return fail("bpm_hist_pairs: coordinate out of range");
-        const double* e = edges2d + (size_t)j * (nb + 1);
-        for (uint32_t i = 0; i <= nb; ++i)
-            if (!std::isfinite(e[i]) || (i > 0 && e[i] < e[i - 1])) return fail("bpm_hist_pairs: edges must be finite and non-decreasing");
-    }
+    CK(check_dims_edges(s, "bpm_hist_pairs", m, dims, nb, edges2d));
     for (size_t p = 0; p < P; ++p)
         if (pair_a[p] < 0 || pair_a[p] >= n_dims || pair_b[p] < 0 || pair_b[p] >= n_dims)
             return fail("bpm_hist_pairs: a pair names a coordinate that is not in dims");
@@ -3439,9 +3433,9 @@ extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dim
     // [counts u64 | edges f64 | tiles 16 B each | pl 8 B each | uslot u32 | dims u32]
     const size_t o_e = n_counts * 8, o_t = o_e + n_edges * 8, o_pl = o_t + n_tiles * 16, o_u = o_pl + P * 8, o_d = o_u + uslot.size() * 4,
                  need = o_d + (size_t)m * 4;
-    HistBuffers b;
-    CK(hist_alloc(b, need, "bpm_hist_pairs",
-                  std::to_string(n_pairs) + " pairs of " + std::to_string(bins2d) + " x " + std::to_string(bins2d) + " 64-bit counts"));
+    DevTemp<unsigned char> b;
+    CK(b.alloc(need, "bpm_hist_pairs",
+               std::to_string(n_pairs) + " pairs of " + std::to_string(bins2d) + " x " + std::to_string(bins2d) + " 64-bit counts"));
     std::fill(counts2d, counts2d + n_counts, (int64_t)0);
     if (rows == 0) return 0;
     std::vector<unsigned char> in(need - o_e);
@@ -3449,15 +3443,12 @@ extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dim
     std::memcpy(in.data() + (o_t - o_e), tiles.data(), n_tiles * 16);
     std::memcpy(in.data() + (o_pl - o_e), pl.data(), P * 8);
     std::memcpy(in.data() + (o_u - o_e), uslot.data(), uslot.size() * 4);
-    for (uint32_t j = 0; j < m; ++j) {
-        const uint32_t k = (uint32_t)dims[j];
-        std::memcpy(in.data() + (o_d - o_e) + 4 * (size_t)j, &k, 4);
-    }
+    stage_dims(in.data() + (o_d - o_e), dims, m);
     HIPCK(hipMemsetAsync(b.p, 0, o_e, s->stream));
     HIPCK(hipMemcpyAsync(b.p + o_e, in.data(), in.size(), hipMemcpyHostToDevice, s->stream));
     const uint32_t lds = nu_max * (nb + 1) * 8 + np_max * cells * 4 + HS_THREADS * HS_UNR;
     uint64_t nby = 1;
-    CK(hist_nby(rows, n_tiles, (uint64_t)(HS_THREADS / nu_max) * HS_UNR, "bpm_hist_pairs", &nby));
+    CK(rows_grid(rows, n_tiles, (uint64_t)(HS_THREADS / nu_max) * HS_UNR, "bpm_hist_pairs", &nby));
     hipLaunchKernelGGL(hs_pair_kernel, dim3((unsigned)n_tiles, (unsigned)nby), dim3(HS_THREADS), lds, s->stream, (const double*)s->hist, s->ld,
                        s->hs_lo, s->hs_hi, reinterpret_cast<const uint4*>(b.p + o_t), reinterpret_cast<const uint32_t*>(b.p + o_u),
                        reinterpret_cast<const uint2*>(b.p + o_pl), reinterpret_cast<const uint32_t*>(b.p + o_d), nb,

@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib as L
 from . import comm as _comm
+from ._history_stats import HistoryStatistics
 from .chain import DetachedChain, McmcChain
 from .utils import _target
 
@@ -49,7 +50,7 @@ def _default_engine_factory(**kw):
 _engine_factory = _default_engine_factory
 
 
-class DeMcMpi(object):
+class DeMcMpi(HistoryStatistics):
     """!
     @brief DE-MC population sampler, one process per MI355X.
     """
@@ -438,44 +439,12 @@ class DeMcMpi(object):
         S2 = np.sum([p[2] for p in parts], axis=0)
         return sh + S1 / n, np.sqrt(np.maximum(S2 / n - (S1 / n) ** 2, 0.0))
 
-    def convergence_diagnostics(self, n_burn=0, max_lag=None):
-        """Split-chain R-hat and effective sample size per coordinate over the history after n_burn super-chain rows (param_est's unit;
-        the window starts at the first whole generation), reduced on the GPU(s) without moving the history (bipymc_amd/diagnostics.py).
-        Collective: every rank calls it; every rank gets the same bits.  max_lag bounds the autocorrelation lags read (ess_capped says
-        where it ended the sum).  -> diagnostics.ConvergenceDiagnostics"""
-        from . import diagnostics as _diag
-        eng = self._engine
-        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
-        return _diag.compute(eng.diag_split_moments, eng.diag_autocov, self.comm.allgather, g0, g1, max_lag=max_lag)
+    # convergence_diagnostics, param_est_quantiles, param_est_cov, param_est_hist: HistoryStatistics, through these two
+    def _stats_engine(self, who):
+        return self._engine
 
-    def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
-        """np.quantile(param_est(n_burn)[2], q, axis=0), exactly, computed on the GPU(s) without moving the history (an MSD radix select,
-        bipymc_amd/quantiles.py).  Collective: every rank calls it; every rank gets the same bits.  -> (len(q), dim), or (dim,) for a
-        scalar q"""
-        from . import quantiles as _qs
-        eng = self._engine
-        return _qs.compute(eng.quantile_begin, eng.quantile_histogram, self.comm.allgather, n_burn, q, dim=eng.dim)
-
-    def param_est_cov(self, n_burn=0):
-        """Posterior mean, covariance (ddof = 1) and, through .corr(), correlation of the super-chain rows >= n_burn: what
-        np.cov(param_est(n_burn)[2], rowvar=False) computes, reduced on the GPU(s) without moving the history (an FP64 matrix-core SYRK
-        centred on the global mean, bipymc_amd/covariance.py).  Collective: every rank calls it; every rank gets the same bits.
-        -> covariance.PosteriorCovariance(mean, cov, n)"""
-        from . import covariance as _cov
-        eng = self._engine
-        return _cov.compute(eng.reduce_moments, eng.reduce_cov, self.comm.allgather, n_burn, eng.dim)
-
-    def param_est_hist(self, n_burn=0, bins=20, range=None, dims=None, pairs=None, bins2d=None):
-        """The counts of a corner plot over the super-chain rows >= n_burn: per coordinate of `dims` (None: all) exactly
-        np.histogram(param_est(n_burn)[2][:, k], bins, range)[0], per pair of `pairs` (None: none; "all": every a < b of dims; or (a, b)
-        tuples) exactly np.histogram2d(..., bins2d, range=[ra, rb])[0], counted on the GPU(s) without moving the history
-        (bipymc_amd/histograms.py; range: None for each coordinate's (min, max), (lo, hi) for all, or one (lo, hi) per coordinate).
-        Collective: every rank calls it; every rank gets the same bits.
-        -> histograms.PosteriorHistograms(dims, edges, counts, pairs, edges2d, counts2d, n) with .density()"""
-        from . import histograms as _hs
-        eng = self._engine
-        return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, self.comm.allgather, n_burn, eng.dim, bins=bins, range=range,
-                           dims=dims, pairs=pairs, bins2d=bins2d)
+    def _stats_allgather(self, obj):
+        return self.comm.allgather(obj)
 
     def super_chain_mpi(self, collection_rank=0):
         return self._super_chain(collection_rank)

@@ -22,6 +22,8 @@ import math
 
 import numpy as np
 
+from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
+
 ConvergenceDiagnostics = collections.namedtuple(
     "ConvergenceDiagnostics", ["r_hat", "ess", "tau", "ess_capped", "lags_used", "n_half_chains", "n_draws", "window"])
 ConvergenceDiagnostics.__doc__ = """r_hat, ess, tau: (dim,) float64; ess_capped: (dim,) bool -- max_lag ended the autocorrelation sum before Geyer's
@@ -158,7 +160,3 @@ def compute(split_moments, autocov, allgather, g0, g1, max_lag=None, block=LAG_B
     ess = (m * n) / tau
     return ConvergenceDiagnostics(r_hat=r_hat, ess=ess, tau=tau, ess_capped=capped, lags_used=lags, n_half_chains=int(m), n_draws=int(n),
                                   window=(int(g0), int(g1)))
-
-
-def single_process_allgather(obj):
-    return [obj]

@@ -19,6 +19,9 @@ import collections
 
 import numpy as np
 
+from ._history_stats import check_n_burn, empty_window
+from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
+
 MAX_BINS = 1024
 MAX_BINS2D = 64
 
@@ -120,10 +123,8 @@ def compute(hist_range, hist_marginals, hist_pairs, allgather, n_burn, dim, bins
     dims, edges) -> (m, bins) counts; hist_pairs(dims, edges2d, pair_a, pair_b) -> (P, bins2d, bins2d) counts (pair_a / pair_b are positions
     in dims); allgather(obj) -> [obj of every rank] in rank order ([obj] for one process, single_process_allgather).
     -> PosteriorHistograms, the same bits on every rank"""
-    n_burn = int(n_burn)
+    n_burn = check_n_burn("param_est_hist", n_burn)
     dim = int(dim)
-    if n_burn < 0:
-        raise ValueError("param_est_hist: n_burn must be >= 0 (got %d)" % n_burn)
     bins = check_bins(bins, MAX_BINS, "bins")
     dm = check_dims(dims, dim)
     pr = check_pairs(pairs, dm)
@@ -133,7 +134,7 @@ def compute(hist_range, hist_marginals, hist_pairs, allgather, n_burn, dim, bins
     parts = allgather(hist_range(n_burn))
     n = sum(int(p[0]) for p in parts)
     if n == 0:
-        raise ValueError("param_est_hist: the window is empty (n_burn = %d is at or beyond the last super-chain row)" % n_burn)
+        raise empty_window("param_est_hist", n_burn)
     lo = np.min([np.asarray(p[1], dtype=np.float64).reshape(dim) for p in parts], axis=0)[dm]
     hi = np.max([np.asarray(p[2], dtype=np.float64).reshape(dim) for p in parts], axis=0)[dm]
     n_nan = np.sum([np.asarray(p[3], dtype=np.int64).reshape(dim) for p in parts], axis=0)[dm]
@@ -152,7 +153,3 @@ def compute(hist_range, hist_marginals, hist_pairs, allgather, n_burn, dim, bins
         for c in allgather(hist_pairs(dm, edges2d, pa, pb)):
             counts2d += np.asarray(c, dtype=np.int64).reshape(len(pr), bins2d, bins2d)
     return PosteriorHistograms(dm, edges, counts, pr, edges2d, counts2d, n)
-
-
-def single_process_allgather(obj):
-    return [obj]

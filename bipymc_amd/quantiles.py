@@ -17,6 +17,9 @@ from __future__ import division
 
 import numpy as np
 
+from ._history_stats import check_n_burn, empty_window
+from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
+
 DEFAULT_Q = (0.05, 0.5, 0.95)
 DIGIT_BITS = 8
 PASSES = 64 // DIGIT_BITS
@@ -139,18 +142,13 @@ def compute(begin, histogram, allgather, n_burn, q=DEFAULT_Q, dim=None):
     allgather(obj) -> [obj of every rank] in rank order ([obj] for one process, single_process_allgather).  -> np.quantile's result,
     shape q.shape + (dim,)"""
     q = check_q(q)
-    if int(n_burn) < 0:
-        raise ValueError("param_est_quantiles: n_burn must be >= 0 (got %d)" % int(n_burn))
-    n = int(np.sum(np.asarray(allgather(begin(int(n_burn))), dtype=np.int64)))
+    n_burn = check_n_burn("param_est_quantiles", n_burn)
+    n = int(np.sum(np.asarray(allgather(begin(n_burn)), dtype=np.int64)))
     if n == 0:
-        raise ValueError("param_est_quantiles: the window is empty (n_burn = %d is at or beyond the last super-chain row)" % int(n_burn))
+        raise empty_window("param_est_quantiles", n_burn)
     prev, nxt, _ = targets(n, q)
     ranks = np.unique(np.concatenate([prev.reshape(-1), nxt.reshape(-1)]))
     keys, n_nan = select(histogram, allgather, n, ranks, int(dim))
     vals = from_key(keys)
     pos = {int(r): i for i, r in enumerate(ranks)}
     return finish(n, q, lambda rr: vals[[pos[int(r)] for r in rr]], n_nan > 0)
-
-
-def single_process_allgather(obj):
-    return [obj]

@@ -11,11 +11,13 @@ from __future__ import division, print_function
 import numpy as np
 
 from . import _lib as L
+from ._history_stats import HistoryStatistics
 from .chain import DetachedChain
+from .comm import single_process_allgather
 from .utils import _target
 
 
-class DeMc(object):
+class DeMc(HistoryStatistics):
     def __init__(self, log_like_fn, n_chains=8, ln_kwargs={}, **proposal_kwargs):
         assert n_chains >= 4                                         # samplers.py:249
         self.n_chains = int(n_chains)
@@ -107,45 +109,12 @@ class DeMc(object):
         """samplers.py:320-326: row g*n_chains + i = chain i at generation g."""
         return self._engine.get_history().reshape(-1, self.am_chains[0].dim).copy()
 
-    def convergence_diagnostics(self, n_burn=0, max_lag=None):
-        """Split-chain R-hat and effective sample size per coordinate over the super-chain rows after n_burn (the window starts at the
-        first whole generation), reduced on the GPU (bipymc_amd/diagnostics.py).  -> diagnostics.ConvergenceDiagnostics"""
-        from . import diagnostics as _diag
-        eng = self._engine
-        if eng is None:
-            raise RuntimeError("convergence_diagnostics: run_mcmc first")
-        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
-        return _diag.compute(eng.diag_split_moments, eng.diag_autocov, _diag.single_process_allgather, g0, g1, max_lag=max_lag)
+    def _stats_engine(self, who):
+        if self._engine is None:
+            raise RuntimeError("%s: run_mcmc first" % who)
+        return self._engine
 
-    def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
-        """np.quantile(param_est(n_burn)[2], q, axis=0), exactly, computed on the GPU without moving the history (bipymc_amd/quantiles.py).
-        -> (len(q), dim), or (dim,) for a scalar q"""
-        from . import quantiles as _qs
-        eng = self._engine
-        if eng is None:
-            raise RuntimeError("param_est_quantiles: run_mcmc first")
-        return _qs.compute(eng.quantile_begin, eng.quantile_histogram, _qs.single_process_allgather, n_burn, q, dim=eng.dim)
-
-    def param_est_cov(self, n_burn=0):
-        """Posterior mean, covariance (ddof = 1) and, through .corr(), correlation of the super-chain rows >= n_burn: what
-        np.cov(param_est(n_burn)[2], rowvar=False) computes, reduced on the GPU without moving the history (bipymc_amd/covariance.py).
-        -> covariance.PosteriorCovariance(mean, cov, n)"""
-        from . import covariance as _cov
-        eng = self._engine
-        if eng is None:
-            raise RuntimeError("param_est_cov: run_mcmc first")
-        return _cov.compute(eng.reduce_moments, eng.reduce_cov, _cov.single_process_allgather, n_burn, eng.dim)
-
-    def param_est_hist(self, n_burn=0, bins=20, range=None, dims=None, pairs=None, bins2d=None):
-        """The counts of a corner plot over the super-chain rows >= n_burn: np.histogram's per coordinate of `dims`, np.histogram2d's per
-        pair of `pairs`, exactly, counted on the GPU without moving the history (bipymc_amd/histograms.py).
-        -> histograms.PosteriorHistograms(dims, edges, counts, pairs, edges2d, counts2d, n) with .density()"""
-        from . import histograms as _hs
-        eng = self._engine
-        if eng is None:
-            raise RuntimeError("param_est_hist: run_mcmc first")
-        return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, _hs.single_process_allgather, n_burn, eng.dim, bins=bins,
-                           range=range, dims=dims, pairs=pairs, bins2d=bins2d)
+    _stats_allgather = staticmethod(single_process_allgather)
 
     def param_est(self, n_burn):
         chain_slice = self.super_chain[n_burn:, :]                      # samplers.py:311-315

@@ -6,10 +6,8 @@ ranks; no side effects; errors.
 Tolerance: the derived bound of tests/test_covariance_host.py (its docstring), element by element
     |cov_dev - cov_numpy| <= 2 (n + 4) u sqrt(C_ii C_jj),   |mean_dev - mean_numpy| <= 2 (n + 4) u (|mean| + sqrt(C_kk)),
 and (n + 4) u sqrt(C_ii C_jj) against a np.longdouble two-pass covariance where n <= 10^5.  Nothing else."""
-import ctypes as C
 import os
 import statistics
-import subprocess
 import sys
 
 import numpy as np
@@ -20,15 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+from _history_cases import _dream_class, _engine, group_single_rank, local_group, per_rank, run_rank_processes  # noqa: E402
 from test_covariance_host import check_against_numpy, cov_bound  # noqa: E402
-
-
-def _engine(N, d, **kw):
-    from bipymc_amd import _lib as L
-    from bipymc_amd.engine import HipEngine
-    from bipymc_amd.utils import d100_gauss
-    tid, tp, _ = d100_gauss.Gauss_100D(rho=0.5, dim=d)._bpm_target_spec()
-    return HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=5, **kw)
 
 
 def _device(eng, n_burn):
@@ -115,15 +106,6 @@ def test_installed_history_dim_1800():
     for n_burn in (0, N + 3):
         _check(_device(e, n_burn), X.reshape(-1, d)[n_burn:])
     e.close()
-
-
-def _dream_class(N, d, gens, shuffle=True, rho=0.5):
-    from bipymc_amd import DreamMpi
-    from bipymc_amd.utils import d100_gauss
-    t = d100_gauss.Gauss_100D(rho=rho, dim=d)
-    s = DreamMpi(t.ln_like, np.zeros(d), n_chains=N, n_cr_gen=10, burnin_gen=50, seed=21)
-    s.run_mcmc(N * (gens + 1), shuffle=shuffle)
-    return s
 
 
 def test_dream_shuffled_history_partial_generation():
@@ -254,38 +236,14 @@ def test_dim_beyond_the_limit_is_named():
 
 
 def _group_cov(R):
-    """R ranks as handles of this process over the push exchange (the test variant's local group), stepped as tests/_push_worker.py does"""
-    from bipymc_amd import _lib as L
     from bipymc_amd import covariance as CV
-    from bipymc_amd.engine import HipEngine
-    from _push_worker import case_spec, start_state
-    spec, algo, N, kw, G = case_spec("dream_gauss100_long")
-    tid, tp, d = spec
-    uid = b"BPMLOCAL" + bytes(120)
-    ranks = [HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, rank=r, world_size=R, nccl_uid=uid,
-                       lib=L.load_test(), **kw) for r in range(R)]
-    blobs = [e.push_export() for e in ranks]
-    for e in ranks:
-        e.push_connect(blobs)
-    arr = (C.c_void_p * R)(*[e._h for e in ranks])
-    ok = C.c_int32(0)
-    L.check(ranks[0].lib.bpm_push_selftest(arr, R, C.byref(ok)), ranks[0].lib)
-    assert ok.value == 1
-    x0 = start_state("dream_gauss100_long", N, d)
-    for e in ranks:
-        e.set_state(x0)
-        e.begin_run(flip=0.4)
-    L.check(ranks[0].lib.bpm_local_group_step(arr, R, G), ranks[0].lib)
+    ranks, N, d = local_group(R)
     n_burn = N * 7 + N // 2 + 1                 # a partial generation that starts inside a later rank's chains
     # every rank runs the driver on the gathered parts, as a communicator's allgather hands them out
-    res = [CV.compute(lambda nb: [e.reduce_moments(nb) for e in ranks], lambda nb, c: [e.reduce_cov(nb, c) for e in ranks],
-                      lambda x: x, n_burn, d) for _ in ranks]
+    res = [CV.compute(per_rank(ranks, "reduce_moments"), per_rank(ranks, "reduce_cov"), lambda x: x, n_burn, d) for _ in ranks]
     for e in ranks:
         e.close()
-    one = HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, **kw)
-    one.set_state(x0)
-    one.begin_run(flip=0.4)
-    one.step(G)
+    one = group_single_rank()
     ref = _device(one, n_burn)
     H = one.get_history()
     one.close()
@@ -304,22 +262,8 @@ def test_local_group_against_single_rank(R):
 
 
 def test_rank_processes_sharing_the_gpu(tmp_path):
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env["BPM_PUSH_TIMEOUT_S"] = "60"
-    worker = os.path.join(HERE, "_covariance_worker.py")
-    subprocess.check_call(["timeout", "-k", "10", "300", sys.executable, worker, str(tmp_path), "0", "1"], env=env, timeout=330)
-    procs = [subprocess.Popen(["timeout", "-k", "10", "300", sys.executable, worker, str(tmp_path), str(r), "2"], env=env) for r in range(2)]
-    for p in procs:
-        try:
-            assert p.wait(timeout=330) == 0
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
+    one, r = run_rank_processes(tmp_path, "cov")
     from bipymc_amd.covariance import PosteriorCovariance
-    one = np.load(os.path.join(str(tmp_path), "cov_w1_rank0.npz"))
-    r = [np.load(os.path.join(str(tmp_path), "cov_w2_rank%d.npz" % k)) for k in range(2)]
     pcs = [PosteriorCovariance(x["mean"], x["cov"], int(x["n"])) for x in [one] + r]
     _check(pcs[0], one["chain_slice"])
     _same_bits(pcs[1], pcs[2])

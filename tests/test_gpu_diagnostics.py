@@ -1,9 +1,7 @@
 """Convergence diagnostics on the GPU (bpm_diag_split_moments / bpm_diag_autocov + bipymc_amd/diagnostics.py): split-chain R-hat and ESS
 of the resident history against the NumPy restatement of tests/test_diagnostics_host.py, on installed AR(1) histories with known answers,
 on sampler histories (position-ordered, snooker, wide rows, the serial class), at cfg2's size, across ranks; no side effects; errors."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,15 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+from _history_cases import _dream_class, _engine, group_single_rank, local_group, per_rank, run_rank_processes  # noqa: E402
 from test_diagnostics_host import _ar1, reference  # noqa: E402
-
-
-def _engine(N, d, G=None, **kw):
-    from bipymc_amd import _lib as L
-    from bipymc_amd.engine import HipEngine
-    from bipymc_amd.utils import d100_gauss
-    tid, tp, _ = d100_gauss.Gauss_100D(rho=0.5, dim=d)._bpm_target_spec()
-    return HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=5, **kw)
 
 
 def _device(eng, g0=0, g1=None, max_lag=None):
@@ -72,15 +63,6 @@ def test_known_answers_on_installed_ar1_histories():
     assert np.isnan(got.r_hat[2]) and np.isnan(got.ess[2])
     _check(got, reference(Z))
     e.close()
-
-
-def _dream_class(N, d, gens, shuffle=True, n_burn=0):
-    from bipymc_amd import DreamMpi
-    from bipymc_amd.utils import d100_gauss
-    t = d100_gauss.Gauss_100D(rho=0.5, dim=d)
-    s = DreamMpi(t.ln_like, np.zeros(d), n_chains=N, n_cr_gen=10, burnin_gen=50, seed=21)
-    s.run_mcmc(N * (gens + 1), shuffle=shuffle)
-    return s
 
 
 def test_dream_position_ordered_history_against_numpy():
@@ -193,37 +175,13 @@ def test_errors_say_what_is_wrong():
 
 
 def _group_diag(R):
-    """R ranks as handles of this process over the push exchange (the test variant's local group), stepped as tests/_push_worker.py does"""
-    from bipymc_amd import _lib as L
     from bipymc_amd import diagnostics as D
-    from bipymc_amd.engine import HipEngine
-    from _push_worker import case_spec, start_state
-    spec, algo, N, kw, G = case_spec("dream_gauss100_long")
-    tid, tp, d = spec
-    uid = b"BPMLOCAL" + bytes(120)
-    ranks = [HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, rank=r, world_size=R, nccl_uid=uid,
-                       lib=L.load_test(), **kw) for r in range(R)]
-    blobs = [e.push_export() for e in ranks]
-    for e in ranks:
-        e.push_connect(blobs)
-    arr = (C.c_void_p * R)(*[e._h for e in ranks])
-    ok = C.c_int32(0)
-    L.check(ranks[0].lib.bpm_push_selftest(arr, R, C.byref(ok)), ranks[0].lib)
-    assert ok.value == 1
-    x0 = start_state("dream_gauss100_long", N, d)
-    for e in ranks:
-        e.set_state(x0)
-        e.begin_run(flip=0.4)
-    L.check(ranks[0].lib.bpm_local_group_step(arr, R, G), ranks[0].lib)
+    ranks, N, d = local_group(R)
     g0, g1 = D.window(N * 7 + 1, N, ranks[0].history_rows())
-    res = D.compute(lambda a, b: [e.diag_split_moments(a, b) for e in ranks], lambda t0, nl: [e.diag_autocov(t0, nl) for e in ranks],
-                    lambda x: x, g0, g1)
+    res = D.compute(per_rank(ranks, "diag_split_moments"), per_rank(ranks, "diag_autocov"), lambda x: x, g0, g1)
     for e in ranks:
         e.close()
-    one = HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, **kw)
-    one.set_state(x0)
-    one.begin_run(flip=0.4)
-    one.step(G)
+    one = group_single_rank()
     ref = _device(one, g0, g1)
     one.close()
     return res, ref
@@ -238,21 +196,7 @@ def test_local_group_equals_single_rank(R):
 
 
 def test_rank_processes_sharing_the_gpu(tmp_path):
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env["BPM_PUSH_TIMEOUT_S"] = "60"
-    worker = os.path.join(HERE, "_diag_worker.py")
-    subprocess.check_call([sys.executable, worker, str(tmp_path), "0", "1"], env=env, timeout=300)
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path), str(r), "2"], env=env) for r in range(2)]
-    for p in procs:
-        try:
-            assert p.wait(timeout=300) == 0
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    one = np.load(os.path.join(str(tmp_path), "diag_w1_rank0.npz"))
-    r = [np.load(os.path.join(str(tmp_path), "diag_w2_rank%d.npz" % k)) for k in range(2)]
+    one, r = run_rank_processes(tmp_path, "diag")
     for f in r[0].files:
         assert np.array_equal(r[0][f], r[1][f], equal_nan=True), f
     np.testing.assert_allclose(r[0]["r_hat"], one["r_hat"], rtol=1e-12)

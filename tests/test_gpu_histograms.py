@@ -3,9 +3,7 @@ np.histogram / np.histogram2d on param_est(n_burn)[2] exactly (np.array_equal, n
 bit -- on installed histories with values on and one ulp beside every edge, a large offset with a tiny spread, denormals, a constant
 column, NaN and infinities, on sampler histories (DREAM, DE-MC with snooker, the serial class, wide rows), at cfg2's size, across ranks;
 no side effects; errors."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,15 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+from _history_cases import _dream_class, _engine, group_single_rank, local_group, per_rank, run_rank_processes  # noqa: E402
 from test_histograms_host import check_against_numpy  # noqa: E402
-
-
-def _engine(N, d, **kw):
-    from bipymc_amd import _lib as L
-    from bipymc_amd.engine import HipEngine
-    from bipymc_amd.utils import d100_gauss
-    tid, tp, _ = d100_gauss.Gauss_100D(rho=0.5, dim=d)._bpm_target_spec()
-    return HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=5, **kw)
 
 
 def _device(eng, n_burn, **kw):
@@ -125,15 +116,6 @@ def test_installed_history_explicit_ranges_nan_and_inf(bins, bins2d):
         _device(e, N * 6, dims=[4])
     _check(_device(e, N * 7), _window(X, N * 7), {})      # ... and behind all of them the column is fine
     e.close()
-
-
-def _dream_class(N, d, gens, shuffle=True):
-    from bipymc_amd import DreamMpi
-    from bipymc_amd.utils import d100_gauss
-    t = d100_gauss.Gauss_100D(rho=0.5, dim=d)
-    s = DreamMpi(t.ln_like, np.zeros(d), n_chains=N, n_cr_gen=10, burnin_gen=50, seed=21)
-    s.run_mcmc(N * (gens + 1), shuffle=shuffle)
-    return s
 
 
 def test_dream_shuffled_history_partial_generation():
@@ -308,37 +290,14 @@ KW_GROUP = dict(pairs=[(0, 1), (99, 3), (3, 99), (50, 51)], bins2d=16)
 
 
 def _group_histograms(R):
-    """R ranks as handles of this process over the push exchange (the test variant's local group), stepped as tests/_push_worker.py does"""
-    from bipymc_amd import _lib as L
     from bipymc_amd import histograms as HS
-    from bipymc_amd.engine import HipEngine
-    from _push_worker import case_spec, start_state
-    spec, algo, N, kw, G = case_spec("dream_gauss100_long")
-    tid, tp, d = spec
-    uid = b"BPMLOCAL" + bytes(120)
-    ranks = [HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, rank=r, world_size=R, nccl_uid=uid,
-                       lib=L.load_test(), **kw) for r in range(R)]
-    blobs = [e.push_export() for e in ranks]
-    for e in ranks:
-        e.push_connect(blobs)
-    arr = (C.c_void_p * R)(*[e._h for e in ranks])
-    ok = C.c_int32(0)
-    L.check(ranks[0].lib.bpm_push_selftest(arr, R, C.byref(ok)), ranks[0].lib)
-    assert ok.value == 1
-    x0 = start_state("dream_gauss100_long", N, d)
-    for e in ranks:
-        e.set_state(x0)
-        e.begin_run(flip=0.4)
-    L.check(ranks[0].lib.bpm_local_group_step(arr, R, G), ranks[0].lib)
+    ranks, N, d = local_group(R)
     n_burn = N * 7 + N // 2 + 1                 # a partial generation that starts inside a later rank's chains
-    res = HS.compute(lambda nb: [e.hist_range(nb) for e in ranks], lambda a, b: [e.hist_marginals(a, b) for e in ranks],
-                     lambda a, b, c, d_: [e.hist_pairs(a, b, c, d_) for e in ranks], lambda x: x, n_burn, d, **KW_GROUP)
+    res = HS.compute(per_rank(ranks, "hist_range"), per_rank(ranks, "hist_marginals"), per_rank(ranks, "hist_pairs"), lambda x: x, n_burn, d,
+                     **KW_GROUP)
     for e in ranks:
         e.close()
-    one = HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, **kw)
-    one.set_state(x0)
-    one.begin_run(flip=0.4)
-    one.step(G)
+    one = group_single_rank()
     ref = _device(one, n_burn, **KW_GROUP)
     H = one.get_history()
     one.close()
@@ -354,22 +313,8 @@ def test_local_group_equals_single_rank(R):
 
 
 def test_rank_processes_sharing_the_gpu(tmp_path):
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env["BPM_PUSH_TIMEOUT_S"] = "60"
-    worker = os.path.join(HERE, "_histogram_worker.py")
-    subprocess.check_call([sys.executable, worker, str(tmp_path), "0", "1"], env=env, timeout=300)
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path), str(r), "2"], env=env) for r in range(2)]
-    for p in procs:
-        try:
-            assert p.wait(timeout=300) == 0
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    one = np.load(os.path.join(str(tmp_path), "hs_w1_rank0.npz"))
-    r = [np.load(os.path.join(str(tmp_path), "hs_w2_rank%d.npz" % k)) for k in range(2)]
-    from _histogram_worker import KW
+    one, r = run_rank_processes(tmp_path, "hist")
+    from _stats_worker import KW
     from bipymc_amd.histograms import PosteriorHistograms
     ph = PosteriorHistograms(np.arange(10), one["edges"], one["counts"], np.asarray(KW["pairs"]), one["edges2d"], one["counts2d"], int(one["n"]))
     _check(ph, one["chain_slice"], KW)

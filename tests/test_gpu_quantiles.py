@@ -2,9 +2,7 @@
 np.quantile(param_est(n_burn)[2], q, axis=0) value for value (np.array_equal, equal_nan=True) -- on installed histories with NaN, inf,
 signed zeros, ties and padding columns, on sampler histories (shuffled DREAM, snooker, wide rows, the serial class), at cfg2's size,
 across ranks; no side effects; errors."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,15 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+from _history_cases import _dream_class, _engine, group_single_rank, local_group, per_rank, run_rank_processes  # noqa: E402
+
 QS = [0.0, 0.05, 0.5, 1.0 / 3.0, 0.95, 1.0]
-
-
-def _engine(N, d, **kw):
-    from bipymc_amd import _lib as L
-    from bipymc_amd.engine import HipEngine
-    from bipymc_amd.utils import d100_gauss
-    tid, tp, _ = d100_gauss.Gauss_100D(rho=0.5, dim=d)._bpm_target_spec()
-    return HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=5, **kw)
 
 
 def _device(eng, n_burn, q=QS):
@@ -64,15 +56,6 @@ def test_installed_history_with_nan_inf_signed_zeros_and_ties():
     assert (got < 0).all()
     _same(got, _want(Y, 0, [0.0, 1.0]))
     e.close()
-
-
-def _dream_class(N, d, gens, shuffle=True):
-    from bipymc_amd import DreamMpi
-    from bipymc_amd.utils import d100_gauss
-    t = d100_gauss.Gauss_100D(rho=0.5, dim=d)
-    s = DreamMpi(t.ln_like, np.zeros(d), n_chains=N, n_cr_gen=10, burnin_gen=50, seed=21)
-    s.run_mcmc(N * (gens + 1), shuffle=shuffle)
-    return s
 
 
 def test_dream_shuffled_history_partial_generation():
@@ -189,37 +172,13 @@ def test_errors_say_what_is_wrong():
 
 
 def _group_quantiles(R):
-    """R ranks as handles of this process over the push exchange (the test variant's local group), stepped as tests/_push_worker.py does"""
-    from bipymc_amd import _lib as L
     from bipymc_amd import quantiles as Q
-    from bipymc_amd.engine import HipEngine
-    from _push_worker import case_spec, start_state
-    spec, algo, N, kw, G = case_spec("dream_gauss100_long")
-    tid, tp, d = spec
-    uid = b"BPMLOCAL" + bytes(120)
-    ranks = [HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, rank=r, world_size=R, nccl_uid=uid,
-                       lib=L.load_test(), **kw) for r in range(R)]
-    blobs = [e.push_export() for e in ranks]
-    for e in ranks:
-        e.push_connect(blobs)
-    arr = (C.c_void_p * R)(*[e._h for e in ranks])
-    ok = C.c_int32(0)
-    L.check(ranks[0].lib.bpm_push_selftest(arr, R, C.byref(ok)), ranks[0].lib)
-    assert ok.value == 1
-    x0 = start_state("dream_gauss100_long", N, d)
-    for e in ranks:
-        e.set_state(x0)
-        e.begin_run(flip=0.4)
-    L.check(ranks[0].lib.bpm_local_group_step(arr, R, G), ranks[0].lib)
+    ranks, N, d = local_group(R)
     n_burn = N * 7 + N // 2 + 1                 # a partial generation that starts inside a later rank's chains
-    res = Q.compute(lambda nb: [e.quantile_begin(nb) for e in ranks], lambda a, b, c: [e.quantile_histogram(a, b, c) for e in ranks],
-                    lambda x: x, n_burn, QS, dim=d)
+    res = Q.compute(per_rank(ranks, "quantile_begin"), per_rank(ranks, "quantile_histogram"), lambda x: x, n_burn, QS, dim=d)
     for e in ranks:
         e.close()
-    one = HipEngine(algo=algo, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=11, **kw)
-    one.set_state(x0)
-    one.begin_run(flip=0.4)
-    one.step(G)
+    one = group_single_rank()
     ref = _device(one, n_burn)
     H = one.get_history()
     one.close()
@@ -234,22 +193,8 @@ def test_local_group_equals_single_rank(R):
 
 
 def test_rank_processes_sharing_the_gpu(tmp_path):
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env["BPM_PUSH_TIMEOUT_S"] = "60"
-    worker = os.path.join(HERE, "_quantile_worker.py")
-    subprocess.check_call([sys.executable, worker, str(tmp_path), "0", "1"], env=env, timeout=300)
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path), str(r), "2"], env=env) for r in range(2)]
-    for p in procs:
-        try:
-            assert p.wait(timeout=300) == 0
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    one = np.load(os.path.join(str(tmp_path), "qs_w1_rank0.npz"))
-    r = [np.load(os.path.join(str(tmp_path), "qs_w2_rank%d.npz" % k)) for k in range(2)]
-    from _quantile_worker import Q
+    one, r = run_rank_processes(tmp_path, "quantiles")
+    from _stats_worker import Q
     _same(one["q"], np.quantile(one["chain_slice"], Q, axis=0))
     assert np.array_equal(r[0]["q"].view(np.uint64), r[1]["q"].view(np.uint64))
     _same(r[0]["q"], one["q"])

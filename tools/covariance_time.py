@@ -15,22 +15,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _history_bench import PEAK_BW, Report, cfg2_engine, median_time, quantile_pass0_time  # noqa: E402
 from bipymc_amd import _lib as L                      # noqa: E402
 from bipymc_amd import covariance as CV               # noqa: E402
-from bipymc_amd.engine import HipEngine               # noqa: E402
-from bipymc_amd.utils import d100_gauss               # noqa: E402
 
-PEAK_BW = 8.0e12          # HBM3E spec (MI355X_MICROARCH.md)
-
-
-def median_time(fn, reps=5):
-    ts = []
-    out = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
 
 
 def main():
@@ -39,26 +27,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    N = 8192
-    t = d100_gauss.Gauss_100D()
-    tid, tp, d = t._bpm_target_spec()
-    e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=1, burnin_gen=100, n_cr_gen=20)
-    e.set_state(np.random.RandomState(0).normal(size=(N, d)) * np.sqrt(np.arange(d) + 1.0))
-    e.reserve_history(a.G + 1)
-    e.begin_run()
-    e.step(a.G)
-    e.synchronize()
-    rows = e.history_rows()
-    ld = d + (d & 1)
-    n_burn = N                                     # the initial state left out
-    n = rows * N - n_burn
-    win_bytes = n * ld * 8
+    report = Report()
+    say = report.say
+    e = cfg2_engine(a.G)
+    N, d, rows, ld = e.N, e.d, e.rows, e.ld
+    n_burn, n, win_bytes, t = e.n_burn, e.n, e.win_bytes, e.target
     tiles = (d + 15) // 16
     flop = (n + 3) // 4 * (tiles * (tiles + 1) // 2) * 2048.0      # what the matrix cores execute: 16x16x4 per tile pair and 4 rows
     say("# posterior covariance at cfg2's shape: N = %d chains, d = %d, %d history rows (%.2f GB resident), window %d rows x %d; "
@@ -70,10 +43,7 @@ def main():
     pc = run()                                     # warm-up
     center = pc.mean
     t_mom, _ = median_time(lambda: e.reduce_moments(n_burn))
-    e.quantile_begin(n_burn)
-    pk, pv = np.arange(d, dtype=np.int32), np.zeros(d, dtype=np.uint64)
-    e.quantile_histogram(pk, pv, 0)
-    t_q0, _ = median_time(lambda: e.quantile_histogram(pk, pv, 0))
+    t_q0 = quantile_pass0_time(e, n_burn, d)
     t_cov, _ = median_time(lambda: e.reduce_cov(n_burn, center))
     t_call, pc = median_time(run)
     say("single full-window passes of this build, host-to-host: bpm_reduce_moments %.3f ms (%.2f TB/s); pass 0 of the quantile select "
@@ -111,9 +81,7 @@ def main():
         say("within 2 (n + 4) u sqrt(C_ii C_jj) of np.cov element by element: %s (largest error / bound %.2e); exactly symmetric: %s"
             % (bool(np.all(np.abs(pc.cov - want) <= bound)), float(np.max(np.abs(pc.cov - want) / bound)), bool(np.array_equal(pc.cov, pc.cov.T))))
     e.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

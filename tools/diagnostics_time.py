@@ -11,23 +11,11 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _history_bench import PEAK_BW, Report, cfg2_engine, median_time  # noqa: E402
 from bipymc_amd import _lib as L                      # noqa: E402
 from bipymc_amd import diagnostics as D               # noqa: E402
-from bipymc_amd.engine import HipEngine               # noqa: E402
-from bipymc_amd.utils import d100_gauss               # noqa: E402
 
-PEAK_BW = 8.0e12          # HBM3E spec (MI355X_MICROARCH.md)
 PEAK_FP64 = 78.6e12       # FP64 vector spec of the MI355X (FMA = 2 FLOP)
-
-
-def median_time(fn, reps=5):
-    ts = []
-    out = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
 
 
 def numpy_diagnostics(H, max_lag):
@@ -57,23 +45,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    N = 8192
-    t = d100_gauss.Gauss_100D()
-    tid, tp, d = t._bpm_target_spec()
-    e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=1, burnin_gen=100, n_cr_gen=20)
-    e.set_state(np.random.RandomState(0).normal(size=(N, d)) * np.sqrt(np.arange(d) + 1.0))
-    e.reserve_history(a.G + 1)
-    e.begin_run()
-    e.step(a.G)
-    e.synchronize()
-    rows = e.history_rows()
-    ld = d + (d & 1)
+    report = Report()
+    say = report.say
+    e = cfg2_engine(a.G)
+    N, d, rows, ld = e.N, e.d, e.rows, e.ld
     say("# convergence diagnostics at cfg2's shape: N = %d chains, d = %d, %d history rows (%.2f GB resident); build %s"
         % (N, d, rows, rows * N * ld * 8 / 1e9, L.build_id(e.lib)))
     # warm-up of every kernel
@@ -106,9 +81,7 @@ def main():
         say("agreement with NumPy: max rel diff r_hat %.2e, ESS %.2e"
             % (np.max(np.abs(res.r_hat / r_np - 1)), np.max(np.abs(res.ess / ess_np - 1))))
     e.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

@@ -14,22 +14,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _history_bench import PEAK_BW, Report, cfg2_engine, median_time, quantile_pass0_time  # noqa: E402
 from bipymc_amd import _lib as L                      # noqa: E402
 from bipymc_amd import histograms as HS               # noqa: E402
-from bipymc_amd.engine import HipEngine               # noqa: E402
-from bipymc_amd.utils import d100_gauss               # noqa: E402
 
-PEAK_BW = 8.0e12          # HBM3E spec (MI355X_MICROARCH.md)
-
-
-def median_time(fn, reps=5):
-    ts = []
-    out = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
 
 
 def main():
@@ -38,26 +26,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    N = 8192
-    t = d100_gauss.Gauss_100D()
-    tid, tp, d = t._bpm_target_spec()
-    e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=1, burnin_gen=100, n_cr_gen=20)
-    e.set_state(np.random.RandomState(0).normal(size=(N, d)) * np.sqrt(np.arange(d) + 1.0))
-    e.reserve_history(a.G + 1)
-    e.begin_run()
-    e.step(a.G)
-    e.synchronize()
-    rows = e.history_rows()
-    ld = d + (d & 1)
-    n_burn = N                                     # the initial state left out
-    n = rows * N - n_burn
-    win_bytes = n * ld * 8
+    report = Report()
+    say = report.say
+    e = cfg2_engine(a.G)
+    N, d, rows, ld = e.N, e.d, e.rows, e.ld
+    n_burn, n, win_bytes = e.n_burn, e.n, e.win_bytes
     pair_dims = list(range(8))
     say("# posterior histograms at cfg2's shape: N = %d chains, d = %d, %d history rows (%.2f GB resident), window %d rows x %d; "
         "build %s" % (N, d, rows, rows * N * ld * 8 / 1e9, n, d, L.build_id(e.lib)))
@@ -70,10 +43,7 @@ def main():
 
     ph = run()                                     # warm-up
     pp = run_pairs()
-    e.quantile_begin(n_burn)
-    pk, pv = np.arange(d, dtype=np.int32), np.zeros(d, dtype=np.uint64)
-    e.quantile_histogram(pk, pv, 0)
-    t_q0, _ = median_time(lambda: e.quantile_histogram(pk, pv, 0))
+    t_q0 = quantile_pass0_time(e, n_burn, d)
     t_rng, _ = median_time(lambda: e.hist_range(n_burn))
     t_mar, _ = median_time(lambda: e.hist_marginals(ph.dims, ph.edges))
     pos = {int(k): j for j, k in enumerate(pp.dims)}
@@ -110,9 +80,7 @@ def main():
         say("counts equal to np.histogram: %s; to np.histogram2d: %s; every marginal row sums to n: %s"
             % (ok1, ok2, bool(np.all(ph.counts.sum(axis=1) == ph.n))))
     e.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

@@ -11,22 +11,10 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _history_bench import PEAK_BW, Report, cfg2_engine, median_time  # noqa: E402
 from bipymc_amd import _lib as L                      # noqa: E402
 from bipymc_amd import quantiles as Q                 # noqa: E402
-from bipymc_amd.engine import HipEngine               # noqa: E402
-from bipymc_amd.utils import d100_gauss               # noqa: E402
 
-PEAK_BW = 8.0e12          # HBM3E spec (MI355X_MICROARCH.md)
-
-
-def median_time(fn, reps=5):
-    ts = []
-    out = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
 
 
 def main():
@@ -37,25 +25,11 @@ def main():
     ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
     q = [float(x) for x in a.q.split(",")]
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    N = 8192
-    t = d100_gauss.Gauss_100D()
-    tid, tp, d = t._bpm_target_spec()
-    e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=1, burnin_gen=100, n_cr_gen=20)
-    e.set_state(np.random.RandomState(0).normal(size=(N, d)) * np.sqrt(np.arange(d) + 1.0))
-    e.reserve_history(a.G + 1)
-    e.begin_run()
-    e.step(a.G)
-    e.synchronize()
-    rows = e.history_rows()
-    ld = d + (d & 1)
-    n_burn = N                                     # the initial state left out
-    win_bytes = (rows * N - n_burn) * ld * 8
+    report = Report()
+    say = report.say
+    e = cfg2_engine(a.G)
+    N, d, rows, ld = e.N, e.d, e.rows, e.ld
+    n_burn, win_bytes = e.n_burn, e.win_bytes
     say("# posterior quantiles at cfg2's shape: N = %d chains, d = %d, %d history rows (%.2f GB resident), window %d rows x %d, q = %s; "
         "build %s" % (N, d, rows, rows * N * ld * 8 / 1e9, rows * N - n_burn, d, a.q, L.build_id(e.lib)))
 
@@ -93,9 +67,7 @@ def main():
             % (t_copy, H.nbytes / 1e9, t_np, t_copy + t_np, (t_copy + t_np) / t_call))
         say("equal to np.quantile value for value: %s" % bool(np.array_equal(res, want, equal_nan=True)))
     e.close()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":
