@@ -12,3 +12,4 @@ from .dream import DreamMpi  # noqa: F401
 from .device_likelihood import HipLikelihood  # noqa: F401
 from .covariance import PosteriorCovariance  # noqa: F401
 from .histograms import PosteriorHistograms  # noqa: F401
+from .traces import PosteriorTrace  # noqa: F401

@@ -1,5 +1,6 @@
-"""The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance and
-histograms (bipymc_amd/diagnostics.py, quantiles.py, covariance.py, histograms.py), each reduced where the history lives.
+"""The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance,
+histograms and per-generation traces (bipymc_amd/diagnostics.py, quantiles.py, covariance.py, histograms.py, traces.py), each reduced where
+the history lives.
 
 The contract they share.  The window is the super-chain rows >= n_burn, param_est's selection (row g * n_chains + i = chain i at generation
 g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
@@ -54,3 +55,13 @@ class HistoryStatistics(object):
         eng = self._stats_engine("param_est_hist")
         return _hs.compute(eng.hist_range, eng.hist_marginals, eng.hist_pairs, self._stats_allgather, n_burn, eng.dim, bins=bins,
                            range=range, dims=dims, pairs=pairs, bins2d=bins2d)
+
+    def param_est_trace(self, n_burn=0, every=1, chains=None):
+        """What a trace plot shows, per bin of `every` generations from the first whole generation at or after n_burn: mean, sd (np.mean /
+        np.std of the bin's rows), min, max and NaN count per coordinate, mean / min / max of the log-likelihood, the best sample of the
+        window, and the global chains `chains` (None: none) at the first generation of every bin -- the picture the reference draws from
+        param_est(n_burn=0)'s copy of the history.  -> traces.PosteriorTrace with .band(k)"""
+        from . import traces as _tr
+        eng = self._stats_engine("param_est_trace")
+        return _tr.compute(eng.trace_bins, eng.trace_chains, self._stats_allgather, n_burn, self.n_chains, eng.history_rows(), eng.dim,
+                           every=every, chains=chains)

@@ -109,6 +109,8 @@ SIGNATURES = {
     "bpm_hist_range": (C.c_int, [_H, C.c_int64, _dp, _dp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "bpm_hist_marginals": (C.c_int, [_H, C.c_int32, _P(C.c_int32), C.c_int32, _dp, _P(C.c_int64)]),
     "bpm_hist_pairs": (C.c_int, [_H, C.c_int32, _P(C.c_int32), C.c_int32, _dp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
+    "bpm_trace_bins": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _dp, _dp, _P(C.c_int64), _dp]),
+    "bpm_trace_chains": (C.c_int, [_H, C.c_int32, _P(C.c_int32), _dp, _dp]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only
@@ -149,7 +151,7 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

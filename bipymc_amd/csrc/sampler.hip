@@ -37,6 +37,7 @@
 #include "quantiles.h"
 #include "covariance.h"
 #include "histograms.h"
+#include "traces.h"
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -381,7 +382,8 @@ static EvalLaunch g_eval_gauss[7] = SHAPE_TABLE(launch_eval, launch_eval_wide<TA
 static EvalLaunch g_eval_mixture[7] = SHAPE_TABLE(launch_eval, launch_eval_wide<TARGET_MIXTURE>, TARGET_MIXTURE COMMA);
 
 // "The history is still what the first call of a pair saw" (bpm_diag_split_moments -> bpm_diag_autocov, bpm_quantile_begin ->
-// bpm_quantile_histogram, bpm_hist_range -> bpm_hist_marginals / bpm_hist_pairs): the first call take()s, the ones that follow check().
+// bpm_quantile_histogram, bpm_hist_range -> bpm_hist_marginals / bpm_hist_pairs, bpm_trace_bins -> bpm_trace_chains): the first call take()s,
+// the ones that follow check().
 struct bpm_sampler;
 struct HistorySnapshot {
     bool valid = false;
@@ -611,6 +613,10 @@ struct bpm_sampler {
     // call saw (hs_seen); every device buffer of these calls is temporary
     HistorySnapshot hs_seen;
     uint64_t hs_lo = 0, hs_hi = 0;
+    // trace summaries (traces.h, bpm_trace_*): the generations [tr_g0, tr_g1) and the bin width of the last bpm_trace_bins, valid while the
+    // history is what that call saw (tr_seen); every device buffer of these calls is temporary
+    HistorySnapshot tr_seen;
+    int64_t tr_g0 = 0, tr_g1 = 0, tr_every = 1;
     double* om = nullptr;        // outlier check: world x [omega (n_local) | ln_like (n_local)], all-gathered in place
     double* sel = nullptr;       // outlier check: [0..3] order statistics around Q1 / Q3, [4] first argmax of omega
     unsigned char* sel_state = nullptr;   // radix-select state between the passes (SelState)
@@ -819,7 +825,7 @@ static int normalize_history(bpm_sampler* s, int64_t r0, int64_t r1) {
     return 0;
 }
 
-// ---- shared by the statistics of the history (bpm_reduce_moments ... bpm_hist_pairs) ---------------------------------------------------
+// ---- shared by the statistics of the history (bpm_reduce_moments ... bpm_trace_chains) -------------------------------------------------
 static int require_resident_history(const bpm_sampler* s, const char* who) {
     if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
         return fail(std::string(who) + ": needs keep_history=True (a resident history of every generation)");
@@ -3455,6 +3461,137 @@ extern "C" int bpm_hist_pairs(bpm_handle_t s, int32_t n_dims, const int32_t* dim
                        reinterpret_cast<const double*>(b.p + o_e), nu_max, np_max, reinterpret_cast<unsigned long long*>(b.p));
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(counts2d, b.p, o_e, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+// ---- per-generation trace summaries (traces.h; bipymc_amd/traces.py merges the ranks and finishes mean and sd) --------------------------
+// What the reference's trace plots show (plot_mcmc_indep_chains / plot_mcmc_chain, mc_plot/mc_plot.py:52-102: every chain against the
+// generation, np.mean and np.std per generation), taken where the history lives instead of from param_est(n_burn=0)'s copy of it.
+
+// workgroups per bin along its rows.  Many short bins need none beyond the first; few long bins (every large) are cut so that the grid
+// still fills the chip: rows_grid's rule with the (tile, bin) pairs in the place of its tiles -- about 2048 workgroups in all, each at
+// least 4 sweeps of `rows_per_sweep` rows, none with 2^31 rows or more
+static int trace_parts(uint64_t rows_per_bin, uint64_t tiles_x_bins, uint64_t rows_per_sweep, uint64_t* parts) {
+    return rows_grid(rows_per_bin, tiles_x_bins, rows_per_sweep, "bpm_trace_bins", parts);
+}
+
+// Bins t = 0 .. T - 1, T = ceil((g_hi - g_lo) / every), of the generations [g_lo + t every, min(g_lo + (t + 1) every, g_hi)) over this
+// rank's chains.  bin_counts: [2][T][dim] = how many values are finite | NaN; bin_sums: [5][T][dim] = shift c | sum (x - c) | sum (x - c)^2
+// over the finite values | min | max over the values that are not NaN (+inf / -inf where there is none).  ll_counts: [4][T] = finite | NaN |
+// +inf | -inf; ll_sums: [5][T] likewise for the ln-likes.  best_ll / best_row / best_x: the largest ln-like of the window that is not NaN,
+// the smallest local row g * n_local + i that carries it and its dim coordinates (NaN, -1, NaN where every ln-like is NaN).
+extern "C" int bpm_trace_bins(bpm_handle_t s, int64_t g_lo, int64_t g_hi, int64_t every, int64_t* bin_counts, double* bin_sums, int64_t* ll_counts,
+                              double* ll_sums, double* best_ll, int64_t* best_row, double* best_x) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    s->tr_seen.valid = false;
+    if (!bin_counts || !bin_sums || !ll_counts || !ll_sums || !best_ll || !best_row || !best_x) return fail("bpm_trace_bins: null argument");
+    CK(require_resident_history(s, "bpm_trace_bins"));
+    if (g_lo < 0 || g_hi < g_lo || g_hi > s->hist_rows) return fail("bpm_trace_bins: generation range out of bounds");
+    if (every < 1) return fail("bpm_trace_bins: every must be >= 1 (got " + std::to_string((long long)every) + ")");
+    CK(normalize_history(s, g_lo, g_hi));
+    s->tr_g0 = g_lo; s->tr_g1 = g_hi; s->tr_every = every;
+    s->tr_seen.take(s);
+    const uint32_t ld = s->ld, dim = s->dim;
+    *best_ll = std::nan("");
+    *best_row = -1;
+    std::fill(best_x, best_x + dim, std::nan(""));
+    const uint64_t span = (uint64_t)(g_hi - g_lo);
+    if (span == 0) return 0;
+    const uint64_t ev = std::min<uint64_t>((uint64_t)every, span);      // (a bin wider than the window is the window)
+    const uint64_t T = (span + ev - 1) / ev, rows_per_bin = ev * s->n_local;
+    const uint32_t kw = std::min<uint32_t>(ld, TR_THREADS), n_tiles = (ld + kw - 1) / kw, cpw = TR_THREADS / kw;
+    if (T * n_tiles >= (1ull << 31)) return fail("bpm_trace_bins: too many bins");
+    uint64_t pb = 1, pl = 1;
+    CK(trace_parts(rows_per_bin, T * n_tiles, (uint64_t)cpw * TR_UNR, &pb));
+    CK(trace_parts(rows_per_bin, T, (uint64_t)TR_THREADS * TR_UNR, &pl));
+    // [bins: part records | folded records][ln-likes: part records | folded records]; with one part the part records are the folded ones
+    const uint64_t nb_out = T * ld, nb_rec = nb_out * pb, nl_out = T, nl_rec = T * pl;
+    const size_t o_bf = (size_t)TR_F_BINS * nb_rec, o_lp = o_bf + (pb > 1 ? (size_t)TR_F_BINS * nb_out : 0);
+    const size_t o_lf = o_lp + (size_t)TR_F_LL * nl_rec, need = o_lf + (pl > 1 ? (size_t)TR_F_LL * nl_out : 0);
+    DevTemp<double> b;
+    CK(b.alloc(need, "bpm_trace_bins", "the per-bin records of " + std::to_string((unsigned long long)T) + " bins"));
+    double* bins_rec = b.p;
+    double* ll_rec = b.p + o_lp;
+    hipLaunchKernelGGL(tr_bins_kernel, dim3((unsigned)(T * n_tiles), (unsigned)pb), dim3(TR_THREADS), 0, s->stream, (const double*)s->hist, ld,
+                       s->n_local, (uint64_t)g_lo, (uint64_t)g_hi, ev, kw, n_tiles, bins_rec, nb_rec);
+    hipLaunchKernelGGL(tr_ll_kernel, dim3((unsigned)T, (unsigned)pl), dim3(TR_THREADS), 0, s->stream, (const double*)s->llhist, s->n_local,
+                       (uint64_t)g_lo, (uint64_t)g_hi, ev, ll_rec, nl_rec);
+    if (pb > 1) {
+        hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((nb_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream,
+                           (const double*)bins_rec, (uint32_t)pb, ld, nb_out, (uint32_t)TR_F_BINS, b.p + o_bf);
+        bins_rec = b.p + o_bf;
+    }
+    if (pl > 1) {
+        hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((nl_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream,
+                           (const double*)ll_rec, (uint32_t)pl, 1u, nl_out, (uint32_t)TR_F_LL, b.p + o_lf);
+        ll_rec = b.p + o_lf;
+    }
+    HIPCK(hipGetLastError());
+    std::vector<double> hb((size_t)TR_F_BINS * nb_out), hl((size_t)TR_F_LL * nl_out);
+    HIPCK(hipMemcpyAsync(hb.data(), bins_rec, hb.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(hl.data(), ll_rec, hl.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    auto word = [](const std::vector<double>& h, size_t i) {
+        int64_t w;
+        std::memcpy(&w, &h[i], 8);
+        return w;
+    };
+    const int count_f[2] = {TR_N, TR_NAN}, sum_f[5] = {TR_C, TR_S1, TR_S2, TR_MIN, TR_MAX}, ll_count_f[4] = {TR_N, TR_NAN, TR_PINF, TR_NINF};
+    const size_t td = (size_t)T * dim;
+    for (uint64_t t = 0; t < T; ++t)
+        for (uint32_t k = 0; k < dim; ++k) {
+            const size_t src = (size_t)t * ld + k, dst = (size_t)t * dim + k;
+            for (int f = 0; f < 2; ++f) bin_counts[f * td + dst] = word(hb, (size_t)count_f[f] * nb_out + src);
+            for (int f = 0; f < 5; ++f) bin_sums[f * td + dst] = hb[(size_t)sum_f[f] * nb_out + src];
+        }
+    uint64_t bkey = 0, brow = TR_NO_ROW;
+    for (uint64_t t = 0; t < T; ++t) {
+        for (int f = 0; f < 4; ++f) ll_counts[f * T + t] = word(hl, (size_t)ll_count_f[f] * nl_out + t);
+        for (int f = 0; f < 5; ++f) ll_sums[f * T + t] = hl[(size_t)sum_f[f] * nl_out + t];
+        const uint64_t kb = (uint64_t)word(hl, (size_t)TR_BKEY * nl_out + t), rb = (uint64_t)word(hl, (size_t)TR_BROW * nl_out + t);
+        if (kb > bkey || (kb == bkey && rb < brow)) { bkey = kb; brow = rb; }      // bins in order: the larger key, then the smaller row
+    }
+    if (brow != TR_NO_ROW) {
+        if (brow >= (uint64_t)s->hist_rows * s->n_local) return fail("bpm_trace_bins: internal error (arg-max row out of range)");
+        HIPCK(hipMemcpyAsync(best_ll, s->llhist + brow, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipMemcpyAsync(best_x, s->hist + brow * ld, dim * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        *best_row = (int64_t)brow;
+    }
+    return 0;
+}
+
+// The local chains local_ids[0 .. n) at the first generation of every bin of the last bpm_trace_bins, T bins:
+// out_x[(t * n + j) * dim + k] and out_ll[t * n + j] = chain local_ids[j] at generation g_lo + t * every.
+extern "C" int bpm_trace_chains(bpm_handle_t s, int32_t n, const int32_t* local_ids, double* out_x, double* out_ll) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!local_ids || !out_x || !out_ll) return fail("bpm_trace_chains: null argument");
+    CK(s->tr_seen.check(s, "bpm_trace_chains", "bpm_trace_bins"));
+    if (n < 1 || (uint32_t)n > s->n_local) return fail("bpm_trace_chains: n must be 1 ... n_local");
+    for (int32_t j = 0; j < n; ++j)
+        if (local_ids[j] < 0 || (uint32_t)local_ids[j] >= s->n_local)
+            return fail("bpm_trace_chains: local chain " + std::to_string(local_ids[j]) + " is outside [0, " + std::to_string(s->n_local) + ")");
+    const uint64_t span = (uint64_t)(s->tr_g1 - s->tr_g0);
+    if (span == 0) return 0;
+    const uint64_t ev = std::min<uint64_t>((uint64_t)s->tr_every, span), T = (span + ev - 1) / ev;
+    const uint64_t n_x = T * (uint64_t)n * s->dim, n_ll = T * (uint64_t)n, n_el = n_x + n_ll;
+    if ((n_el + TR_THREADS - 1) / TR_THREADS >= (1ull << 31)) return fail("bpm_trace_chains: too many bins x chains");
+    // [out_x | out_ll | ids u32]
+    DevTemp<double> b;
+    CK(b.alloc((size_t)n_el + ((size_t)n + 1) / 2, "bpm_trace_chains", "the gathered chains"));
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(b.p + n_el);
+    std::vector<unsigned char> ids((size_t)n * 4);
+    stage_dims(ids.data(), local_ids, (size_t)n);
+    HIPCK(hipMemcpyAsync(d_ids, ids.data(), ids.size(), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(tr_gather_kernel, dim3((unsigned)((n_el + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream, (const double*)s->hist,
+                       (const double*)s->llhist, s->ld, s->dim, s->n_local, (uint64_t)s->tr_g0, ev, T, (uint32_t)n, (const uint32_t*)d_ids, b.p,
+                       b.p + n_x);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(out_x, b.p, (size_t)n_x * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(out_ll, b.p + n_x, (size_t)n_ll * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }

@@ -487,6 +487,40 @@ class HipEngine(object):
                                          pb.ctypes.data_as(i32), out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
+    def trace_bins(self, g_lo, g_hi, every):
+        """-> (counts (2, T, dim) int64, sums (5, T, dim), ll_counts (4, T) int64, ll_sums (5, T), best_ll, best_row, best_x (dim,)): per bin of
+        `every` history rows of [g_lo, g_hi) over this rank's chains, how many values are finite | NaN, and a shift | the shifted sum | the
+        shifted sum of squares of the finite ones | min | max; the same over the ln-likes (counts: finite | NaN | +inf | -inf); the rank's
+        largest ln-like, its row of the super chain g * n_chains + i (-1: none that is not NaN) and that row.  Fixes the bins of the
+        trace_chains calls that follow (bpm_trace_bins; bipymc_amd/traces.py merges the ranks)"""
+        g_lo, g_hi, every = int(g_lo), int(g_hi), int(every)
+        span = max(0, g_hi - g_lo)
+        T = -(-span // min(max(every, 1), max(span, 1)))         # (a bin wider than the range is the range)
+        counts = np.zeros((2, T, self.dim), dtype=np.int64); sums = np.zeros((5, T, self.dim))
+        ll_counts = np.zeros((4, T), dtype=np.int64); ll_sums = np.zeros((5, T))
+        best_ll = C.c_double(0.0); best_row = C.c_int64(-1); best_x = np.empty(self.dim)
+        i64 = C.POINTER(C.c_int64)
+        self._ck(self.lib.bpm_trace_bins(self._h, g_lo, g_hi, every, counts.ctypes.data_as(i64), _dptr(sums), ll_counts.ctypes.data_as(i64),
+                                         _dptr(ll_sums), C.byref(best_ll), C.byref(best_row), _dptr(best_x)))
+        self._trace_T = T
+        row = int(best_row.value)
+        if row >= 0:
+            row = (row // self.n_local) * self.n_chains + self.lo + row % self.n_local
+        return counts, sums, ll_counts, ll_sums, float(best_ll.value), row, best_x
+
+    def trace_chains(self, chains):
+        """-> (pos (c,), x (T, c, dim), ll (T, c)): those of the global chains `chains` this rank holds (pos: their positions in `chains`) at
+        the first history row of every bin of the last trace_bins call (bpm_trace_chains)"""
+        ch = np.asarray(chains, dtype=np.int64).reshape(-1)
+        pos = np.nonzero((ch >= self.lo) & (ch < self.lo + self.n_local))[0]
+        if len(pos) == 0:
+            return pos, np.empty((0, 0, self.dim)), np.empty((0, 0))
+        ids = np.ascontiguousarray(ch[pos] - self.lo, dtype=np.int32)
+        T = getattr(self, "_trace_T", 0)
+        x = np.empty((T, len(ids), self.dim)); ll = np.empty((T, len(ids)))
+        self._ck(self.lib.bpm_trace_chains(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(x), _dptr(ll)))
+        return pos, x, ll
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

@@ -346,6 +346,26 @@ int bpm_hist_range(bpm_handle_t h, int64_t n_burn, double* lo, double* hi, int64
 int bpm_hist_marginals(bpm_handle_t h, int32_t n_dims, const int32_t* dims, int32_t bins, const double* edges, int64_t* counts);
 int bpm_hist_pairs(bpm_handle_t h, int32_t n_dims, const int32_t* dims, int32_t bins2d, const double* edges2d, int64_t n_pairs,
                    const int32_t* pair_a, const int32_t* pair_b, int64_t* counts2d);
+/* Per-generation trace summaries of the resident history on the device: what the reference's trace plots draw from the gathered chains
+ * (plot_mcmc_indep_chains / plot_mcmc_chain, mc_plot/mc_plot.py:52-102: one line per chain, np.mean and np.std per generation; the reason
+ * its examples call param_est(n_burn=0) a second time), without moving the history.
+ * bpm_trace_bins: bins t = 0 .. T - 1, T = ceil((g_hi - g_lo) / every), of the history rows [g_lo + t every, min(g_lo + (t + 1) every, g_hi))
+ * pooled over this rank's chains (every larger than the range: one bin).  Per bin and coordinate, bin_counts = [2][T][dim]: how many values
+ * are finite | NaN; bin_sums = [5][T][dim]: a shift c (a finite value of the bin: the rank's first row of it where that is finite) | sum (x - c)
+ * | sum (x - c)^2 over the finite values | min | max over the values that are not NaN (+inf / -inf where there is none; infinite values show
+ * here only).  The same over the ln-like history, ll_counts = [4][T]: finite | NaN | +inf | -inf, ll_sums = [5][T].  best_ll / best_row /
+ * best_x (dim values): the largest ln-like of the range that is not NaN, the smallest local row g * n_local + i that carries it, and that
+ * row's state (NaN, -1, NaN where every ln-like is NaN).  One pass over the range; every partial result is merged in a fixed order and
+ * there is no floating-point atomic, so the same history gives the same bits.  bipymc_amd/traces.py merges the ranks (mean = c + S1 / n,
+ * M2 = S2 - S1^2 / n, Chan's formula) and finishes mean and sd.
+ * bpm_trace_chains: the local chains local_ids[0 .. n) at the first history row of every bin of the last bpm_trace_bins:
+ * out_x[(t * n + j) * dim + k], out_ll[t * n + j].  An error once the history changed since bpm_trace_bins (a step, bpm_set_history or
+ * bpm_set_state).  Every device buffer is temporary; nothing the samplers read is written (a history kept in position order is put into
+ * chain order first, as bpm_get_history does).  Errors: no resident history (keep_history = 0), a range outside the history, every < 1,
+ * a chain outside [0, n_local), records larger than the free device memory (the message names the requirement). */
+int bpm_trace_bins(bpm_handle_t h, int64_t g_lo, int64_t g_hi, int64_t every, int64_t* bin_counts, double* bin_sums, int64_t* ll_counts,
+                   double* ll_sums, double* best_ll, int64_t* best_row, double* best_x);
+int bpm_trace_chains(bpm_handle_t h, int32_t n, const int32_t* local_ids, double* out_x, double* out_ll);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
