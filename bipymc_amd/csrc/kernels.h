@@ -296,6 +296,30 @@ __device__ __forceinline__ double gsum(double v) {
     if (LPC == 64) v = (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
     return v;
 }
+// Two sums at once, step by step: the same tree and order for each as gsum (same bits); a DPP step has to wait for the addition before it,
+// and the other sum's step fills that wait.
+template <int LPC>
+__device__ __forceinline__ void gsum2(double& v, double& w) {
+    static_assert(LPC == 1 || LPC == 4 || LPC == 16 || LPC == 32 || LPC == 64, "subgroup sizes");
+    if (LPC >= 4) {
+        const double v1 = dpp_f64<0xB1>(v), w1 = dpp_f64<0xB1>(w);
+        v += v1; w += w1;
+        const double v2 = dpp_f64<0x4E>(v), w2 = dpp_f64<0x4E>(w);
+        v += v2; w += w2;
+    }
+    if (LPC >= 16) {
+        const double v3 = dpp_f64<0x141>(v), w3 = dpp_f64<0x141>(w);
+        v += v3; w += w3;
+        const double v4 = dpp_f64<0x140>(v), w4 = dpp_f64<0x140>(w);
+        v += v4; w += w4;
+    }
+    if (LPC == 32) { const double vs = __shfl_xor(v, 16), ws = __shfl_xor(w, 16); v += vs; w += ws; }
+    if (LPC == 64) {
+        const double va = readlane_f64(v, 0) + readlane_f64(v, 16), wa = readlane_f64(w, 0) + readlane_f64(w, 16);
+        const double vb = readlane_f64(v, 32) + readlane_f64(v, 48), wb = readlane_f64(w, 32) + readlane_f64(w, 48);
+        v = va + vb; w = wa + wb;
+    }
+}
 template <int LPC>
 __device__ __forceinline__ int gsum_i(int v) {
     if (LPC >= 4) {
@@ -470,8 +494,7 @@ struct Target<TARGET_GAUSS, LPC, DPL> {
                 s2 += z * z;
             }
         }
-        s1 = gsum<LPC>(s1);
-        s2 = gsum<LPC>(s2);
+        gsum2<LPC>(s1, s2);
         return k.c0 - 0.5 * (k.a * s2 - k.b * s1 * s1);
     }
 };
@@ -545,7 +568,7 @@ struct Work {
     double delta;      // CR statistic (dream.py:130)
     double log_corr;   // snooker Jacobian term
     double gamma;
-    uint32_t acc_hi, acc_lo;   // words of the accept uniform
+    double u_acc;              // the accept uniform (u01_53 of the header block's words z, w): made where the header arrives, not behind the rows
     uint32_t item;             // work-item number of this update (index of its accept byte when acc_by_item)
     uint32_t pos_own;          // its position in this generation's shuffle order (mode 0)
     double ll_cur;             // cached ln_like of the current state, fetched early
@@ -556,6 +579,22 @@ struct Work {
 };
 
 typedef double bpm_d2v __attribute__((ext_vector_type(2)));
+// A row load that EVERY lane issues (pair index clamped to the row's last pair), for rows whose values in the lanes beyond the row never reach a
+// result (DREAM's partner rows: those lanes hold no coordinate, their mask bits are never set).  load_row's `if (2 pi < ld)` is a branch around
+// each load; a wait for anything requested BEFORE such loads must then assume the path that skipped them all, i.e. it becomes vmcnt(0): the gamma
+// table lookup of one wavefront per chain -- values requested at kernel entry -- sat out the arrival of all six partner rows, and with it the
+// gamma / jump selects and everything the scheduler had placed behind them.
+template <int LPC, int DPL>
+__device__ __forceinline__ void load_row_all(const double* row, int q, uint32_t ld, double* v) {
+    const uint32_t last = (ld >> 1) - 1u;      // (ld is even and >= 2)
+#pragma unroll
+    for (int u = 0; u < DPL / 2; ++u) {
+        const uint32_t pi = (uint32_t)(q + u * LPC);
+        const double2 t = reinterpret_cast<const double2*>(row)[pi < last ? pi : last];
+        v[2 * u] = t.x;
+        v[2 * u + 1] = t.y;
+    }
+}
 template <int LPC, int DPL>
 __device__ __forceinline__ void load_row(const double* row, int q, uint32_t ld, double* v) {
 #pragma unroll
@@ -865,7 +904,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         }
     }
     BPM_STAMP(3);
-    wk.acc_hi = h0.z; wk.acc_lo = h0.w;
+    wk.u_acc = u01_53(h0.z, h0.w);
     const double u_sel = (double)(h0.x >> 16) * 1.52587890625e-05;      // CR select (DREAM) / snooker select (DE-MC)
     const double u_gam = (double)(h0.x & 0xFFFFu) * 1.52587890625e-05;  // gamma = 1 jump select
     uint32_t snk_id[3] = {0u, 0u, 0u};
@@ -899,8 +938,13 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     if (DREAM && NP > 0) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {             // all 2 NP row loads in flight together
-            load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p)), q, ld, ra[p]);
-            load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p + 1)), q, ld, rb[p]);
+            if (LPC == WAVE) {
+                load_row_all<LPC, DPL>(row_ptr(a.L, part.get(2 * p)), q, ld, ra[p]);
+                load_row_all<LPC, DPL>(row_ptr(a.L, part.get(2 * p + 1)), q, ld, rb[p]);
+            } else {
+                load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p)), q, ld, ra[p]);
+                load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p + 1)), q, ld, rb[p]);
+            }
         }
     }
     BPM_STAMP(7);
@@ -992,6 +1036,16 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         }
         if (a.k % 5 == 0 && !(u_gam < 0.2)) { gamma = 1.0; wk.jump = 1; }
         wk.gamma = gamma;
+        // One wavefront per chain: a launch is ONE round of wavefronts, four per SIMD, whose rows arrive together -- whatever is issued behind the
+        // row wait is issued four times over before the first store leaves.  Nothing row-independent belongs there: the accept uniform (six f64
+        // conversions the compiler otherwise sinks behind exp()) is made live here, and so are the argument fields that finish_update reads -- left
+        // alone they are three scalar loads, each with its own wait, between the accept test and the history store.
+        if (LPC == WAVE) {
+            int u_hi = __builtin_amdgcn_readfirstlane(__double2hiint(wk.u_acc)), u_lo = __builtin_amdgcn_readfirstlane(__double2loint(wk.u_acc));
+            asm volatile("" : "+s"(u_hi), "+s"(u_lo));      // (wavefront-uniform: held in scalar registers across the row wait, no VGPR)
+            wk.u_acc = __hiloint2double(u_hi, u_lo);
+            asm volatile("" ::"s"(a.wt), "s"(a.hist_by_pos), "s"(a.upd_off), "s"(a.hist_row), "s"(a.llhist_row), "s"(a.ll), "s"(a.acc_count));
+        }
         // sum over pairs of (A_p - B_p)  (dream.py:65-68,85-86), p = 0 first
         double sum[DPL];
         if (NP > 0) {
@@ -1140,7 +1194,7 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     const bool is_nan = alpha != alpha;
     alpha = fmin(1.0, alpha);
     alpha = fmax(0.0, alpha);                            // np.clip(np.min((1, .)), 0, 1); NaN stays NaN in NumPy
-    const bool accepted = !is_nan && (u01_53(wk.acc_hi, wk.acc_lo) < alpha);
+    const bool accepted = !is_nan && (wk.u_acc < alpha);
     const bool lean = LEAN == 2 || (LEAN == 1 && a.lean != 0u);
     if (lean) {      // one counter bump per wavefront (all lanes are still here): acc_count[n_local + shard]
         const unsigned long long m = __ballot(active && accepted && q == 0);
@@ -1149,6 +1203,14 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
                                    (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (!active) return;
+    double nv[DPL];
+#pragma unroll
+    for (int s = 0; s < DPL; ++s) nv[s] = accepted ? wk.p[s] : wk.x[s];
+    const double new_ll = accepted ? ll_prop : ll_cur;
+    const uint32_t hi = a.hist_by_pos ? wk.pos_own : li;
+    // one wavefront per chain: the history row -- every update's one certain store, 64 lanes wide -- leaves as soon as the accept flag exists,
+    // ahead of the single-lane bookkeeping stores (counter, ln-like, NaN count) and their branches; it stays BEHIND the accept test
+    if (LPC == WAVE && a.hist_row) store_row_stream<LPC, DPL>(a.hist_row + (uint32_t)(hi * ld), q, ld, nv);
     // accept bookkeeping without same-address atomics (8192 of them serialise at ~12 ns each):
     // every chain owns one counter, the host sums them (demc.py:143-150)
     if (q == 0) {
@@ -1163,10 +1225,6 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
         if (is_nan) atomicAdd(&a.counters[2], 1ull);
         if (a.accbits) a.accbits[a.acc_by_item ? wk.item : li] = accepted ? (uint8_t)1 : (uint8_t)0;
     }
-    double nv[DPL];
-#pragma unroll
-    for (int s = 0; s < DPL; ++s) nv[s] = accepted ? wk.p[s] : wk.x[s];
-    const double new_ll = accepted ? ll_prop : ll_cur;
     if (a.x_next) {
         // synchronous generation (samplers.py:300-308 delayed_accept): updates are banked, applied after the launch
         store_row<LPC, DPL>(a.x_next + (uint32_t)(li * ld), q, ld, nv);
@@ -1221,8 +1279,7 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
             }
         }
     }
-    const uint32_t hi = a.hist_by_pos ? wk.pos_own : li;
-    if (a.hist_row) store_row_stream<LPC, DPL>(a.hist_row + (uint32_t)(hi * ld), q, ld, nv);
+    if (LPC != WAVE && a.hist_row) store_row_stream<LPC, DPL>(a.hist_row + (uint32_t)(hi * ld), q, ld, nv);
     // (a streaming store like the row's: nobody reads the ln-like history inside the generation loop.  As a plain store the by-chain form cost cfg5's burn-in
     // 3.4 us per generation, this one 1.0; the by-position form gains too: cfg5 45.5 -> 44.5)
     // (one wavefront per chain -- a single 8-byte store per wavefront -- keeps the ordinary store: nothing to gain, and under a kernel trace the streaming
@@ -1316,6 +1373,12 @@ __device__ __forceinline__ bool resolve_chain(const PhaseArgs& a, uint32_t w, ui
     return active;
 }
 
+// The stamp build (-DBPM_STAMPS) times the single-GPU HOT instantiations themselves: there the stamp buffer does not send a launch to the general kernel.
+#ifdef BPM_STAMPS
+__host__ inline bool stamps_allow_hot(const PhaseArgs&) { return true; }
+#else
+__host__ inline bool stamps_allow_hot(const PhaseArgs& a) { return a.stamps == nullptr; }
+#endif
 // HOT: frequent cases as their own instantiations: 1 = single GPU, steady state, with plan records, 2 = the same without,
 // 3 / 4 = the same during DREAM's CR adaptation (burn-in), 5 / 6 = a rank of a multi-GPU world in the steady state
 // with the replay exchange (accept bytes; its compacted records when 5, none when 6); 0 = the general kernel.
@@ -1328,7 +1391,7 @@ __host__ inline bool phase_args_hot_sharded(const PhaseArgs& a, bool dream, bool
 __host__ inline bool phase_args_hot(const PhaseArgs& a, bool dream, bool with_plan, bool adapting) {
     return a.n_peers == 0 && a.mode == 0 && (a.rec_tab != nullptr) == with_plan && trace_i32_of(a) == nullptr && a.pack == nullptr && a.x_next == nullptr &&
            (a.adapt_on != 0) == adapting && a.epsilon > 0.0 && a.L.world == 1 &&
-           a.perm_tab != nullptr && a.inv_tab != nullptr && a.lo == 0 && a.stamps == nullptr && a.accbits == nullptr && a.replay == 0 &&
+           a.perm_tab != nullptr && a.inv_tab != nullptr && a.lo == 0 && stamps_allow_hot(a) && a.accbits == nullptr && a.replay == 0 &&
            (!dream || (a.u_epsilon > 0.0 && a.n_cr == 3));
 }
 template <int ALGO, int TARGET, int LPC, int DPL, int NP, int HOT = 0>
@@ -1353,7 +1416,12 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     if (COPY) {
         a_hot = a_in;
         a_hot.mode = 0u; trace_set(a_hot, nullptr, nullptr, nullptr); a_hot.pack = nullptr;
-        a_hot.replay = 0u; a_hot.x_next = nullptr; a_hot.adapt_on = ADAPT ? 1u : 0u; a_hot.stamps = nullptr;
+        a_hot.replay = 0u; a_hot.x_next = nullptr; a_hot.adapt_on = ADAPT ? 1u : 0u;
+#ifndef BPM_STAMPS
+        a_hot.stamps = nullptr;
+#else
+        if (SHARD) a_hot.stamps = nullptr;
+#endif
         if (!ADAPT) a_hot.cr_fold_part = nullptr;
         if (!SHARD) { a_hot.accbits = nullptr; a_hot.lo = 0; a_hot.L.world = 1; a_hot.acc_by_item = 0u; a_hot.n_peers = 0u; a_hot.peer_tab = nullptr; }
         if (ALGO == ALGO_DREAM) a_hot.n_cr = 3;
@@ -1365,7 +1433,10 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
 #ifdef BPM_TEST_HOOKS
         __builtin_assume(a_in.trace_i32 == nullptr);
 #endif
-        __builtin_assume(a_in.x_next == nullptr); __builtin_assume(a_in.adapt_on == (ADAPT ? 1u : 0u)); __builtin_assume(a_in.stamps == nullptr);
+        __builtin_assume(a_in.x_next == nullptr); __builtin_assume(a_in.adapt_on == (ADAPT ? 1u : 0u));
+#ifndef BPM_STAMPS
+        __builtin_assume(a_in.stamps == nullptr);
+#endif
         if (!SHARD) { __builtin_assume(a_in.lo == 0); __builtin_assume(a_in.L.world == 1); }
         __builtin_assume(a_in.epsilon > 0.0);
         __builtin_assume(a_in.perm_tab != nullptr); __builtin_assume(a_in.inv_tab != nullptr);
@@ -1463,6 +1534,7 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     Work<DPL> wk;
     wk.item = w;
     wk.pos_own = a.upd_off + (active ? w : 0u);
+    if (LPC == WAVE) wk.pos_own = (uint32_t)__builtin_amdgcn_readfirstlane((int)wk.pos_own);      // uniform: the history row's address stays on the scalar unit
     constexpr bool LEAN = lean_scalars<TARGET, LPC>();
     // (LEAN: ln_like of the current state from the own row == the cached value, bit for bit -- see lean_scalars)
     const uint32_t dim_early = a.L.dim;      // (captured by value, a few registers: a by-reference capture put one instantiation's constants on the stack)
@@ -1488,7 +1560,9 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     if (CRP && active && a.adapt_on && a.cr_gate) { cr_d = wk.delta; cr_i = wk.cr_idx; }      // what finish_update wrote into the chain's slots
     BPM_STAMP(6);
 #ifdef BPM_STAMPS
-    if (bpm_stamp[2] == 0) bpm_stamp[2] = bpm_rt0;
+    // (planned path: slot 2 is free for the entry's device-wide counter, and slot 1 -- "c known", which the record wait of slot 3 covers --
+    // takes the s_memtime stamp "partner rows requested" that make_proposal left in slot 7, before the device-wide counter overwrites it)
+    if (bpm_stamp[2] == 0) { bpm_stamp[2] = bpm_rt0; bpm_stamp[1] = bpm_stamp[7]; }
     // slot 7: device-wide 100 MHz counter at the end of the wavefront (s_memtime counters are per CU, not comparable
     // across CUs) with the XCD id in bits 60..63; slot 2 (in-kernel header draw, unused with plan records) holds the
     // same counter at entry when the wavefront took the planned path
@@ -1785,7 +1859,7 @@ __global__ __launch_bounds__(block_for(LPC)) void phase_commit_kernel(const Phas
     }
     const double ll_prop = active ? a.aux_buf[a.L.n_local + w] : 0.0;
     const u32x4 h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
-    wk.acc_hi = h0.z; wk.acc_lo = h0.w;
+    wk.u_acc = u01_53(h0.z, h0.w);
     wk.delta = 0.0; wk.gamma = 0.0; wk.cr_idx = -1; wk.d_prime = 0; wk.jump = 0; wk.snk = 0; wk.maskbits = 0; wk.item = w; wk.pos_own = 0u;
     // finish_update rewrites the CR slots: carry the values written by the propose kernel
     if (ALGO == ALGO_DREAM && active) {
