@@ -11,7 +11,7 @@
 // What it is not: a second code path for the kernels.  The kernel objects are the ones HIP loaded from this library's own fat
 // binary (found through the HSA loader's executable list), every packet carries the barrier bit, and memory is HIP's.  Fences are the
 // caller's choice per packet: agent-scope acquire + release like a HIP stream's, or the acquire only -- the sampler's steady state,
-// whose kernels send what their successor reads through agent-scope stores (sampler.hip: g_dq_update_fence).  The queue keeps track of
+// whose kernels send what their successor reads through agent-scope stores (sampler.hip: Dispatch::update_fence).  The queue keeps track of
 // release-less packets: drain() puts a fenced empty kernel behind them unless a later kernel on every XCD has released since.
 // Ordering against the sampler's HIP stream is by the host: the sampler drains one before it uses the other (transitions happen at
 // the end of burn-in and at the API boundary only).  BPM_QUEUE_INFLIGHT=n bounds the dispatches between two drains (for tools that

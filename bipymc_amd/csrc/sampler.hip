@@ -47,6 +47,12 @@
 
 using namespace bpm;
 
+// The host code below launches the update kernels the way the preload build compiles them (leading arguments in SGPRs, the specialised
+// instantiations): every target of csrc/Makefile defines it.  (kernels.h keeps its own #ifdef: hiprtc compiles it WITHOUT, user_likelihood.h.)
+#ifndef BPM_PRELOAD
+#error "sampler.hip needs -DBPM_PRELOAD -mllvm -amdgpu-kernarg-preload-count=5 (the flag pair of CXXFLAGS in csrc/Makefile)"
+#endif
+
 // The ONE environment variable that changes which kernels / launch shapes the library uses: BPM_TEST_PATHS, a comma-separated list read
 // once per process, for the tests that pin every alternative kernel path to the default one bit for bit
 // (tests/test_gpu_api.py::test_alternative_kernel_paths_on_one_gpu) and for the timing tools:
@@ -144,29 +150,130 @@ static int load_rccl() {
     } while (0)
 
 // ---- kernel dispatch ---------------------------------------------------------------
-// bpm_step_timed: the NEXT update-kernel launch of this thread carries this event as its stop event (hipExtLaunchKernelGGL
-// binds it to the dispatch itself: its time stamp is the kernel's end, and no marker packet enters the queue)
-static thread_local hipEvent_t g_stop_event = nullptr;
-static thread_local int64_t g_timed_launches = 0;
-static inline hipEvent_t take_stop_event() {
-    hipEvent_t e = g_stop_event;
-    g_stop_event = nullptr;
-    return e;
-}
 typedef void (*PhaseLaunch)(const PhaseArgs&, hipStream_t);
 typedef void (*EvalLaunch)(const double*, uint32_t, uint32_t, uint32_t, const double*, double*, hipStream_t);
 
-// update launches of the generation being run that took a flavour which writes level 1 of the CR reduction ITSELF (kernels.h: CRP): what
-// finish_generation holds against the host's prediction (gen_cr_inkernel) before it lets cr_final_kernel fold the partial sums
-static thread_local int g_crp_launched = 0;
-// ... and those that were handed a pending fold of the previous generation's sums AND took a flavour that folds (PhaseArgs::cr_fold_part; bpm_sampler::cr_pending)
-static thread_local int g_crfold_launched = 0;
-static thread_local bool g_call_last_gen = false;      // run_generations: the generation being run is the last one of the bpm_step call (its fold is dispatched)
+// What the functions of the generation loop (run_generations -> group_generation -> prepare_generation / finish_generation -> the launch_*
+// templates; build_window, launch_cr_final, launch_push_sync, push_barrier, push_gen_sums, launch_arena_probe, bpm_push_selftest) tell each other
+// about WHERE and HOW the current launches go: one instance per thread, grouped by lifetime.  A DispatchScope (below) is open while any of it is
+// set and puts everything but the carried flag and the counters back to idle on every way out; an OnHipStream takes a piece of work to the HIP
+// stream for a moment.  Outside a scope the state is idle: `dq` is null and every launch goes to the sampler's HIP stream.
+struct bpm_sampler;
+struct Dispatch {
+    // ---- per bpm_step call (run_generations)
+    // the host-callback sampler whose generation loop the update kernel compiled around its HIP-source likelihood is driving (else nullptr):
+    // prepare_generation asks who drives a host-callback sampler
+    bpm_sampler* user_cur = nullptr;
+    bool user_launch_failed = false;       // launch_user_fused found no module to launch from: run_generations reports it
+
+    // ---- per generation
+    // Direct mode (aql_queue.h): while run_generations has the sampler in direct mode, dq names its queue and every kernel of the
+    // generation loop -- update kernels here, table builds in build_window -- is dispatched by a packet this library writes itself.
+    bpm::DirectQueue* dq = nullptr;
+    // A local group whose ranks each have a queue of their own (BPM_TEST_PATHS=groupqueues) runs in direct mode rank by rank: dq is
+    // re-bound to the rank a piece of work belongs to (bind_rank_queue); the ranks' kernels then wait for each other ACROSS queues the way
+    // the ranks of a multi-GPU world do.
+    bool group_direct = false;
+    bool dq_error = false;                 // a dispatch could not be made: run_generations reports it
+    // Fences of an update-kernel packet.  A HIP stream puts agent-scope acquire + release around every kernel; the release (write-back of
+    // every XCD's L2 at the end of the kernel) is 0.6 us of a 6 us launch period at cfg2.  On the library's own queue the update kernel instead
+    // sends what later kernels read -- accepted rows, ln-like, accept counters, during CR adaptation the Welford rows and the CR slots --
+    // through write-through stores (PhaseArgs::wt, kernels.h: store_row_wt16) and its packet carries the acquire only; history rows
+    // (non-temporal stores, read by nobody before the drain) are written back by the fenced empty kernel DirectQueue::drain puts behind
+    // such packets.  Round 2 did this in the steady state up to 4 MiB per half generation only (two 8-byte atomic stores per lane cost
+    // more than the release beyond that, and in burn-in); with one 16-byte store per lane it wins everywhere (profiles/r03_write_through_16B.txt).
+    // bpm_set_launch_path(h, 1, 3): acquire + release on every packet with plain stores.  The packet after a table build or after entering
+    // direct mode always acquires.
+    int update_fence = bpm::DirectQueue::FENCED;
+    bool wt_stores = false;                // this generation's update kernels store through (PhaseArgs::wt)
+    bool call_last_gen = false;            // the generation being run is the last one of the bpm_step call (its fold is dispatched) ...
+    bool dq_call_last_gen = false;         // ... and runs in direct mode: its last update dispatch carries the release (release_this)
+
+    // ---- one-shot: riders on the NEXT update launch, consumed by it (take_update_packet / take_stop_event)
+    // bpm_step_timed: the launch carries this event as its stop event (hipExtLaunchKernelGGL binds it to the dispatch itself: its time stamp
+    // is the kernel's end, and no marker packet enters the queue) ...
+    hipEvent_t stop_event = nullptr;
+    int sig = -1;                          // ... or, on the library's own queue, this timing signal
+    bool release_this = false;             // the packet carries the release: the drain that usually follows the call then needs no fence
+                                           // kernel (2.5 us of a short window)
+    // the packet acquires whatever update_fence says: set by what went onto the queue beside the update kernels (a table build, the running-moment
+    // sums, a push barrier, a section on the HIP stream, entering direct mode), cleared by the CR reduction, whose packets all acquire themselves.
+    // The one rider that is CARRIED from a generation to the next -- a side kernel at the end of a generation marks the first update packet of the
+    // following one -- so no scope resets it.
+    bool need_acquire = false;
+
+    // ---- tallies of the generation, restarted by prepare_generation and held against the host's prediction by finish_generation
+    // update launches that took a flavour which writes level 1 of the CR reduction ITSELF (kernels.h: CRP): what finish_generation holds against
+    // gen_cr_inkernel before it lets cr_final_kernel fold the partial sums
+    int crp_launched = 0;
+    // ... and those that were handed a pending fold of the previous generation's sums AND took a flavour that folds (PhaseArgs::cr_fold_part; bpm_sampler::cr_pending)
+    int crfold_launched = 0;
+
+    // ---- per-thread counters, never reset: update-kernel dispatches by path (bpm_get_launch_stats) and altogether (bpm_step_timed)
+    int64_t n_direct = 0, n_stream = 0;
+    int64_t timed_launches = 0;
+
+    void restart_tallies() { crp_launched = 0; crfold_launched = 0; }
+    void mark_acquire(bool v) { need_acquire = v; }
+    // everything a DispatchScope owns, back to idle
+    void idle() {
+        user_cur = nullptr; user_launch_failed = false;
+        dq = nullptr; group_direct = false; dq_error = false; update_fence = bpm::DirectQueue::FENCED;
+        wt_stores = false; call_last_gen = false; dq_call_last_gen = false;
+        stop_event = nullptr; sig = -1; release_this = false;
+        restart_tallies();
+    }
+};
+static thread_local Dispatch g_disp;
+// Open around one generation (or one chunk of generations under the sparse exchange) of run_generations and around the arena part of
+// bpm_push_selftest: whatever way the function is left, the next entry point of this thread finds the state idle.
+struct DispatchScope {
+    Dispatch& d;
+    explicit DispatchScope(bpm_sampler* user_cur = nullptr) : d(g_disp) { d.user_cur = user_cur; }
+    ~DispatchScope() { d.idle(); }
+    DispatchScope(const DispatchScope&) = delete;
+    DispatchScope& operator=(const DispatchScope&) = delete;
+};
+// "Run this on the HIP stream for a moment" inside a direct-mode generation (the outlier check): the queue binding is set aside and comes back.
+struct OnHipStream {
+    Dispatch& d;
+    bpm::DirectQueue* const dq;
+    const bool group_direct;
+    OnHipStream() : d(g_disp), dq(d.dq), group_direct(d.group_direct) { d.dq = nullptr; d.group_direct = false; }
+    ~OnHipStream() { d.dq = dq; d.group_direct = group_direct; }
+    OnHipStream(const OnHipStream&) = delete;
+    OnHipStream& operator=(const OnHipStream&) = delete;
+};
+// The one consumer of the riders of an update packet on the library's own queue: its fences and its timing signal, what it used cleared.
+struct UpdatePacket { int fence, sig; };
+static inline UpdatePacket take_update_packet(Dispatch& d) {
+    UpdatePacket p{d.update_fence, d.sig};
+    d.sig = -1;
+    if (d.need_acquire) { p.fence |= bpm::DirectQueue::ACQUIRE; d.need_acquire = false; }
+    if (d.release_this) { p.fence |= bpm::DirectQueue::RELEASE; d.release_this = false; }
+    return p;
+}
+// ... and of the rider of an update launch on the HIP stream
+static inline hipEvent_t take_stop_event(Dispatch& d) {
+    hipEvent_t e = d.stop_event;
+    d.stop_event = nullptr;
+    return e;
+}
+// A kernel BESIDE the update kernels (table builds, the CR reduction, the running-moment sums, the push barrier, the arena probe) as a packet on
+// the queue of the generation being run (g_disp.dq, not null).  `ka` is its kernel-argument block as the device reads it.
+// then: what the launch means for the next update packet -- it must acquire, need not (the CR fold: see need_acquire), or no change.
+enum class Then { KEEP, ACQUIRE, NO_ACQUIRE };
+static int launch_beside(const void* kernel, const char* name, uint32_t grid_x, uint32_t grid_y, uint32_t block, const void* ka, size_t nbytes, int fence, Then then) {
+    Dispatch& d = g_disp;
+    const bpm::DqKernel* k = d.dq->kernel(kernel);
+    if (!k || d.dq->launch(*k, grid_x, grid_y, block, ka, nbytes, fence) != 0) return fail(std::string("direct AQL queue: ") + name + ": " + d.dq->why());
+    if (then != Then::KEEP) d.mark_acquire(then == Then::ACQUIRE);
+    return 0;
+}
 static inline uint32_t grid_for(uint32_t n_items, int lpc) {
     const uint32_t cpw = (uint32_t)(block_for(lpc) / lpc);
     return (n_items + cpw - 1) / cpw;
 }
-#ifdef BPM_PRELOAD
 // The kernel-argument block of phase_fused_kernel exactly as the device reads it (natural alignment = the kernarg layout): the
 // launch goes through hipExtModuleLaunchKernel with this buffer -- no per-launch symbol lookup, no per-argument marshalling.
 struct FusedKernarg {
@@ -175,47 +282,20 @@ struct FusedKernarg {
     PhaseArgs a;
 };
 static_assert(offsetof(FusedKernarg, a) == 24 && sizeof(FusedKernarg) == 24 + sizeof(PhaseArgs), "kernarg layout of phase_fused_kernel");
-// Direct mode (aql_queue.h): while run_generations has the sampler in direct mode, g_dq names its queue and every kernel of the
-// generation loop -- update kernels here, table builds in build_window -- is dispatched by a packet this library writes itself.
-static thread_local bpm::DirectQueue* g_dq = nullptr;
-static thread_local int g_dq_sig = -1;            // the next update dispatch carries this timing signal (bpm_step_timed)
-static thread_local bool g_dq_error = false;      // a dispatch could not be made: run_generations reports it
-// Fences of an update-kernel packet.  A HIP stream puts agent-scope acquire + release around every kernel; the release (write-back of
-// every XCD's L2 at the end of the kernel) is 0.6 us of a 6 us launch period at cfg2.  On the library's own queue the update kernel instead
-// sends what later kernels read -- accepted rows, ln-like, accept counters, during CR adaptation the Welford rows and the CR slots --
-// through write-through stores (PhaseArgs::wt, kernels.h: store_row_wt16) and its packet carries the acquire only; history rows
-// (non-temporal stores, read by nobody before the drain) are written back by the fenced empty kernel DirectQueue::drain puts behind
-// such packets.  Round 2 did this in the steady state up to 4 MiB per half generation only (two 8-byte atomic stores per lane cost
-// more than the release beyond that, and in burn-in); with one 16-byte store per lane it wins everywhere (profiles/r03_write_through_16B.txt).
-// bpm_set_launch_path(h, 1, 3): acquire + release on every packet with plain stores.  The packet after a table build or after entering
-// direct mode always acquires.
-static thread_local int g_dq_update_fence = bpm::DirectQueue::FENCED;
-static thread_local bool g_dq_call_last_gen = false;      // run_generations: this is the last generation of the bpm_step call ...
-static thread_local bool g_dq_release_this = false;       // ... whose last update dispatch carries the release: the drain that usually
-                                                           // follows the call then needs no fence kernel (2.5 us of a short window)
-static thread_local bool g_wt_stores = false;             // this generation's update kernels store through (PhaseArgs::wt)
-static thread_local bool g_dq_need_acquire = false;
-static thread_local int64_t g_n_direct = 0, g_n_stream = 0;   // update-kernel dispatches of this thread by path (bpm_get_launch_stats)
-// A local group whose ranks each have a queue of their own (BPM_TEST_PATHS=groupqueues) runs in direct mode rank by rank: g_dq is
-// re-bound to the rank a piece of work belongs to (bind_rank_queue); the ranks' kernels then wait for each other ACROSS queues the way
-// the ranks of a multi-GPU world do.
-static thread_local bool g_group_direct = false;
 template <class K>
 static inline void launch_packed(K kernel, hipFunction_t& fn, const PhaseArgs& a, unsigned grid, unsigned block, hipStream_t s) {
-    if (g_dq) {
+    Dispatch& d = g_disp;
+    if (d.dq) {
         FusedKernarg ka;
         ka.pl_plan = a.rec_tab; ka.pl_upd_off = a.rec_off; ka.pl_n_items = a.n_items; ka.pl_mode = a.mode; ka._pad = 0u;
         ka.a = a;
-        const bpm::DqKernel* k = g_dq->kernel(reinterpret_cast<const void*>(kernel));
-        const int sig = g_dq_sig; g_dq_sig = -1;
-        int fence = g_dq_update_fence;
-        if (g_dq_need_acquire) { fence |= bpm::DirectQueue::ACQUIRE; g_dq_need_acquire = false; }
-        if (g_dq_release_this) { fence |= bpm::DirectQueue::RELEASE; g_dq_release_this = false; }
-        if (!k || g_dq->launch(*k, grid, 1, block, &ka, sizeof(ka), fence, sig) != 0) g_dq_error = true;
-        ++g_timed_launches; ++g_n_direct;
+        const bpm::DqKernel* k = d.dq->kernel(reinterpret_cast<const void*>(kernel));
+        const UpdatePacket p = take_update_packet(d);
+        if (!k || d.dq->launch(*k, grid, 1, block, &ka, sizeof(ka), p.fence, p.sig) != 0) d.dq_error = true;
+        ++d.timed_launches; ++d.n_direct;
         return;
     }
-    ++g_n_stream;
+    ++d.n_stream;
     if (!fn) { if (hipGetFuncBySymbol(&fn, reinterpret_cast<const void*>(kernel)) != hipSuccess) { (void)hipGetLastError(); fn = nullptr; } }
     if (fn) {
         FusedKernarg ka;
@@ -223,24 +303,25 @@ static inline void launch_packed(K kernel, hipFunction_t& fn, const PhaseArgs& a
         ka.a = a;
         size_t sz = sizeof(ka);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        (void)hipExtModuleLaunchKernel(fn, grid * block, 1, 1, block, 1, 1, 0, s, nullptr, extra, nullptr, take_stop_event(), 0);
+        (void)hipExtModuleLaunchKernel(fn, grid * block, 1, 1, block, 1, 1, 0, s, nullptr, extra, nullptr, take_stop_event(d), 0);
     } else {
-        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, nullptr, take_stop_event(), 0, a.rec_tab, a.rec_off, a.n_items, a.mode, a);
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, nullptr, take_stop_event(d), 0, a.rec_tab, a.rec_off, a.n_items, a.mode, a);
     }
-    ++g_timed_launches;
+    ++d.timed_launches;
 }
 template <int ALGO, int T, int NP, int LPC, int DPL, int HOT>
 static void launch_hot(const PhaseArgs& a, hipStream_t s) {
     static hipFunction_t fn = nullptr;
-    if (ALGO == ALGO_DREAM && hot_is_adapt(HOT) && crp_shape(LPC, DPL)) ++g_crp_launched;
-    if (ALGO == ALGO_DREAM && hot_is_adapt(HOT) && crp_shape(LPC, DPL) && a.cr_fold_part != nullptr) ++g_crfold_launched;
+    if (ALGO == ALGO_DREAM && hot_is_adapt(HOT) && crp_shape(LPC, DPL)) {
+        Dispatch& d = g_disp;
+        ++d.crp_launched;
+        if (a.cr_fold_part != nullptr) ++d.crfold_launched;
+    }
     constexpr unsigned blk = (unsigned)block_for_hot(LPC, HOT, DPL), cpw = blk / (unsigned)LPC;      // (burn-in flavours of one wavefront per chain: 16 chains per workgroup)
     launch_packed(phase_fused_kernel<ALGO, T, LPC, DPL, NP, HOT>, fn, a, (a.n_items + cpw - 1u) / cpw, blk, s);
 }
-#endif
 template <int ALGO, int T, int NP, int LPC, int DPL>
 static void launch_fused(const PhaseArgs& a, hipStream_t s) {
-#ifdef BPM_PRELOAD
     {   // frequent cases take a specialised instantiation (kernels.h: HOT): steady state, DREAM's burn-in, a rank of a world
         constexpr bool CAN_PLAN = (LPC == WAVE && DPL == 2);               // the shape that can read plan records
         const bool wp = CAN_PLAN && a.rec_tab != nullptr;
@@ -262,13 +343,7 @@ static void launch_fused(const PhaseArgs& a, hipStream_t s) {
     {   // the general instantiation: same argument block, same two launch paths
         static hipFunction_t fn = nullptr;
         launch_packed(phase_fused_kernel<ALGO, T, LPC, DPL, NP>, fn, a, grid_for(a.n_items, LPC), (unsigned)block_for(LPC), s);
-        return;
     }
-#else
-    hipExtLaunchKernelGGL((phase_fused_kernel<ALGO, T, LPC, DPL, NP>), dim3(grid_for(a.n_items, LPC)), dim3(block_for(LPC)), 0, s,
-                          nullptr, take_stop_event(), 0, a);
-#endif
-    ++g_timed_launches;
 }
 template <int ALGO, int LPC, int DPL>
 static void launch_propose(const PhaseArgs& a, hipStream_t s) {
@@ -317,22 +392,13 @@ constexpr int SHAPE_WIDE = 6;
 template <int ALGO, int T, int NP>
 static void launch_wide(const PhaseArgs& a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.n_items + (BPM_BLOCK_WAVE / WAVE) - 1) / (BPM_BLOCK_WAVE / WAVE));
-#ifdef BPM_PRELOAD
     static hipFunction_t fn = nullptr;
     launch_packed(phase_wide_kernel<ALGO, T, NP, STAGE_FUSED>, fn, a, grid, (unsigned)BPM_BLOCK_WAVE, s);
-#else
-    hipExtLaunchKernelGGL((phase_wide_kernel<ALGO, T, NP, STAGE_FUSED>), dim3(grid), dim3(BPM_BLOCK_WAVE), 0, s, nullptr, take_stop_event(), 0, a);
-    ++g_timed_launches;
-#endif
 }
 template <int ALGO>
 static void launch_wide_propose(const PhaseArgs& a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.n_items + (BPM_BLOCK_WAVE / WAVE) - 1) / (BPM_BLOCK_WAVE / WAVE));
-#ifdef BPM_PRELOAD
     hipLaunchKernelGGL((phase_wide_kernel<ALGO, TARGET_HOST, 0, STAGE_PROPOSE>), dim3(grid), dim3(BPM_BLOCK_WAVE), 0, s, a.rec_tab, a.rec_off, a.n_items, a.mode, a);
-#else
-    hipLaunchKernelGGL((phase_wide_kernel<ALGO, TARGET_HOST, 0, STAGE_PROPOSE>), dim3(grid), dim3(BPM_BLOCK_WAVE), 0, s, a);
-#endif
 }
 template <int ALGO>
 static void launch_wide_commit(const PhaseArgs& a, hipStream_t s) {
@@ -627,11 +693,6 @@ struct bpm_sampler {
     // (they re-evaluate it from the own row); ll_stale says that generations have run since it was last evaluated -- refresh_ll brings it up
     // to date for whoever reads it (bpm_get_loglike, the outlier check)
     bool lean = false, ll_stale = false;
-#ifdef BPM_EXPERIMENT_XCD      // (round 5 experiment: a generation loop resident on one XCD, kernels.h: xcd_resident_kernel)
-    PhaseArgs* xcd_args = nullptr;           // device: the argument blocks of one batch of half generations
-    uint32_t* xcd_ctl = nullptr;             // device: ticket | barrier counter | workers | error | XCC ids seen
-    int64_t xcd_gens = 0;                    // generations run this way
-#endif
     bool gen_adapt_on = false;
     bool gen_cr_reduce = false;       // this generation's (delta, cr) slots are reduced (adaptation on AND the gate of dream.py:123 open)
 };
@@ -670,13 +731,13 @@ static int check_handle_keep_direct(bpm_handle_t h) {      // (bpm_step and frie
     if (!h) return fail("null handle");
     return 0;
 }
-StreamSection::StreamSection(bpm_sampler* s_) : s(s_), was(s_->dq_active && g_dq != nullptr), rc(0) {
+StreamSection::StreamSection(bpm_sampler* s_) : s(s_), was(s_->dq_active && g_disp.dq != nullptr), rc(0) {
     if (was) { s->dq->flush(); rc = s->dq->drain() != 0 ? fail("direct AQL queue: " + s->dq->why()) : 0; }
 }
 int StreamSection::end() {
     if (!was) return 0;
     CK(wait_stream(s->stream));
-    g_dq_need_acquire = true;
+    g_disp.mark_acquire(true);
     return 0;
 }
 
@@ -775,7 +836,7 @@ static int ensure_history(bpm_sampler* s, int64_t rows) {
     s->llhist = nl;
     s->hist_cap = cap;
     s->hist_tag.resize((size_t)cap, -1);
-    s->dq_active = was_direct && g_dq != nullptr;      // (inside a direct-mode generation: the stream is idle again, go on)
+    s->dq_active = was_direct && g_disp.dq != nullptr;      // (inside a direct-mode generation: the stream is idle again, go on)
     return 0;
 }
 
@@ -935,7 +996,7 @@ static int ensure_gen_sums(bpm_sampler* s, int64_t rows) {
     if (s->gen_sums) HIPCK(hipFree(s->gen_sums));
     s->gen_sums = n;
     s->gen_sums_cap = cap;
-    s->dq_active = was_direct && g_dq != nullptr;
+    s->dq_active = was_direct && g_disp.dq != nullptr;
     return 0;
 }
 // the sums of history row `row` from this rank's block of the state matrix as it stands (two dispatches: per-block partial sums, a
@@ -944,18 +1005,13 @@ static int push_gen_sums(bpm_sampler* s, int64_t row, const double* src = nullpt
     if (!s->cfg.running_moments) return 0;
     const double* Xl = src ? src : s->G + (uint64_t)s->rank * s->L.blk;
     double* out = s->gen_sums + (size_t)row * 2 * s->ld;
-    if (g_dq) {
+    if (g_disp.dq) {
         struct { const double* H; uint64_t lo, hi; uint32_t ld, _pad; const double* shift; double* part; } pa{Xl, 0, s->n_local, s->ld, 0u, s->gs_shift, s->gs_part};
         struct { const double* part; uint32_t nb, ld; double* out; } fa{s->gs_part, s->gs_nb, s->ld, out};
-        const bpm::DqKernel* kp = g_dq->kernel(reinterpret_cast<const void*>(moments_partial_kernel));
-        const bpm::DqKernel* kf = g_dq->kernel(reinterpret_cast<const void*>(moments_final_kernel));
         // (reads rows that update kernels wrote, possibly with agent-scope stores behind release-less packets: acquire; writes what only
         // bpm_reduce_moments reads, behind a drain: plain stores, release left to the drain's fence kernel)
-        if (!kp || !kf || g_dq->launch(*kp, s->gs_nb, 1, MOM_THREADS, &pa, sizeof(pa), bpm::DirectQueue::FENCED) != 0 ||
-            g_dq->launch(*kf, s->ld, 1, MOM_THREADS, &fa, sizeof(fa), bpm::DirectQueue::FENCED) != 0)
-            return fail("direct AQL queue: running-moment kernels: " + g_dq->why());
-        g_dq_need_acquire = true;
-        return 0;
+        CK(launch_beside(reinterpret_cast<const void*>(moments_partial_kernel), "running-moment kernels", s->gs_nb, 1, MOM_THREADS, &pa, sizeof(pa), bpm::DirectQueue::FENCED, Then::KEEP));
+        return launch_beside(reinterpret_cast<const void*>(moments_final_kernel), "running-moment kernels", s->ld, 1, MOM_THREADS, &fa, sizeof(fa), bpm::DirectQueue::FENCED, Then::ACQUIRE);
     }
     hipLaunchKernelGGL(moments_partial_kernel, dim3(s->gs_nb), dim3(MOM_THREADS), 0, s->stream, Xl, (uint64_t)0, (uint64_t)s->n_local, s->ld,
                        (const double*)s->gs_shift, s->gs_part);
@@ -1076,9 +1132,6 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     if (s->h_ids) (void)hipHostFree(s->h_ids);
     if (s->h_props) (void)hipHostFree(s->h_props);
     if (s->h_ll) (void)hipHostFree(s->h_ll);
-#ifdef BPM_EXPERIMENT_XCD
-    if (free_buffers) { if (s->xcd_args) (void)hipFree(s->xcd_args); if (s->xcd_ctl) (void)hipFree(s->xcd_ctl); }
-#endif
     for (hipEvent_t e : s->chunk_ev) if (e) (void)hipEventDestroy(e);
     if (free_buffers) { if (s->user_mod) (void)hipModuleUnload(s->user_mod); if (s->user_fused_mod) { if (s->dq) for (const std::string& nm : s->user_fused_names) s->dq->forget_named(nm); (void)hipModuleUnload(s->user_fused_mod); } if (s->user_params) (void)hipFree(s->user_params); }
     for (auto& B : s->tb) {
@@ -1197,7 +1250,7 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         if (s->dq && !s->dq->kernel(reinterpret_cast<const void*>(perm_table_kernel))) s->dq = nullptr;      // (HIP's copy of the code object not found)
     }
     // The state lives in ordinary device memory; the steady-state packets of the generation loop carry the acquire fence only and the
-    // update kernel writes what its successor reads with agent-scope stores (g_dq_update_fence above).  Without the fence kernel (not
+    // update kernel writes what its successor reads with agent-scope stores (Dispatch::update_fence above).  Without the fence kernel (not
     // found among the loaded code objects): acquire + release on every packet, like a HIP stream; bpm_set_launch_path chooses per handle.
     // The round-2 experiment that kept the state in the GPU's hardware-coherent memory type with acquire-only packets is NOT part of
     // this library: histories came back with older contents in sequences of samplers created and destroyed in one process, cause not
@@ -1288,7 +1341,7 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
     // (the banana's kernels have the lean form only: its ln_like is a dozen flops)
     s->lean = s->shape.idx < 3 && tid != BPM_TARGET_HOST_CALLBACK &&
               (tid == BPM_TARGET_BANANA_2D || ((s->n_local >= 49152u || test_path("lean")) && !test_path("nolean")));
-    // (a host-callback sampler: used only while the update kernel compiled around its HIP-source likelihood drives it -- prepare_generation asks g_user_cur;
+    // (a host-callback sampler: used only while the update kernel compiled around its HIP-source likelihood drives it -- prepare_generation asks Dispatch::user_cur;
     // the proposal / commit kernels of the host transports append by chain)
     s->hist_by_pos = s->world == 1 && s->shape.idx < 3 && cfg->keep_history != 0 && cfg->algo != BPM_ALGO_DEMC_SYNC && !test_path("histchain");
     if (s->hist_by_pos) CKD(dev_alloc(&s->hist_tmp, (size_t)s->n_local * (s->ld + 1)));
@@ -1545,24 +1598,22 @@ static int build_window(bpm_sampler* s, int b, int64_t W, int shuffle) {
     // their kernel path on one GPU); a single-GPU sampler's buffer stays allocated (PhaseArgs::inv_tab is never null with tables) but is not filled
     static const bool force_mode1 = test_path("mode1");
     uint32_t* const inv_out = (s->world > 1 || force_mode1) ? B.inv : nullptr;
-    if (g_dq && !B.sidx) {
+    if (g_disp.dq && !B.sidx) {
         // direct mode, records by position: the same two kernels as packets on the library's queue, in order with
         // the update kernels around them
         struct { PermKeys keys; uint32_t n_gens, N; uint32_t* tab; uint32_t* inv; } pa{keys, (uint32_t)K, s->N, B.perm, inv_out};
         static_assert(offsetof(decltype(pa), tab) == sizeof(PermKeys) + 8, "kernarg layout of perm_table_kernel");
-        const bpm::DqKernel* kp = g_dq->kernel(reinterpret_cast<const void*>(perm_table_kernel));
-        if (!kp || g_dq->launch(*kp, (uint32_t)((n + 255) / 256), 1, 256, &pa, sizeof(pa), bpm::DirectQueue::FENCED) != 0) return fail("direct AQL queue: perm_table_kernel: " + g_dq->why());
+        CK(launch_beside(reinterpret_cast<const void*>(perm_table_kernel), "perm_table_kernel", (uint32_t)((n + 255) / 256), 1, 256, &pa, sizeof(pa), bpm::DirectQueue::FENCED, Then::KEEP));
         if (B.plan) {
             struct { PlanParams P; const uint32_t* tab; uint32_t* plan; const uint32_t* sidx; } qa{
                 PlanParams{s->cfg.seed, (uint64_t)t0, (uint32_t)K, s->N, s->cfg.algo == BPM_ALGO_DREAM ? (uint32_t)s->cfg.del_pairs : 1u,
                            (s->cfg.algo == BPM_ALGO_DEMC && s->cfg.p_snooker > 0.0) ? 1u : 0u, 0u, 0u},
                 B.perm, B.plan, B.sidx};
-            const bpm::DqKernel* kq = g_dq->kernel(reinterpret_cast<const void*>(plan_kernel));
-            if (!kq || g_dq->launch(*kq, (uint32_t)((n + 255) / 256), 1, 256, &qa, sizeof(qa), bpm::DirectQueue::FENCED) != 0) return fail("direct AQL queue: plan_kernel: " + g_dq->why());
+            CK(launch_beside(reinterpret_cast<const void*>(plan_kernel), "plan_kernel", (uint32_t)((n + 255) / 256), 1, 256, &qa, sizeof(qa), bpm::DirectQueue::FENCED, Then::KEEP));
         }
         B.W = W;
         B.shuffle = shuffle;
-        g_dq_need_acquire = true;
+        g_disp.mark_acquire(true);      // (the update kernels read the tables)
         return 0;
     }
     // A rank of a world with owner-sorted records (B.sidx) builds on the HIP stream even while its generation loop runs on the library's
@@ -1631,9 +1682,6 @@ static int ensure_perm_table(bpm_sampler* s, int64_t t, int64_t /*n_ahead*/) {
 
 // Everything of one generation that is decided on the host: flip, shuffle key, group ranges
 // (demc.py:81-86,95-100), gating flags (dream.py:92,123), history row.
-// the host-callback sampler whose generation loop the update kernel compiled around its HIP-source likelihood is driving (run_generations; else nullptr)
-static thread_local bpm_sampler* g_user_cur = nullptr;
-static thread_local bool g_user_launch_failed = false;
 // totals (cr_state) + `cnt` partial sums of one generation -> cr_state: cr_final_kernel on the queue the generation loop runs on
 static int launch_cr_final(bpm_sampler* s, const double* src, uint32_t cnt) {
     const uint32_t n_cr = (uint32_t)s->cfg.n_cr;
@@ -1642,11 +1690,9 @@ static int launch_cr_final(bpm_sampler* s, const double* src, uint32_t cnt) {
     typedef void (*FinalK)(const double*, const double*, uint32_t, uint32_t, double*);
     const uint32_t rounds = (cnt + WAVE - 1) / WAVE;
     const FinalK kfn = rounds <= 1 ? cr_final_kernel<1> : (rounds <= 2 ? cr_final_kernel<2> : (rounds <= 4 ? cr_final_kernel<4> : cr_final_kernel<8>));
-    if (g_dq) {
+    if (g_disp.dq) {
         struct { const double* tot; const double* part; uint32_t nb, n_cr; double* cr_state; } fa{s->cr_state, src, cnt, n_cr, s->cr_state};
-        const bpm::DqKernel* kf = g_dq->kernel(reinterpret_cast<const void*>(kfn));
-        if (!kf || g_dq->launch(*kf, 1, 1, WAVE, &fa, sizeof(fa), fence) != 0) return fail("direct AQL queue: cr_final_kernel: " + g_dq->why());
-        g_dq_need_acquire = false;
+        CK(launch_beside(reinterpret_cast<const void*>(kfn), "cr_final_kernel", 1, 1, WAVE, &fa, sizeof(fa), fence, Then::NO_ACQUIRE));
     } else {
         hipLaunchKernelGGL(kfn, dim3(1), dim3(WAVE), 0, s->stream, (const double*)s->cr_state, src, cnt, n_cr, s->cr_state);
         HIPCK(hipGetLastError());
@@ -1766,9 +1812,9 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
         // (while the outlier check is due every few generations -- DREAM burn-in with outlier_every > 0 -- the ln-like goes by chain: the check sums
         // every chain's ln-like history, and reads the state rows of the few chains it resets where they lie: outlier_row_keys)
         const bool outlier_phase = dream && s->cfg.outlier_every > 0 && s->k_gen < s->cfg.burnin_gen;
-        a.hist_by_pos = (s->hist_by_pos && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || g_user_cur == s) && hist_row != nullptr && !by_chain && !sync &&
+        a.hist_by_pos = (s->hist_by_pos && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || g_disp.user_cur == s) && hist_row != nullptr && !by_chain && !sync &&
                          s->trace_i32 == nullptr) ? (outlier_phase ? 2u : 1u) : 0u;
-        { static const bool wt8 = test_path("wt8"); a.wt = g_wt_stores ? (wt8 ? 1u : 2u) : 0u; }
+        { static const bool wt8 = test_path("wt8"); a.wt = g_disp.wt_stores ? (wt8 ? 1u : 2u) : 0u; }
         a.lean = s->lean ? 1u : 0u;
         a.algo = (uint32_t)s->cfg.algo;
         a.P = (uint32_t)s->cfg.del_pairs;
@@ -1803,13 +1849,11 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
     // CR reduction, level 1 (kernels.h): written by the update kernels themselves when BOTH launches of the generation take a burn-in flavour
     // (HOT 3 / 4: single GPU, work item = position, no trace ...: the predicate launch_fused applies), else computed from the slots in finish_generation
     s->gen_cr_inkernel = false;
-    g_crp_launched = 0;
-    g_crfold_launched = 0;
+    g_disp.restart_tallies();
     s->gen_fold_planned = false;
     if (s->cr_p1) s->cr_p1_cur = s->cr_p1 + (size_t)(s->t_abs & 1) * 2 * MAX_CR * s->cr_n1;
-#ifdef BPM_PRELOAD      // (the specialised flavours exist only in the preload build: without it every launch ends in the general kernel, which writes the slots)
-    // (a host-callback sampler: only while the update kernel compiled around its HIP-source likelihood drives it -- g_user_cur -- and has the burn-in flavour)
-    if (s->gen_cr_reduce && dream && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || (g_user_cur == s && s->user_fused_adapt != nullptr && (s->cur_args[0].rec_tab != nullptr) == s->plan_on)) &&
+    // (a host-callback sampler: only while the update kernel compiled around its HIP-source likelihood drives it -- Dispatch::user_cur -- and has the burn-in flavour)
+    if (s->gen_cr_reduce && dream && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || (g_disp.user_cur == s && s->user_fused_adapt != nullptr && (s->cur_args[0].rec_tab != nullptr) == s->plan_on)) &&
         s->shape.idx != SHAPE_WIDE && crp_shape(s->shape.lpc, s->shape.dpl) &&
         !test_path("nohot") && !test_path("crslots")) {
         bool ok = true;
@@ -1827,7 +1871,6 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
             s->gen_cr_inkernel = true;
         }
     }
-#endif
     // a pending fold of the previous generation's CR statistics (bpm_sampler::cr_pending): consumed by this generation's first update launch when that one
     // takes a flavour that can (a burn-in flavour that sums level 1 itself: HOT 3 / 4), else dispatched now, ahead of the update launches
     if (s->cr_pending) {
@@ -1853,30 +1896,30 @@ static int finish_generation(bpm_sampler* s) {
         // (gen_cr_inkernel) or is computed from the slots here, cr_mid_kernel passes bring more than 1024 partial sums down, cr_final_kernel folds
         const uint32_t n_cr = (uint32_t)s->cfg.n_cr;
         const int fence = s->dq_fence | bpm::DirectQueue::ACQUIRE;      // (a few hundred bytes, all through agent-scope stores: no release on these packets)
-        if (g_dq) g_dq_need_acquire = false;
+        Dispatch& d = g_disp;
+        if (d.dq) d.mark_acquire(false);
         // The host PREDICTED (prepare_generation) that both launches take a flavour that writes level 1 itself; what was launched decides.  Every
         // flavour that does not write level 1 writes the chains' slots (kernels.h: finish_update<..., CRP_W>), so "none did" falls back to
         // cr_level1_kernel over the slots; a mix of the two would fold stale partial sums into p_cr -- an error, never a silent result.
         bool level1_from_slots = !s->gen_cr_inkernel;
-        if (s->gen_fold_planned && g_crfold_launched != 1)
+        if (s->gen_fold_planned && d.crfold_launched != 1)
             return fail("CR reduction: the first update launch of generation " + std::to_string((long long)s->t_abs) + " was handed the previous generation's fold and took a flavour that "
                         "does not fold (launch_fused's flavour choice and prepare_generation's prediction disagree)");
         if (s->gen_cr_inkernel) {
             const int want = (s->cur_args[0].n_items > 0 ? 1 : 0) + (s->cur_args[1].n_items > 0 ? 1 : 0);
-            if (g_crp_launched == 0 && want > 0) level1_from_slots = true;
-            else if (g_crp_launched != want)
-                return fail("CR reduction: " + std::to_string(g_crp_launched) + " of " + std::to_string(want) + " update launches of generation " + std::to_string((long long)s->t_abs) +
+            if (d.crp_launched == 0 && want > 0) level1_from_slots = true;
+            else if (d.crp_launched != want)
+                return fail("CR reduction: " + std::to_string(d.crp_launched) + " of " + std::to_string(want) + " update launches of generation " + std::to_string((long long)s->t_abs) +
                             " wrote their level-1 partial sums (launch_fused's flavour choice and prepare_generation's prediction disagree)");
         }
         if (level1_from_slots) {
             const PhaseArgs& a0 = s->cur_args[0];
             typedef void (*L1K)(Layout, PermKey, const uint32_t*, uint32_t, uint32_t, uint32_t, double*);
             const L1K l1 = s->cr_g1 == 4u ? cr_level1_kernel<4> : (s->cr_g1 == 16u ? cr_level1_kernel<16> : cr_level1_kernel<64>);
-            if (g_dq) {
+            if (d.dq) {
                 struct { Layout L; PermKey pk; const uint32_t* perm; uint32_t N, n_cr, n1, _pad; double* part1; } ka{s->L, a0.pk, a0.perm_tab, s->N, n_cr, s->cr_n1, 0u, s->cr_p1_cur};
-                const bpm::DqKernel* k = g_dq->kernel(reinterpret_cast<const void*>(l1));
-                if (!k || g_dq->launch(*k, (uint32_t)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS), 1, CR_L1_THREADS, &ka, sizeof(ka), fence) != 0)
-                    return fail("direct AQL queue: cr_level1_kernel: " + g_dq->why());
+                CK(launch_beside(reinterpret_cast<const void*>(l1), "cr_level1_kernel", (uint32_t)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS), 1, CR_L1_THREADS, &ka, sizeof(ka),
+                                 fence, Then::KEEP));
             } else {
                 hipLaunchKernelGGL(l1, dim3((unsigned)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS)), dim3(CR_L1_THREADS), 0, s->stream, s->L, a0.pk, a0.perm_tab, s->N,
                                    n_cr, s->cr_n1, s->cr_p1_cur);
@@ -1889,10 +1932,9 @@ static int finish_generation(bpm_sampler* s) {
         while (cnt > CR_FINAL_MAX) {
             const uint32_t nn = (cnt + WAVE - 1) / WAVE;
             double* dst = s->cr_p2[flip];
-            if (g_dq) {
+            if (d.dq) {
                 struct { const double* p1; uint32_t n1, n_cr, n2, _pad; double* p2; } ka{src, cnt, n_cr, nn, 0u, dst};
-                const bpm::DqKernel* k = g_dq->kernel(reinterpret_cast<const void*>(cr_mid_kernel));
-                if (!k || g_dq->launch(*k, nn, 1, WAVE, &ka, sizeof(ka), fence) != 0) return fail("direct AQL queue: cr_mid_kernel: " + g_dq->why());
+                CK(launch_beside(reinterpret_cast<const void*>(cr_mid_kernel), "cr_mid_kernel", nn, 1, WAVE, &ka, sizeof(ka), fence, Then::KEEP));
             } else {
                 hipLaunchKernelGGL(cr_mid_kernel, dim3(nn), dim3(WAVE), 0, s->stream, src, cnt, n_cr, nn, dst);
                 HIPCK(hipGetLastError());
@@ -1900,7 +1942,7 @@ static int finish_generation(bpm_sampler* s) {
             src = dst; cnt = nn; flip ^= 1;
         }
         static const bool no_defer = test_path("crnofold");
-        if (!level1_from_slots && cnt <= CR_FINAL_MAX && !g_call_last_gen && !no_defer) {
+        if (!level1_from_slots && cnt <= CR_FINAL_MAX && !d.call_last_gen && !no_defer) {
             // consumer-side fold: no dispatch -- the next generation's first update launch folds (prepare_generation), or cr_flush_pending
             s->cr_pending = true;
             s->cr_pend_src = src;
@@ -1958,18 +2000,14 @@ static unsigned long long push_timeout_ticks() {
 // one push_sync_kernel of rank s: on the library's own queue when the generation loop runs there, else on the sampler's stream
 static int launch_push_sync(bpm_sampler* s, unsigned long long seq, bool notify, bool wait) {
     const unsigned long long* ctab = s->tab_all + MAX_SEG;
-    if (g_dq) {
+    if (g_disp.dq) {
         struct { PushCtrl* mine; const unsigned long long* ctab; uint32_t world, me; unsigned long long seq; uint32_t nf, wf; unsigned long long to; } ka{
             s->ctrl, ctab, s->world, s->rank, seq, notify ? 1u : 0u, wait ? 1u : 0u, push_timeout_ticks()};
-        const bpm::DqKernel* k = g_dq->kernel(reinterpret_cast<const void*>(push_sync_kernel));
         // NO fences on this packet (the barrier bit orders it behind the update kernel, whose own packet released): the kernel reads and
         // writes nothing but the flags, with system-scope atomics that pass the caches; the update kernel that follows acquires.
         // (With acquire + release at system scope here as well a hand-over measured 10.0 us instead of 3.8 with agent-scope fences:
         // profiles/r03_push_barrier_cost.txt.)
-        if (!k || g_dq->launch(*k, 1, 1, WAVE, &ka, sizeof(ka), 0) != 0)
-            return fail("direct AQL queue: push_sync_kernel: " + g_dq->why());
-        g_dq_need_acquire = true;
-        return 0;
+        return launch_beside(reinterpret_cast<const void*>(push_sync_kernel), "push_sync_kernel", 1, 1, WAVE, &ka, sizeof(ka), 0, Then::ACQUIRE);
     }
     hipLaunchKernelGGL(push_sync_kernel, dim3(1), dim3(WAVE), 0, s->stream, s->ctrl, ctab, s->world, s->rank, seq, notify ? 1u : 0u, wait ? 1u : 0u,
                        push_timeout_ticks());
@@ -1980,11 +2018,11 @@ static int launch_push_sync(bpm_sampler* s, unsigned long long seq, bool notify,
 // A process per rank: one kernel announces and waits.  A local group (R handles of one process on one GPU, possibly sharing hardware
 // queues): all ranks announce, the host joins the streams, all ranks wait -- the waits then find their flags set, no kernel ever
 // spins on a kernel queued behind it.
-static inline void bind_rank_queue(bpm_sampler* s) { if (g_group_direct) g_dq = s->dq; }
+static inline void bind_rank_queue(bpm_sampler* s) { if (g_disp.group_direct) g_disp.dq = s->dq; }
 static int push_barrier(const Group& g) {
     for (int r = 0; r < g.R; ++r) g.h[r]->push_seq += 1;
     if (g.R == 1) return launch_push_sync(g.h[0], g.h[0]->push_seq, true, true);
-    if (g_group_direct) {          // every rank on a queue of its own: the kernels wait for each other across the queues
+    if (g_disp.group_direct) {          // every rank on a queue of its own: the kernels wait for each other across the queues
         for (int r = 0; r < g.R; ++r) { bind_rank_queue(g.h[r]); CK(launch_push_sync(g.h[r], g.h[r]->push_seq, true, true)); g.h[r]->dq->flush(); }
         return 0;
     }
@@ -2195,6 +2233,7 @@ static int exchange_replay(const Group& g, int ph) {
 // xmode: how the half generations' updates reach the other ranks: 0 dense all-gather, 1 accepted rows, 2 accept bytes + replay,
 // 3 pushed by their owners from inside the update kernel (then only the cross-rank barrier follows a half generation)
 static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLaunch fn) {
+    Dispatch& d = g_disp;
     const long long tp0 = g_host_timing ? now_ns() : 0;
     for (int r = 0; r < g.R; ++r) {
         g.h[r]->sparse_active = xmode == 1;
@@ -2219,17 +2258,17 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
                 bpm_sampler* s = g.h[r];
                 bind_rank_queue(s);
                 if (s->cur_args[ph].n_items > 0) {
-                    g_dq_release_this = g_dq && g_dq_call_last_gen && (ph == 1 || s->cur_args[1].n_items == 0);
-                    if (g_dq && s->timed_last_gen >= 0) {
+                    d.release_this = d.dq && d.dq_call_last_gen && (ph == 1 || s->cur_args[1].n_items == 0);
+                    if (d.dq && s->timed_last_gen >= 0) {
                         // direct mode: attaching a time stamp costs the host nothing -- the first and the last update dispatch of the call
-                        if (s->timed_want_first) { s->timed_want_first = false; g_dq_sig = 0; s->timed_l0 = g_timed_launches; }
-                        else if (s->timed_last_gen == s->t_abs && (ph == 1 || s->cur_args[1].n_items == 0)) { g_dq_sig = 1; s->timed_l1 = g_timed_launches; }
+                        if (s->timed_want_first) { s->timed_want_first = false; d.sig = 0; s->timed_l0 = d.timed_launches; }
+                        else if (s->timed_last_gen == s->t_abs && (ph == 1 || s->cur_args[1].n_items == 0)) { d.sig = 1; s->timed_l1 = d.timed_launches; }
                     } else if (s->timed_want_first && s->timed_skip > 0) {
                         --s->timed_skip;
                     } else if (s->timed_want_first) {
-                        s->timed_want_first = false; g_stop_event = s->ev0; s->timed_l0 = g_timed_launches;
+                        s->timed_want_first = false; d.stop_event = s->ev0; s->timed_l0 = d.timed_launches;
                     } else if (s->timed_last_gen == s->t_abs && (ph == 1 || s->cur_args[1].n_items == 0)) {
-                        g_stop_event = s->ev1; s->timed_l1 = g_timed_launches;
+                        d.stop_event = s->ev1; s->timed_l1 = d.timed_launches;
                     }
                     const long long tl0 = g_host_timing ? now_ns() : 0;
                     fn(s->cur_args[ph], s->stream);
@@ -2248,13 +2287,11 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
     if (g.h[0]->outlier_due) {
         // everything of the check, its cross-rank barriers included, runs on the HIP streams: queues drained before, streams after
         std::vector<StreamSection> secs;
-        for (int r = 0; r < (g_group_direct ? g.R : 1); ++r) { bind_rank_queue(g.h[r]); secs.emplace_back(g.h[r]); CK(secs.back().rc); }
-        bpm::DirectQueue* const dq_saved = g_dq;
-        const bool gd_saved = g_group_direct;
-        g_dq = nullptr; g_group_direct = false;
-        const int rc_out = group_outlier_check(g);
-        g_dq = dq_saved; g_group_direct = gd_saved;
-        CK(rc_out);
+        for (int r = 0; r < (d.group_direct ? g.R : 1); ++r) { bind_rank_queue(g.h[r]); secs.emplace_back(g.h[r]); CK(secs.back().rc); }
+        {
+            OnHipStream on_stream;
+            CK(group_outlier_check(g));
+        }
         for (auto& sec : secs) CK(sec.end());
     }
     return 0;
@@ -2263,70 +2300,6 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
 struct HostCkpt {
     int64_t k_gen, t_abs, hist_rows, rows_logical, w_rows;
 };
-
-#ifdef BPM_EXPERIMENT_XCD
-// EXPERIMENT (never the product): up to `want_gens` steady-state generations of a single-GPU sampler as ONE launch of xcd_resident_kernel -- the
-// host walks prepare_generation / finish_generation for every generation of the batch (a batch never crosses a table window), collects the two
-// argument blocks of each, copies them to the device and launches on the HIP stream (acquire + release around the one kernel).
-static int xcd_mode() { static const int m = getenv("BPM_XCD") ? atoi(getenv("BPM_XCD")) : 0; return m; }
-static bool xcd_eligible(const Group& g) {
-    bpm_sampler* s = g.h[0];
-    if (xcd_mode() == 0 || g.R != 1 || s->world != 1 || s->comm || s->trace_i32 || s->cfg.running_moments || s->cfg.outlier_every > 0) return false;
-    if (s->cfg.algo == BPM_ALGO_DREAM && s->cfg.burnin_gen > s->k_gen) return false;
-    if (s->cfg.algo == BPM_ALGO_DEMC && s->cfg.target_id == BPM_TARGET_BANANA_2D && s->shape.idx == 0) return true;
-    if (s->cfg.algo == BPM_ALGO_DREAM && s->cfg.target_id == BPM_TARGET_MIXTURE_PAIRS && s->shape.idx == 1 && s->cfg.del_pairs == 3 && s->cfg.n_cr == 3) return true;
-    return false;
-}
-static int xcd_batch(bpm_sampler* s, int64_t want_gens, int64_t* did) {
-    CK(leave_direct(s));
-    constexpr int MAX_PH = 2 * PERM_CHUNK;
-    if (!s->xcd_args) {
-        CK(dev_alloc(&s->xcd_args, (size_t)MAX_PH));
-        CK(dev_alloc(&s->xcd_ctl, 16));
-        HIPCK(hipMemsetAsync(s->xcd_ctl, 0, 16 * sizeof(uint32_t), s->stream));
-    }
-    bpm::DirectQueue* const dq_saved = g_dq;
-    g_dq = nullptr; g_wt_stores = false;
-    std::vector<PhaseArgs> host;
-    int64_t n = 0;
-    while (n < want_gens) {
-        CK(prepare_generation(s, want_gens - n));
-        for (int ph = 0; ph < 2; ++ph) if (s->cur_args[ph].n_items > 0) host.push_back(s->cur_args[ph]);
-        CK(finish_generation(s));
-        ++n;
-        if (s->t_abs >= s->tab_t0 + s->tab_K) break;          // the next generation belongs to the next window of the tables
-    }
-    g_dq = dq_saved;
-    const uint32_t want = 32u, xcc = (uint32_t)(xcd_mode() >> 4) & 7u;
-    const unsigned long long timeout = 50000000ull;          // 0.5 s of the 100 MHz clock
-    HIPCK(hipMemcpyAsync(s->xcd_args, host.data(), host.size() * sizeof(PhaseArgs), hipMemcpyHostToDevice, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                   // (host is a local vector)
-    HIPCK(hipMemsetAsync(s->xcd_ctl, 0, 3 * sizeof(uint32_t), s->stream));
-    if ((xcd_mode() & 15) == 2) {
-        hipLaunchKernelGGL(xcd_barrier_only_kernel, dim3(256), dim3(1024), 0, s->stream, (uint32_t)host.size(), s->xcd_ctl, want, xcc, timeout);
-    } else if (s->cfg.algo == BPM_ALGO_DEMC) {
-        hipLaunchKernelGGL((xcd_resident_kernel<ALGO_DEMC, TARGET_BANANA, 1, 2, 1>), dim3(256), dim3(1024), 0, s->stream, (const PhaseArgs*)s->xcd_args, (uint32_t)host.size(),
-                           s->xcd_ctl, want, xcc, timeout);
-    } else {
-        hipLaunchKernelGGL((xcd_resident_kernel<ALGO_DREAM, TARGET_MIXTURE, 4, 2, 3>), dim3(256), dim3(1024), 0, s->stream, (const PhaseArgs*)s->xcd_args, (uint32_t)host.size(),
-                           s->xcd_ctl, want, xcc, timeout);
-    }
-    HIPCK(hipGetLastError());
-    s->xcd_gens += n;
-    *did = n;
-    return 0;
-}
-static int xcd_check(bpm_sampler* s) {
-    if (!s->xcd_ctl) return 0;
-    uint32_t c[6];
-    HIPCK(hipMemcpyAsync(c, s->xcd_ctl, sizeof(c), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (c[3] != 0 || (c[2] != 32u && (xcd_mode() & 15) != 2))
-        return fail("XCD-resident experiment: the workers did not meet (registered " + std::to_string(c[0]) + " workgroups on the chosen XCD, workers " + std::to_string(c[2]) +
-                    ", error " + std::to_string(c[3]) + ", XCC ids seen mask " + std::to_string(c[4]) + "): results of this call are invalid");
-    return 0;
-}
-#endif
 
 // Does this group's generation loop go through the library's own AQL queue(s)?  A single GPU's sampler, or -- with the push exchange, where
 // nothing of the loop is a collective call -- a rank of a world; group_direct: the R ranks of a local group, each on a queue of its own.
@@ -2344,8 +2317,9 @@ static bool group_goes_direct(const Group& g, bool push, bool& group_direct) {
 static int run_generations_user(bpm_sampler* s, int64_t n_gens);      // (a host-callback sampler with a device likelihood: below, beside the host-callback core)
 // the update kernel compiled at run time around a caller's likelihood (bpm_sampler::user_fused_fn): the general instantiation's launch, from a module
 static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
-    bpm_sampler* s = g_user_cur;
-    if (!s || !s->user_fused_fn) { g_user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
+    Dispatch& d = g_disp;
+    bpm_sampler* s = d.user_cur;
+    if (!s || !s->user_fused_fn) { d.user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
     PhaseArgs ka = a;
     ka.tparams = s->user_params;                   // the caller's parameter block is the target's
     size_t sz = sizeof(ka);
@@ -2353,22 +2327,19 @@ static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
     static const bool no_hot = test_path("nohot");
     // burn-in: prepare_generation handed this launch the level-1 sums to write (cr_part1) only after phase_args_hot(a, true, plan, true) held for BOTH launches
     const bool adapt = a.cr_part1 != nullptr && s->user_fused_adapt != nullptr;
-    if (adapt) { ++g_crp_launched; if (a.cr_fold_part != nullptr) ++g_crfold_launched; }
+    if (adapt) { ++d.crp_launched; if (a.cr_fold_part != nullptr) ++d.crfold_launched; }
     const unsigned block = adapt ? s->user_fused_block_adapt : s->user_fused_block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
     // (the steady-state instantiation was compiled for update records exactly when this sampler builds them: HOT 1 / HOT 2)
     const bool hot = !adapt && !no_hot && s->user_fused_hot && (a.rec_tab != nullptr) == s->plan_on && phase_args_hot(a, s->cfg.algo == BPM_ALGO_DREAM, a.rec_tab != nullptr, false);
-    if (g_dq) {      // the library's own queue (launch_packed's packet: the module's kernels take the argument block alone, no preloaded leading arguments)
-        const bpm::DqKernel* k = g_dq->kernel_by_name(s->user_fused_names[adapt ? 2 : (hot ? 1 : 0)]);
-        const int sig = g_dq_sig; g_dq_sig = -1;
-        int fence = g_dq_update_fence;
-        if (g_dq_need_acquire) { fence |= bpm::DirectQueue::ACQUIRE; g_dq_need_acquire = false; }
-        if (g_dq_release_this) { fence |= bpm::DirectQueue::RELEASE; g_dq_release_this = false; }
-        if (!k || g_dq->launch(*k, grid, 1, block, &ka, sizeof(ka), fence, sig) != 0) g_dq_error = true;
-        ++g_timed_launches; ++g_n_direct;
+    if (d.dq) {      // the library's own queue (launch_packed's packet: the module's kernels take the argument block alone, no preloaded leading arguments)
+        const bpm::DqKernel* k = d.dq->kernel_by_name(s->user_fused_names[adapt ? 2 : (hot ? 1 : 0)]);
+        const UpdatePacket p = take_update_packet(d);
+        if (!k || d.dq->launch(*k, grid, 1, block, &ka, sizeof(ka), p.fence, p.sig) != 0) d.dq_error = true;
+        ++d.timed_launches; ++d.n_direct;
         return;
     }
-    (void)hipExtModuleLaunchKernel(adapt ? s->user_fused_adapt : (hot ? s->user_fused_hot : s->user_fused_fn), grid * block, 1, 1, block, 1, 1, 0, st, nullptr, extra, nullptr, take_stop_event(), 0);
-    ++g_timed_launches; ++g_n_stream;
+    (void)hipExtModuleLaunchKernel(adapt ? s->user_fused_adapt : (hot ? s->user_fused_hot : s->user_fused_fn), grid * block, 1, 1, block, 1, 1, 0, st, nullptr, extra, nullptr, take_stop_event(d), 0);
+    ++d.timed_launches; ++d.n_stream;
 }
 static int run_generations(const Group& g, int64_t n_gens) {
     bpm_sampler* s0 = g.h[0];
@@ -2377,8 +2348,6 @@ static int run_generations(const Group& g, int64_t n_gens) {
     const bool user_fused = s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->user_fused_fn != nullptr && g.R == 1;
     if (s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->user_fn && g.R == 1 && !user_fused) return run_generations_user(s0, n_gens);
     if (user_fused && s0->world > 1 && !s0->comm) return fail("bpm_step: a host-callback sampler of a world needs an RCCL communicator (create it with a unique id)");
-    g_user_cur = user_fused ? s0 : nullptr;
-    struct UserCurReset { ~UserCurReset() { g_user_cur = nullptr; } } user_cur_reset;      // (prepare_generation asks g_user_cur who drives a host-callback sampler)
     PhaseLaunch fn = user_fused ? launch_user_fused : pick_fused(s0);
     if (!fn) return fail("bpm_step: host-callback target must be driven with bpm_propose / bpm_commit (or give it a device likelihood: bpm_set_device_likelihood)");
     const bool dream = s0->cfg.algo == BPM_ALGO_DREAM;
@@ -2388,15 +2357,9 @@ static int run_generations(const Group& g, int64_t n_gens) {
     bool push_entered = false;
     while (done < n_gens) {
         const bool adapting = dream && s0->cfg.burnin_gen > s0->k_gen;          // dream.py:92: CR statistics travel in the dense block
-#ifdef BPM_EXPERIMENT_XCD
-        if (xcd_eligible(g)) {
-            int64_t did = 0;
-            CK(xcd_batch(s0, n_gens - done, &did));
-            done += did;
-            if (done >= n_gens) CK(xcd_check(s0));
-            continue;
-        }
-#endif
+        // one generation, or one chunk of generations under the sparse exchange (prepare_generation asks Dispatch::user_cur who drives a host-callback sampler)
+        DispatchScope scope(user_fused ? s0 : nullptr);
+        Dispatch& d = scope.d;
         if (push || !(s0->sparse_enabled && !adapting)) {
             // (HIP-graph replay of steady-state chunks was built and measured in round 1 -- 13.1 vs 12.5 us per generation at cfg2 -- and
             // removed in round 3: DESIGN.md section 5 item 6)
@@ -2414,29 +2377,26 @@ static int run_generations(const Group& g, int64_t n_gens) {
                 if (direct && !s->dq_active) {
                     CK(wait_stream(s->stream));                         // what the stream still holds (burn-in, table builds) comes first
                     s->dq_active = true;
-                    g_dq_need_acquire = true;
+                    d.mark_acquire(true);
                 } else if (!direct && s->dq_active) {
                     CK(leave_direct(s));
                 }
             }
-            g_group_direct = group_direct;
-            g_dq = direct ? s0->dq : nullptr;
-            g_dq_error = false;
+            d.group_direct = group_direct;
+            d.dq = direct ? s0->dq : nullptr;
             // (half a generation rewrites at most N/2 + 1 rows)
             // Release-less packets + write-through stores in every generation, burn-in included, at every size: with ONE 16-byte sc1 store
             // per lane (store_row_wt16) the write-through form beats the end-of-kernel release everywhere it was measured -- round 2's two
             // 8-byte atomic stores lost above 4 MiB per half generation and in burn-in, hence its size rule and the fenced burn-in
             // (profiles/r03_write_through_16B.txt: cfg2 burn-in 23.1 -> 21.9 us, cfg5 57.6 -> 55.9, cfg5 burn-in 90 -> 81, N = 65536 x d = 100 70.0 -> 68.7).
             // BPM_TEST_PATHS=wt8 selects the 8-byte form, bpm_set_launch_path(h, 1, 3) the fenced packets with plain stores.
-            const bool plain_stores = false;
-            g_dq_update_fence = plain_stores ? (int)bpm::DirectQueue::FENCED : s0->dq_fence;
-            // push exchange: every update packet acquires and releases at SYSTEM scope (rows go to and come from other agents)
+            d.update_fence = s0->dq_fence;
             // push exchange: system scope -- every update packet acquires and releases at SYSTEM scope, plain stores into the own replica (rows
             // go to and come from other agents); agent scope -- the single-GPU form: acquire only, write-through stores into the own replica
-            if (push && !s0->push_agent_scope) g_dq_update_fence = bpm::DirectQueue::FENCED | bpm::DirectQueue::SYSTEM;
-            g_wt_stores = !plain_stores && !s0->coherent && direct && !(g_dq_update_fence & bpm::DirectQueue::RELEASE);
-            g_dq_call_last_gen = direct && done == n_gens - 1;
-            g_call_last_gen = done == n_gens - 1;
+            if (push && !s0->push_agent_scope) d.update_fence = bpm::DirectQueue::FENCED | bpm::DirectQueue::SYSTEM;
+            d.wt_stores = !s0->coherent && direct && !(d.update_fence & bpm::DirectQueue::RELEASE);
+            d.dq_call_last_gen = direct && done == n_gens - 1;
+            d.call_last_gen = done == n_gens - 1;
             if (push && !push_entered) {
                 // entry barrier of the call: a peer's first update kernel may push into THIS replica only after this rank has finished
                 // whatever its host did to the replica before the call (bpm_set_state, a warm start, ...) -- and vice versa
@@ -2445,18 +2405,15 @@ static int run_generations(const Group& g, int64_t n_gens) {
                 push_entered = true;
             }
             const int rc_gen = group_generation(g, n_gens - done, push ? 3 : (replay ? 2 : 0), fn);
-            g_wt_stores = false; g_dq_call_last_gen = false; g_dq_release_this = false; g_call_last_gen = false;
-            g_group_direct = false;
             if (direct) {
-                g_dq = nullptr;
                 for (int r = 0; r < (group_direct ? g.R : 1); ++r) {
                     bpm_sampler* s = g.h[r];
                     s->dq->flush();                                     // one doorbell per generation
-                    if (g_dq_error || s->dq->failed()) return fail("direct AQL queue: " + (s->dq->why().empty() ? std::string("update kernel not found among the loaded code objects") : s->dq->why()));
+                    if (d.dq_error || s->dq->failed()) return fail("direct AQL queue: " + (s->dq->why().empty() ? std::string("update kernel not found among the loaded code objects") : s->dq->why()));
                 }
             }
             CK(rc_gen);
-            if (g_user_launch_failed) { g_user_launch_failed = false; return fail("bpm_step: the update kernel compiled around the HIP-source likelihood was not launched (module gone)"); }
+            if (d.user_launch_failed) return fail("bpm_step: the update kernel compiled around the HIP-source likelihood was not launched (module gone)");
             if (push) for (int r = 0; r < g.R; ++r) g.h[r]->n_push_gens += 1;
             else if (replay) for (int r = 0; r < g.R; ++r) g.h[r]->n_replay_gens += 1;
             ++done;
@@ -2718,12 +2675,9 @@ extern "C" int bpm_push_connect(bpm_handle_t s, const void* blobs) {
 static int launch_arena_probe(bpm_sampler* s, int mode, int form, unsigned long long seed, double* save, int fence) {
     ProbeGeo geo{s->L.blk, s->n_local, s->ld, (s->om && s->off_om) ? 2u * s->n_local : 0u, s->world, s->rank, 2u * s->ld + 8u};
     unsigned long long* bad = &s->ctrl->arena_bad[form];
-    if (g_dq) {
+    if (g_disp.dq) {
         struct { const unsigned long long* tab; ProbeGeo g; int mode; unsigned long long seed; double* save; unsigned long long* bad; } ka{s->tab_all, geo, mode, seed, save, bad};
-        const bpm::DqKernel* k = g_dq->kernel(reinterpret_cast<const void*>(push_arena_probe_kernel));
-        if (!k || g_dq->launch(*k, PROBE_REGIONS, s->world, WAVE, &ka, sizeof(ka), fence) != 0) return fail("direct AQL queue: push_arena_probe_kernel: " + g_dq->why());
-        g_dq_need_acquire = true;
-        return 0;
+        return launch_beside(reinterpret_cast<const void*>(push_arena_probe_kernel), "push_arena_probe_kernel", PROBE_REGIONS, s->world, WAVE, &ka, sizeof(ka), fence, Then::ACQUIRE);
     }
     hipLaunchKernelGGL(push_arena_probe_kernel, dim3(PROBE_REGIONS, s->world), dim3(WAVE), 0, s->stream, (const unsigned long long*)s->tab_all, geo, mode, seed, save, bad);
     HIPCK(hipGetLastError());
@@ -2778,27 +2732,29 @@ extern "C" int bpm_push_selftest(bpm_handle_t* handles, int32_t R, int32_t* ok) 
         bpm_sampler* s = handles[r];
         if (direct && !s->dq_active) { CK(wait_stream(s->stream)); s->dq_active = true; }
     }
-    g_group_direct = group_direct;
-    g_dq = direct ? handles[0]->dq : nullptr;
-    g_dq_need_acquire = true;
     int rc = 0;
-    for (int form = 0; form < 2 && rc == 0; ++form) {
-        // form 0: acquire + release at system scope around the writer (what the HSA memory model asks for between agents); form 1: the single-GPU
-        // form, acquire only at agent scope -- the probe rows themselves are system-scope write-through stores either way, as the pushed rows are
-        const int f_read = form == 0 ? (bpm::DirectQueue::ACQUIRE | bpm::DirectQueue::SYSTEM) : bpm::DirectQueue::ACQUIRE;
-        const int f_write = form == 0 ? (bpm::DirectQueue::FENCED | bpm::DirectQueue::SYSTEM) : bpm::DirectQueue::ACQUIRE;
-        for (int mode = 0; mode < 3 && rc == 0; ++mode) {
-            rc = push_barrier(g);
-            for (int r = 0; r < R && rc == 0; ++r) {
-                bind_rank_queue(handles[r]);
-                rc = launch_arena_probe(handles[r], mode, form, seed + 16u * (unsigned)form, save[(size_t)r], mode == 1 ? f_write : f_read);
-                if (g_dq) g_dq->flush();
+    {   // the probes go where the update kernels would: the dispatch state of a generation, for the length of this block
+        DispatchScope scope;
+        Dispatch& d = scope.d;
+        d.group_direct = group_direct;
+        d.dq = direct ? handles[0]->dq : nullptr;
+        d.mark_acquire(true);
+        for (int form = 0; form < 2 && rc == 0; ++form) {
+            // form 0: acquire + release at system scope around the writer (what the HSA memory model asks for between agents); form 1: the single-GPU
+            // form, acquire only at agent scope -- the probe rows themselves are system-scope write-through stores either way, as the pushed rows are
+            const int f_read = form == 0 ? (bpm::DirectQueue::ACQUIRE | bpm::DirectQueue::SYSTEM) : bpm::DirectQueue::ACQUIRE;
+            const int f_write = form == 0 ? (bpm::DirectQueue::FENCED | bpm::DirectQueue::SYSTEM) : bpm::DirectQueue::ACQUIRE;
+            for (int mode = 0; mode < 3 && rc == 0; ++mode) {
+                rc = push_barrier(g);
+                for (int r = 0; r < R && rc == 0; ++r) {
+                    bind_rank_queue(handles[r]);
+                    rc = launch_arena_probe(handles[r], mode, form, seed + 16u * (unsigned)form, save[(size_t)r], mode == 1 ? f_write : f_read);
+                    if (d.dq) d.dq->flush();
+                }
             }
+            if (rc == 0) rc = push_barrier(g);      // nobody goes on (to the next form, to a generation) while a peer still verifies
         }
-        if (rc == 0) rc = push_barrier(g);      // nobody goes on (to the next form, to a generation) while a peer still verifies
     }
-    g_group_direct = false;
-    g_dq = nullptr;
     for (int r = 0; r < R; ++r) { const int rl = leave_direct(handles[r]); if (rc == 0) rc = rl; }
     CK(rc);
     CK(group_sync(g));
@@ -2820,8 +2776,8 @@ extern "C" int bpm_get_launch_stats(bpm_handle_t s, int64_t* out) {
     CK(check_handle_keep_direct(s));
     if (!out) return fail("bpm_get_launch_stats: null argument");
     out[0] = s->dq != nullptr ? 1 : 0;
-    out[1] = g_n_direct;
-    out[2] = g_n_stream;
+    out[1] = g_disp.n_direct;
+    out[2] = g_disp.n_stream;
     out[3] = s->dq_active ? 1 : 0;
     out[4] = s->coherent ? 1 : 0;
     out[5] = s->dq_fence;
@@ -2875,9 +2831,7 @@ extern "C" int bpm_step_timed(bpm_handle_t s, int64_t n_gens, float* elapsed_ms,
     const long long tt0 = g_host_timing ? now_ns() : 0;
     const int rc = bpm_step(s, n_gens);
     s->timed_want_first = false;
-    s->timed_last_gen = -1;
-    g_stop_event = nullptr;
-    g_dq_sig = -1;
+    s->timed_last_gen = -1;      // (the riders of the timed launches went with run_generations's scopes)
     CK(rc);
     s->timed_direct = s->dq_active;
     if (s->dq_active) { if (s->dq->drain() != 0) return fail("direct AQL queue: " + s->dq->why()); }     // (the sampler stays in direct mode: the next call goes on)

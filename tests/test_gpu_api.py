@@ -1220,7 +1220,7 @@ def test_many_ranks_sorted_records_and_fallback(R):
 def test_direct_queue_equals_stream_launches(case):
     """The generation loop of a single-GPU sampler is dispatched by AQL packets the library writes into its own queue
     (bipymc_amd/csrc/aql_queue.h).  In the steady state those packets carry the acquire fence only and the update kernel writes what
-    its successor reads with agent-scope stores (sampler.hip: g_dq_update_fence); launching the same kernels on the HIP stream, or
+    its successor reads with agent-scope stores (sampler.hip: Dispatch::update_fence); launching the same kernels on the HIP stream, or
     through the queue with a HIP stream's acquire + release on every packet, must give the same bits: state, ln-like, the whole
     history, CR statistics, accept counters.  The runs cross a table window (64 generations), grow the history while the queue is
     busy (no reservation), pass through burn-in with the outlier check (HIP-stream sections between drains) and call the timed entry
@@ -1380,6 +1380,64 @@ def test_direct_queue_interleaved_with_other_entry_points():
     assert len(outs[0]) == len(outs[1])
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
+
+
+def test_two_samplers_of_one_thread_on_different_launch_paths_do_not_share_dispatch_state():
+    """What the launch functions tell each other about where the current launches go is held per THREAD (sampler.hip: struct Dispatch), not per
+    handle: two samplers alive in one thread, A on the library's own queue and B on HIP-stream launches, stepped alternately in short calls
+    (across the end of burn-in, with a timed call of A between two calls of B), must each end exactly where the same sampler ends when it
+    runs alone in the same call pattern -- state, ln-likes, history, p_cr bit for bit -- and every call's launches must be counted on the
+    path of the sampler that made them."""
+    from bipymc_amd import _lib as L
+    from bipymc_amd.engine import HipEngine
+    from bipymc_amd.utils import d100_gauss
+    tid, tp, d = d100_gauss.Gauss_100D(dim=16)._bpm_target_spec()
+    N, calls = 256, (1, 2, 5, 1, 20, 11)
+    X0 = {"A": np.random.RandomState(3).normal(size=(N, d)) + 0.5, "B": np.random.RandomState(4).normal(size=(N, d)) - 0.5}
+
+    def make(name):
+        e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed={"A": 31, "B": 32}[name], burnin_gen=5, n_cr_gen=3)
+        if name == "B":
+            e.set_launch_path(False)
+        e.set_state(X0[name])
+        e.begin_run()
+        return e
+
+    def call(e, name, n, timed=False):          # one step call, its launches counted on the sampler's own path and on no other
+        before = e.launch_stats()
+        if timed:
+            e.step_timed(n)
+        else:
+            e.step(n)
+        after = e.launch_stats()
+        mine, other = ("direct", "stream") if name == "A" else ("stream", "direct")
+        assert after[mine] - before[mine] > 0 and after[other] == before[other], (name, n, before, after)
+
+    def result(e):
+        st = e.stats()
+        return [e.get_state(), e.get_loglike(), e.get_history(0, e.history_rows()), np.asarray(st["p_cr"]), np.array([st["k_gen"], e.history_rows()], dtype=float)]
+
+    def pattern(engines):                       # engines: {"A": ..., "B": ...} or one of the two alone
+        for n in calls:
+            for name in ("A", "B"):
+                if name in engines:
+                    call(engines[name], name, n)
+            if n == 5 and "A" in engines:       # B's call of 5 generations before, B's call of 1 generation after
+                call(engines["A"], "A", 3, timed=True)
+
+    both = {"A": make("A"), "B": make("B")}
+    pattern(both)
+    together = {name: result(e) for name, e in both.items()}
+    for e in both.values():
+        e.close()
+    for name in ("A", "B"):
+        e = make(name)
+        pattern({name: e})
+        alone = result(e)
+        e.close()
+        assert alone[4][0] == sum(calls) + (3 if name == "A" else 0)
+        for x, y in zip(together[name], alone):
+            assert np.array_equal(x, y), name
 
 
 @pytest.mark.parametrize("seq_seed", [77, 1234])
