@@ -121,6 +121,7 @@ TEST_SIGNATURES = {
     "bpm_get_trace": (C.c_int, [_H, _ip, _dp, _u8p]),
     "bpm_debug_destroy_plan": (C.c_int, [C.c_int32, C.c_int32]),
     "bpm_debug_fail_queue": (C.c_int, [_H, C.c_int32]),
+    "bpm_debug_kernarg_layout": (C.c_int, [C.c_int32, _P(C.c_char_p), _ip, _P(C.c_int64), _P(C.c_int64)]),
     "bpm_debug_queue_pad": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int64)]),
     "bpm_debug_coherence_probe": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int64)]),
     "bpm_selftest_philox": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, _u32p, _u32p]),

@@ -28,6 +28,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bipymc_hip.h"
@@ -189,7 +190,7 @@ struct Dispatch {
     bool call_last_gen = false;            // the generation being run is the last one of the bpm_step call (its fold is dispatched) ...
     bool dq_call_last_gen = false;         // ... and runs in direct mode: its last update dispatch carries the release (release_this)
 
-    // ---- one-shot: riders on the NEXT update launch, consumed by it (take_update_packet / take_stop_event)
+    // ---- one-shot: riders on the NEXT update launch, consumed by it (update_packet / take_stop_event)
     // bpm_step_timed: the launch carries this event as its stop event (hipExtLaunchKernelGGL binds it to the dispatch itself: its time stamp
     // is the kernel's end, and no marker packet enters the queue) ...
     hipEvent_t stop_event = nullptr;
@@ -244,29 +245,49 @@ struct OnHipStream {
     OnHipStream(const OnHipStream&) = delete;
     OnHipStream& operator=(const OnHipStream&) = delete;
 };
-// The one consumer of the riders of an update packet on the library's own queue: its fences and its timing signal, what it used cleared.
-struct UpdatePacket { int fence, sig; };
-static inline UpdatePacket take_update_packet(Dispatch& d) {
-    UpdatePacket p{d.update_fence, d.sig};
-    d.sig = -1;
-    if (d.need_acquire) { p.fence |= bpm::DirectQueue::ACQUIRE; d.need_acquire = false; }
-    if (d.release_this) { p.fence |= bpm::DirectQueue::RELEASE; d.release_this = false; }
-    return p;
-}
-// ... and of the rider of an update launch on the HIP stream
+// The one consumer of the rider of an update launch on the HIP stream (update_packet, below, is that of the riders of a packet)
 static inline hipEvent_t take_stop_event(Dispatch& d) {
     hipEvent_t e = d.stop_event;
     d.stop_event = nullptr;
     return e;
 }
-// A kernel BESIDE the update kernels (table builds, the CR reduction, the running-moment sums, the push barrier, the arena probe) as a packet on
-// the queue of the generation being run (g_disp.dq, not null).  `ka` is its kernel-argument block as the device reads it.
+// The kernel-argument block of a kernel with parameters P... as the device reads it: every parameter at the next offset aligned to its own
+// alignment; the block ends at the last parameter's end rounded up to the largest alignment among them.
+template <class... P>
+struct KernargLayout {
+    static constexpr size_t n = sizeof...(P);
+    size_t off[n] = {}, size[n] = {sizeof(P)...}, bytes = 0;
+    constexpr KernargLayout() {
+        constexpr size_t al[n] = {alignof(P)...};
+        size_t end = 0, al_max = 1;
+        for (size_t i = 0; i < n; ++i) {
+            off[i] = (end + al[i] - 1) / al[i] * al[i];
+            end = off[i] + size[i];
+            al_max = std::max(al_max, al[i]);
+        }
+        bytes = (end + al_max - 1) / al_max * al_max;
+    }
+};
+// A kernel BESIDE the update kernels (table builds, the CR reduction, the running-moment sums, the push barrier, the arena probe): a packet on the
+// queue of the generation being run where one is bound (g_disp.dq), else a launch on `stream`.  The arguments are converted to the kernel's own
+// parameter types on either path, and the packet's argument block is laid out from those types: no hand-made mirror of a signature to keep in step.
+// (What must stay on the HIP stream WHILE a queue is bound -- see build_window -- launches there itself and never comes here.)
 // then: what the launch means for the next update packet -- it must acquire, need not (the CR fold: see need_acquire), or no change.
 enum class Then { KEEP, ACQUIRE, NO_ACQUIRE };
-static int launch_beside(const void* kernel, const char* name, uint32_t grid_x, uint32_t grid_y, uint32_t block, const void* ka, size_t nbytes, int fence, Then then) {
+template <class... P>
+static int launch_side(hipStream_t stream, void (*kernel)(P...), const char* name, dim3 grid, uint32_t block, int fence, Then then, std::common_type_t<P>... args) {
     Dispatch& d = g_disp;
-    const bpm::DqKernel* k = d.dq->kernel(kernel);
-    if (!k || d.dq->launch(*k, grid_x, grid_y, block, ka, nbytes, fence) != 0) return fail(std::string("direct AQL queue: ") + name + ": " + d.dq->why());
+    if (!d.dq) {
+        hipLaunchKernelGGL(kernel, grid, dim3(block), 0, stream, args...);
+        HIPCK(hipGetLastError());
+        return 0;
+    }
+    constexpr KernargLayout<P...> lay;
+    alignas(16) unsigned char ka[lay.bytes] = {};
+    size_t i = 0;
+    ((void)std::memcpy(ka + lay.off[i++], &args, sizeof(P)), ...);
+    const bpm::DqKernel* k = d.dq->kernel(reinterpret_cast<const void*>(kernel));
+    if (!k || d.dq->launch(*k, grid.x, grid.y, block, ka, lay.bytes, fence) != 0) return fail(std::string("direct AQL queue: ") + name + ": " + d.dq->why());
     if (then != Then::KEEP) d.mark_acquire(then == Then::ACQUIRE);
     return 0;
 }
@@ -282,32 +303,33 @@ struct FusedKernarg {
     PhaseArgs a;
 };
 static_assert(offsetof(FusedKernarg, a) == 24 && sizeof(FusedKernarg) == 24 + sizeof(PhaseArgs), "kernarg layout of phase_fused_kernel");
+// One update-kernel dispatch from a ready argument block (a FusedKernarg, or the bare PhaseArgs a run-time module's kernels take) and the counters
+// it moves: as a packet on the library's own queue (k: null = the kernel was not found), the one consumer of a packet's riders -- its fences and
+// its timing signal, what it used cleared ...
+static inline void update_packet(Dispatch& d, const bpm::DqKernel* k, unsigned grid, unsigned block, const void* ka, size_t nbytes) {
+    int fence = d.update_fence;
+    const int sig = d.sig;
+    d.sig = -1;
+    if (d.need_acquire) { fence |= bpm::DirectQueue::ACQUIRE; d.need_acquire = false; }
+    if (d.release_this) { fence |= bpm::DirectQueue::RELEASE; d.release_this = false; }
+    if (!k || d.dq->launch(*k, grid, 1, block, ka, nbytes, fence, sig) != 0) d.dq_error = true;
+    ++d.timed_launches; ++d.n_direct;
+}
+// ... or from a module function on the HIP stream
+static inline void update_on_stream(Dispatch& d, hipFunction_t fn, unsigned grid, unsigned block, void* ka, size_t nbytes, hipStream_t s) {
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
+    (void)hipExtModuleLaunchKernel(fn, grid * block, 1, 1, block, 1, 1, 0, s, nullptr, extra, nullptr, take_stop_event(d), 0);
+    ++d.timed_launches; ++d.n_stream;
+}
 template <class K>
 static inline void launch_packed(K kernel, hipFunction_t& fn, const PhaseArgs& a, unsigned grid, unsigned block, hipStream_t s) {
     Dispatch& d = g_disp;
-    if (d.dq) {
-        FusedKernarg ka;
-        ka.pl_plan = a.rec_tab; ka.pl_upd_off = a.rec_off; ka.pl_n_items = a.n_items; ka.pl_mode = a.mode; ka._pad = 0u;
-        ka.a = a;
-        const bpm::DqKernel* k = d.dq->kernel(reinterpret_cast<const void*>(kernel));
-        const UpdatePacket p = take_update_packet(d);
-        if (!k || d.dq->launch(*k, grid, 1, block, &ka, sizeof(ka), p.fence, p.sig) != 0) d.dq_error = true;
-        ++d.timed_launches; ++d.n_direct;
-        return;
-    }
-    ++d.n_stream;
+    FusedKernarg ka{a.rec_tab, a.rec_off, a.n_items, a.mode, 0u, a};
+    if (d.dq) return update_packet(d, d.dq->kernel(reinterpret_cast<const void*>(kernel)), grid, block, &ka, sizeof(ka));
     if (!fn) { if (hipGetFuncBySymbol(&fn, reinterpret_cast<const void*>(kernel)) != hipSuccess) { (void)hipGetLastError(); fn = nullptr; } }
-    if (fn) {
-        FusedKernarg ka;
-        ka.pl_plan = a.rec_tab; ka.pl_upd_off = a.rec_off; ka.pl_n_items = a.n_items; ka.pl_mode = a.mode; ka._pad = 0u;
-        ka.a = a;
-        size_t sz = sizeof(ka);
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        (void)hipExtModuleLaunchKernel(fn, grid * block, 1, 1, block, 1, 1, 0, s, nullptr, extra, nullptr, take_stop_event(d), 0);
-    } else {
-        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, nullptr, take_stop_event(d), 0, a.rec_tab, a.rec_off, a.n_items, a.mode, a);
-    }
-    ++d.timed_launches;
+    if (fn) return update_on_stream(d, fn, grid, block, &ka, sizeof(ka), s);
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, nullptr, take_stop_event(d), 0, a.rec_tab, a.rec_off, a.n_items, a.mode, a);
+    ++d.timed_launches; ++d.n_stream;
 }
 template <int ALGO, int T, int NP, int LPC, int DPL, int HOT>
 static void launch_hot(const PhaseArgs& a, hipStream_t s) {
@@ -1005,19 +1027,10 @@ static int push_gen_sums(bpm_sampler* s, int64_t row, const double* src = nullpt
     if (!s->cfg.running_moments) return 0;
     const double* Xl = src ? src : s->G + (uint64_t)s->rank * s->L.blk;
     double* out = s->gen_sums + (size_t)row * 2 * s->ld;
-    if (g_disp.dq) {
-        struct { const double* H; uint64_t lo, hi; uint32_t ld, _pad; const double* shift; double* part; } pa{Xl, 0, s->n_local, s->ld, 0u, s->gs_shift, s->gs_part};
-        struct { const double* part; uint32_t nb, ld; double* out; } fa{s->gs_part, s->gs_nb, s->ld, out};
-        // (reads rows that update kernels wrote, possibly with agent-scope stores behind release-less packets: acquire; writes what only
-        // bpm_reduce_moments reads, behind a drain: plain stores, release left to the drain's fence kernel)
-        CK(launch_beside(reinterpret_cast<const void*>(moments_partial_kernel), "running-moment kernels", s->gs_nb, 1, MOM_THREADS, &pa, sizeof(pa), bpm::DirectQueue::FENCED, Then::KEEP));
-        return launch_beside(reinterpret_cast<const void*>(moments_final_kernel), "running-moment kernels", s->ld, 1, MOM_THREADS, &fa, sizeof(fa), bpm::DirectQueue::FENCED, Then::ACQUIRE);
-    }
-    hipLaunchKernelGGL(moments_partial_kernel, dim3(s->gs_nb), dim3(MOM_THREADS), 0, s->stream, Xl, (uint64_t)0, (uint64_t)s->n_local, s->ld,
-                       (const double*)s->gs_shift, s->gs_part);
-    hipLaunchKernelGGL(moments_final_kernel, dim3(s->ld), dim3(MOM_THREADS), 0, s->stream, (const double*)s->gs_part, s->gs_nb, s->ld, out);
-    HIPCK(hipGetLastError());
-    return 0;
+    // (on the queue: reads rows that update kernels wrote, possibly with agent-scope stores behind release-less packets: acquire; writes what only
+    // bpm_reduce_moments reads, behind a drain: plain stores, release left to the drain's fence kernel)
+    CK(launch_side(s->stream, moments_partial_kernel, "running-moment kernels", dim3(s->gs_nb), MOM_THREADS, bpm::DirectQueue::FENCED, Then::KEEP, Xl, 0, s->n_local, s->ld, s->gs_shift, s->gs_part));
+    return launch_side(s->stream, moments_final_kernel, "running-moment kernels", dim3(s->ld), MOM_THREADS, bpm::DirectQueue::FENCED, Then::ACQUIRE, s->gs_part, s->gs_nb, s->ld, out);
 }
 
 // after the state matrix was (re)initialised: history := [state], moments reset
@@ -1601,15 +1614,11 @@ static int build_window(bpm_sampler* s, int b, int64_t W, int shuffle) {
     if (g_disp.dq && !B.sidx) {
         // direct mode, records by position: the same two kernels as packets on the library's queue, in order with
         // the update kernels around them
-        struct { PermKeys keys; uint32_t n_gens, N; uint32_t* tab; uint32_t* inv; } pa{keys, (uint32_t)K, s->N, B.perm, inv_out};
-        static_assert(offsetof(decltype(pa), tab) == sizeof(PermKeys) + 8, "kernarg layout of perm_table_kernel");
-        CK(launch_beside(reinterpret_cast<const void*>(perm_table_kernel), "perm_table_kernel", (uint32_t)((n + 255) / 256), 1, 256, &pa, sizeof(pa), bpm::DirectQueue::FENCED, Then::KEEP));
+        CK(launch_side(bs, perm_table_kernel, "perm_table_kernel", dim3((uint32_t)((n + 255) / 256)), 256, bpm::DirectQueue::FENCED, Then::KEEP, keys, K, s->N, B.perm, inv_out));
         if (B.plan) {
-            struct { PlanParams P; const uint32_t* tab; uint32_t* plan; const uint32_t* sidx; } qa{
-                PlanParams{s->cfg.seed, (uint64_t)t0, (uint32_t)K, s->N, s->cfg.algo == BPM_ALGO_DREAM ? (uint32_t)s->cfg.del_pairs : 1u,
-                           (s->cfg.algo == BPM_ALGO_DEMC && s->cfg.p_snooker > 0.0) ? 1u : 0u, 0u, 0u},
-                B.perm, B.plan, B.sidx};
-            CK(launch_beside(reinterpret_cast<const void*>(plan_kernel), "plan_kernel", (uint32_t)((n + 255) / 256), 1, 256, &qa, sizeof(qa), bpm::DirectQueue::FENCED, Then::KEEP));
+            const PlanParams pp{s->cfg.seed, (uint64_t)t0, (uint32_t)K, s->N, s->cfg.algo == BPM_ALGO_DREAM ? (uint32_t)s->cfg.del_pairs : 1u,
+                                (s->cfg.algo == BPM_ALGO_DEMC && s->cfg.p_snooker > 0.0) ? 1u : 0u, 0u, 0u};
+            CK(launch_side(bs, plan_kernel, "plan_kernel", dim3((uint32_t)((n + 255) / 256)), 256, bpm::DirectQueue::FENCED, Then::KEEP, pp, B.perm, B.plan, B.sidx));
         }
         B.W = W;
         B.shuffle = shuffle;
@@ -1690,14 +1699,7 @@ static int launch_cr_final(bpm_sampler* s, const double* src, uint32_t cnt) {
     typedef void (*FinalK)(const double*, const double*, uint32_t, uint32_t, double*);
     const uint32_t rounds = (cnt + WAVE - 1) / WAVE;
     const FinalK kfn = rounds <= 1 ? cr_final_kernel<1> : (rounds <= 2 ? cr_final_kernel<2> : (rounds <= 4 ? cr_final_kernel<4> : cr_final_kernel<8>));
-    if (g_disp.dq) {
-        struct { const double* tot; const double* part; uint32_t nb, n_cr; double* cr_state; } fa{s->cr_state, src, cnt, n_cr, s->cr_state};
-        CK(launch_beside(reinterpret_cast<const void*>(kfn), "cr_final_kernel", 1, 1, WAVE, &fa, sizeof(fa), fence, Then::NO_ACQUIRE));
-    } else {
-        hipLaunchKernelGGL(kfn, dim3(1), dim3(WAVE), 0, s->stream, (const double*)s->cr_state, src, cnt, n_cr, s->cr_state);
-        HIPCK(hipGetLastError());
-    }
-    return 0;
+    return launch_side(s->stream, kfn, "cr_final_kernel", dim3(1), WAVE, fence, Then::NO_ACQUIRE, s->cr_state, src, cnt, n_cr, s->cr_state);
 }
 // the fold nobody consumed (bpm_sampler::cr_pending)
 static int cr_flush_pending(bpm_sampler* s) {
@@ -1916,15 +1918,8 @@ static int finish_generation(bpm_sampler* s) {
             const PhaseArgs& a0 = s->cur_args[0];
             typedef void (*L1K)(Layout, PermKey, const uint32_t*, uint32_t, uint32_t, uint32_t, double*);
             const L1K l1 = s->cr_g1 == 4u ? cr_level1_kernel<4> : (s->cr_g1 == 16u ? cr_level1_kernel<16> : cr_level1_kernel<64>);
-            if (d.dq) {
-                struct { Layout L; PermKey pk; const uint32_t* perm; uint32_t N, n_cr, n1, _pad; double* part1; } ka{s->L, a0.pk, a0.perm_tab, s->N, n_cr, s->cr_n1, 0u, s->cr_p1_cur};
-                CK(launch_beside(reinterpret_cast<const void*>(l1), "cr_level1_kernel", (uint32_t)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS), 1, CR_L1_THREADS, &ka, sizeof(ka),
-                                 fence, Then::KEEP));
-            } else {
-                hipLaunchKernelGGL(l1, dim3((unsigned)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS)), dim3(CR_L1_THREADS), 0, s->stream, s->L, a0.pk, a0.perm_tab, s->N,
-                                   n_cr, s->cr_n1, s->cr_p1_cur);
-                HIPCK(hipGetLastError());
-            }
+            CK(launch_side(s->stream, l1, "cr_level1_kernel", dim3((uint32_t)(((uint64_t)s->cr_n1 * s->cr_g1 + CR_L1_THREADS - 1) / CR_L1_THREADS)), CR_L1_THREADS, fence, Then::KEEP,
+                           s->L, a0.pk, a0.perm_tab, s->N, n_cr, s->cr_n1, s->cr_p1_cur));
         }
         const double* src = s->cr_p1_cur;
         uint32_t cnt = s->cr_n1;
@@ -1932,13 +1927,7 @@ static int finish_generation(bpm_sampler* s) {
         while (cnt > CR_FINAL_MAX) {
             const uint32_t nn = (cnt + WAVE - 1) / WAVE;
             double* dst = s->cr_p2[flip];
-            if (d.dq) {
-                struct { const double* p1; uint32_t n1, n_cr, n2, _pad; double* p2; } ka{src, cnt, n_cr, nn, 0u, dst};
-                CK(launch_beside(reinterpret_cast<const void*>(cr_mid_kernel), "cr_mid_kernel", nn, 1, WAVE, &ka, sizeof(ka), fence, Then::KEEP));
-            } else {
-                hipLaunchKernelGGL(cr_mid_kernel, dim3(nn), dim3(WAVE), 0, s->stream, src, cnt, n_cr, nn, dst);
-                HIPCK(hipGetLastError());
-            }
+            CK(launch_side(s->stream, cr_mid_kernel, "cr_mid_kernel", dim3(nn), WAVE, fence, Then::KEEP, src, cnt, n_cr, nn, dst));
             src = dst; cnt = nn; flip ^= 1;
         }
         static const bool no_defer = test_path("crnofold");
@@ -2000,19 +1989,12 @@ static unsigned long long push_timeout_ticks() {
 // one push_sync_kernel of rank s: on the library's own queue when the generation loop runs there, else on the sampler's stream
 static int launch_push_sync(bpm_sampler* s, unsigned long long seq, bool notify, bool wait) {
     const unsigned long long* ctab = s->tab_all + MAX_SEG;
-    if (g_disp.dq) {
-        struct { PushCtrl* mine; const unsigned long long* ctab; uint32_t world, me; unsigned long long seq; uint32_t nf, wf; unsigned long long to; } ka{
-            s->ctrl, ctab, s->world, s->rank, seq, notify ? 1u : 0u, wait ? 1u : 0u, push_timeout_ticks()};
-        // NO fences on this packet (the barrier bit orders it behind the update kernel, whose own packet released): the kernel reads and
-        // writes nothing but the flags, with system-scope atomics that pass the caches; the update kernel that follows acquires.
-        // (With acquire + release at system scope here as well a hand-over measured 10.0 us instead of 3.8 with agent-scope fences:
-        // profiles/r03_push_barrier_cost.txt.)
-        return launch_beside(reinterpret_cast<const void*>(push_sync_kernel), "push_sync_kernel", 1, 1, WAVE, &ka, sizeof(ka), 0, Then::ACQUIRE);
-    }
-    hipLaunchKernelGGL(push_sync_kernel, dim3(1), dim3(WAVE), 0, s->stream, s->ctrl, ctab, s->world, s->rank, seq, notify ? 1u : 0u, wait ? 1u : 0u,
-                       push_timeout_ticks());
-    HIPCK(hipGetLastError());
-    return 0;
+    // NO fences on the queue's packet (the barrier bit orders it behind the update kernel, whose own packet released): the kernel reads and
+    // writes nothing but the flags, with system-scope atomics that pass the caches; the update kernel that follows acquires.
+    // (With acquire + release at system scope here as well a hand-over measured 10.0 us instead of 3.8 with agent-scope fences:
+    // profiles/r03_push_barrier_cost.txt.)
+    return launch_side(s->stream, push_sync_kernel, "push_sync_kernel", dim3(1), WAVE, 0, Then::ACQUIRE,
+                       s->ctrl, ctab, s->world, s->rank, seq, notify ? 1u : 0u, wait ? 1u : 0u, push_timeout_ticks());
 }
 // The cross-rank barrier of the push exchange: "every rank has finished -- and pushed -- everything it enqueued before this point".
 // A process per rank: one kernel announces and waits.  A local group (R handles of one process on one GPU, possibly sharing hardware
@@ -2258,16 +2240,17 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
                 bpm_sampler* s = g.h[r];
                 bind_rank_queue(s);
                 if (s->cur_args[ph].n_items > 0) {
-                    d.release_this = d.dq && d.dq_call_last_gen && (ph == 1 || s->cur_args[1].n_items == 0);
+                    const bool last_update = ph == 1 || s->cur_args[1].n_items == 0;      // this rank's last update dispatch of the generation
+                    d.release_this = d.dq && d.dq_call_last_gen && last_update;
                     if (d.dq && s->timed_last_gen >= 0) {
                         // direct mode: attaching a time stamp costs the host nothing -- the first and the last update dispatch of the call
                         if (s->timed_want_first) { s->timed_want_first = false; d.sig = 0; s->timed_l0 = d.timed_launches; }
-                        else if (s->timed_last_gen == s->t_abs && (ph == 1 || s->cur_args[1].n_items == 0)) { d.sig = 1; s->timed_l1 = d.timed_launches; }
+                        else if (s->timed_last_gen == s->t_abs && last_update) { d.sig = 1; s->timed_l1 = d.timed_launches; }
                     } else if (s->timed_want_first && s->timed_skip > 0) {
                         --s->timed_skip;
                     } else if (s->timed_want_first) {
                         s->timed_want_first = false; d.stop_event = s->ev0; s->timed_l0 = d.timed_launches;
-                    } else if (s->timed_last_gen == s->t_abs && (ph == 1 || s->cur_args[1].n_items == 0)) {
+                    } else if (s->timed_last_gen == s->t_abs && last_update) {
                         d.stop_event = s->ev1; s->timed_l1 = d.timed_launches;
                     }
                     const long long tl0 = g_host_timing ? now_ns() : 0;
@@ -2322,8 +2305,6 @@ static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
     if (!s || !s->user_fused_fn) { d.user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
     PhaseArgs ka = a;
     ka.tparams = s->user_params;                   // the caller's parameter block is the target's
-    size_t sz = sizeof(ka);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     static const bool no_hot = test_path("nohot");
     // burn-in: prepare_generation handed this launch the level-1 sums to write (cr_part1) only after phase_args_hot(a, true, plan, true) held for BOTH launches
     const bool adapt = a.cr_part1 != nullptr && s->user_fused_adapt != nullptr;
@@ -2331,15 +2312,9 @@ static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
     const unsigned block = adapt ? s->user_fused_block_adapt : s->user_fused_block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
     // (the steady-state instantiation was compiled for update records exactly when this sampler builds them: HOT 1 / HOT 2)
     const bool hot = !adapt && !no_hot && s->user_fused_hot && (a.rec_tab != nullptr) == s->plan_on && phase_args_hot(a, s->cfg.algo == BPM_ALGO_DREAM, a.rec_tab != nullptr, false);
-    if (d.dq) {      // the library's own queue (launch_packed's packet: the module's kernels take the argument block alone, no preloaded leading arguments)
-        const bpm::DqKernel* k = d.dq->kernel_by_name(s->user_fused_names[adapt ? 2 : (hot ? 1 : 0)]);
-        const UpdatePacket p = take_update_packet(d);
-        if (!k || d.dq->launch(*k, grid, 1, block, &ka, sizeof(ka), p.fence, p.sig) != 0) d.dq_error = true;
-        ++d.timed_launches; ++d.n_direct;
-        return;
-    }
-    (void)hipExtModuleLaunchKernel(adapt ? s->user_fused_adapt : (hot ? s->user_fused_hot : s->user_fused_fn), grid * block, 1, 1, block, 1, 1, 0, st, nullptr, extra, nullptr, take_stop_event(d), 0);
-    ++d.timed_launches; ++d.n_stream;
+    // (launch_packed's two paths; the module's kernels take the argument block alone, no preloaded leading arguments)
+    if (d.dq) return update_packet(d, d.dq->kernel_by_name(s->user_fused_names[adapt ? 2 : (hot ? 1 : 0)]), grid, block, &ka, sizeof(ka));
+    update_on_stream(d, adapt ? s->user_fused_adapt : (hot ? s->user_fused_hot : s->user_fused_fn), grid, block, &ka, sizeof(ka), st);
 }
 static int run_generations(const Group& g, int64_t n_gens) {
     bpm_sampler* s0 = g.h[0];
@@ -2675,13 +2650,7 @@ extern "C" int bpm_push_connect(bpm_handle_t s, const void* blobs) {
 static int launch_arena_probe(bpm_sampler* s, int mode, int form, unsigned long long seed, double* save, int fence) {
     ProbeGeo geo{s->L.blk, s->n_local, s->ld, (s->om && s->off_om) ? 2u * s->n_local : 0u, s->world, s->rank, 2u * s->ld + 8u};
     unsigned long long* bad = &s->ctrl->arena_bad[form];
-    if (g_disp.dq) {
-        struct { const unsigned long long* tab; ProbeGeo g; int mode; unsigned long long seed; double* save; unsigned long long* bad; } ka{s->tab_all, geo, mode, seed, save, bad};
-        return launch_beside(reinterpret_cast<const void*>(push_arena_probe_kernel), "push_arena_probe_kernel", PROBE_REGIONS, s->world, WAVE, &ka, sizeof(ka), fence, Then::ACQUIRE);
-    }
-    hipLaunchKernelGGL(push_arena_probe_kernel, dim3(PROBE_REGIONS, s->world), dim3(WAVE), 0, s->stream, (const unsigned long long*)s->tab_all, geo, mode, seed, save, bad);
-    HIPCK(hipGetLastError());
-    return 0;
+    return launch_side(s->stream, push_arena_probe_kernel, "push_arena_probe_kernel", dim3(PROBE_REGIONS, s->world), WAVE, fence, Then::ACQUIRE, s->tab_all, geo, mode, seed, save, bad);
 }
 
 // Collective over the ranks (all processes call it together; a local group passes its R handles), in two parts.
@@ -4272,6 +4241,34 @@ extern "C" int bpm_debug_time_kernels(bpm_handle_t s, int32_t reps, float* updat
         HIPCK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
         (which == 0 ? *update_us : *replay_us) = ms * 1e3f / (float)reps;
     }
+    return 0;
+}
+
+// Test hook: the argument block the host hands kernel `index` of those it dispatches by packets of its own -- the side kernels as launch_side lays
+// them out (from the function-pointer types its callers pass), the update kernels as FusedKernarg's members.  (tests/test_abi.py holds them
+// against the code object's own metadata, on a machine without a GPU.)
+struct KernargRow { const char* name; size_t n; const size_t* off; const size_t* size; };
+template <class... P>
+static KernargRow kernarg_row(const char* name, void (*)(P...)) {
+    static constexpr KernargLayout<P...> lay;
+    static_assert(lay.n <= 8, "bpm_debug_kernarg_layout reports up to 8 arguments");
+    return {name, lay.n, lay.off, lay.size};
+}
+static KernargRow fused_kernarg_row(const char* name) {
+    static const size_t off[] = {offsetof(FusedKernarg, pl_plan), offsetof(FusedKernarg, pl_upd_off), offsetof(FusedKernarg, pl_n_items), offsetof(FusedKernarg, pl_mode), offsetof(FusedKernarg, a)};
+    static const size_t size[] = {sizeof(FusedKernarg::pl_plan), sizeof(FusedKernarg::pl_upd_off), sizeof(FusedKernarg::pl_n_items), sizeof(FusedKernarg::pl_mode), sizeof(FusedKernarg::a)};
+    return {name, 5, off, size};
+}
+extern "C" int bpm_debug_kernarg_layout(int32_t index, const char** name, int32_t* n_args, int64_t offsets[8], int64_t sizes[8]) {
+#define ROW(k) kernarg_row(#k, k)
+    static const KernargRow rows[] = {ROW(moments_partial_kernel), ROW(moments_final_kernel), ROW(perm_table_kernel), ROW(plan_kernel), kernarg_row("cr_final_kernel", cr_final_kernel<1>),
+                                      kernarg_row("cr_level1_kernel", cr_level1_kernel<4>), ROW(cr_mid_kernel), ROW(push_sync_kernel), ROW(push_arena_probe_kernel),
+                                      fused_kernarg_row("phase_fused_kernel"), fused_kernarg_row("phase_wide_kernel")};
+#undef ROW
+    if (index < 0 || index >= (int32_t)(sizeof(rows) / sizeof(rows[0]))) return fail("bpm_debug_kernarg_layout: no kernel of that index");
+    const KernargRow& r = rows[index];
+    *name = r.name; *n_args = (int32_t)r.n;
+    for (size_t i = 0; i < r.n; ++i) { offsets[i] = (int64_t)r.off[i]; sizes[i] = (int64_t)r.size[i]; }
     return 0;
 }
 

@@ -35,6 +35,10 @@ int bpm_get_trace(bpm_handle_t h, int32_t* out_i32, double* out_f64, uint8_t* ou
  * queue is unusable for the rest of the process afterwards: child processes only) */
 int bpm_debug_destroy_plan(int32_t queue_failed, int32_t quiesced);
 int bpm_debug_fail_queue(bpm_handle_t h, int32_t refuse_quiesce);
+/* the argument block the host hands kernel `index` (0, 1, ... until the call fails) of those it dispatches by packets of its own -- the kernels beside
+ * the update kernels, then the update kernels: *name = the kernel's plain name (static storage), *n_args <= 8 explicit arguments, their byte offsets
+ * and sizes as the host lays them out.  No GPU, no handle: a test holds them against the code object's metadata. */
+int bpm_debug_kernarg_layout(int32_t index, const char** name, int32_t* n_args, int64_t offsets[8], int64_t sizes[8]);
 /* no-op packets on the handle's own AQL queue until its next packet takes position `pos` (0 ... 254) of an epoch of 256 packets;
  * *widx = the queue's write index afterwards (a test then puts a drain's packets at a chosen place of the ring) */
 int bpm_debug_queue_pad(bpm_handle_t h, int32_t pos, int64_t* widx);

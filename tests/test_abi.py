@@ -201,6 +201,54 @@ def test_no_kernel_spills_or_touches_scratch_memory(built):
     assert asm.count("scratch_load") + asm.count("scratch_store") == 0
 
 
+def test_packed_kernel_arguments_match_the_code_objects_layout(built_test):
+    """The library's own AQL queue hands a kernel an argument block the HOST lays out (sampler.hip: launch_side from the kernel's parameter types,
+    FusedKernarg for the update kernels); no HIP error check sees a block the device reads differently.  bpm_debug_kernarg_layout reports the
+    host's offsets and sizes; the code object's metadata (.args of every kernel, hidden arguments aside) says what the device reads.  Every
+    instantiation of every reported kernel must agree, argument by argument; no GPU needed."""
+    import ctypes as C
+    import sys
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import LLVM
+    from bipymc_amd import _lib
+    lib = _lib.load_test()
+    host = {}
+    for i in range(64):
+        name, n, off, size = C.c_char_p(), C.c_int32(0), (C.c_int64 * 8)(), (C.c_int64 * 8)()
+        if lib.bpm_debug_kernarg_layout(i, C.byref(name), C.byref(n), off, size) != 0:
+            break
+        host[name.value.decode()] = [(int(off[j]), int(size[j])) for j in range(n.value)]
+    assert sorted(host) == sorted(["moments_partial_kernel", "moments_final_kernel", "perm_table_kernel", "plan_kernel", "cr_final_kernel", "cr_level1_kernel",
+                                   "cr_mid_kernel", "push_sync_kernel", "push_arena_probe_kernel", "phase_fused_kernel", "phase_wide_kernel"])
+    for name in ("phase_fused_kernel", "phase_wide_kernel"):          # FusedKernarg: the preloaded leading arguments, then PhaseArgs
+        assert [o for o, _ in host[name]] == [0, 8, 12, 16, 24] and [s for _, s in host[name]][:4] == [8, 4, 4, 4]
+    with tempfile.TemporaryDirectory() as td:
+        fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "k.co")
+        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, built_test, os.path.join(td, "x.so")])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co]).decode()
+    seen = dict((name, 0) for name in host)
+    for blk in notes.split("  - .agpr_count:")[1:]:
+        kname = re.search(r"^    \.name:\s+(\S+)", blk, re.M).group(1)
+        names = [name for name in host if name in kname]
+        if not names:
+            continue
+        assert len(names) == 1, (kname, names)
+        args = re.search(r"^    \.args:\n((?:      .*\n)*)", blk, re.M).group(1)
+        device = []
+        for arg in re.split(r"^      - ", args, flags=re.M)[1:]:
+            f = dict(re.findall(r"\.(\w+):\s+(\S+)", arg))
+            if not f["value_kind"].startswith("hidden_"):
+                device.append((int(f["offset"]), int(f["size"])))
+        assert device == host[names[0]], (kname, device, host[names[0]])
+        seen[names[0]] += 1
+    assert all(seen.values()), seen                                  # a reported name that matches no kernel is an error
+    # (every instantiation: the CR reduction's three level-1 and four final kernels, the update kernels' many flavours)
+    assert seen["cr_level1_kernel"] == 3 and seen["cr_final_kernel"] == 4 and seen["phase_fused_kernel"] > 100 and seen["phase_wide_kernel"] >= 4, seen
+
+
 def test_hip_source_likelihood_compiles_without_a_gpu():
     """bpm_check_device_likelihood (include/bipymc_hip.h): hiprtc builds the caller's ln_like + the wrapper kernel for gfx950 with no device in the
     machine; a source that does not compile comes back as an error carrying the compiler's log (through HipLikelihood.check as ValueError)."""
