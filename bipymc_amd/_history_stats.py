@@ -1,6 +1,6 @@
 """The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance,
-histograms and per-generation traces (bipymc_amd/diagnostics.py, quantiles.py, covariance.py, histograms.py, traces.py), each reduced where
-the history lives.
+histograms, per-generation traces and summaries of user-written derived quantities (bipymc_amd/diagnostics.py, quantiles.py, covariance.py,
+histograms.py, traces.py, derived.py), each reduced where the history lives.
 
 The contract they share.  The window is the super-chain rows >= n_burn, param_est's selection (row g * n_chains + i = chain i at generation
 g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
@@ -65,3 +65,12 @@ class HistoryStatistics(object):
         eng = self._stats_engine("param_est_trace")
         return _tr.compute(eng.trace_bins, eng.trace_chains, self._stats_allgather, n_burn, self.n_chains, eng.history_rows(), eng.dim,
                            every=every, chains=chains)
+
+    def param_est_fn(self, fn, n_burn=0, values=False):
+        """The posterior of a function of the parameters: `fn` (a derived.HipFunction: a few lines of HIP mapping one sample and its
+        log-likelihood to n_out numbers) over param_est(n_burn)[2]'s rows -- np.mean, np.std, np.nanmin, np.nanmax and the NaN count of every
+        output, and with values=True the (rows, n_out) matrix itself in super-chain order; what the reference's fitting scripts compute on the
+        host from param_est's copy of the history.  -> derived.PosteriorDerived(mean, sd, min, max, n_nan, n, values) with .band(k)"""
+        from . import derived as _dv
+        eng = self._stats_engine("param_est_fn")
+        return _dv.compute(eng.derive, self._stats_allgather, fn, n_burn, self.n_chains, eng.history_rows(), values=values)

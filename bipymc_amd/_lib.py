@@ -111,6 +111,9 @@ SIGNATURES = {
     "bpm_hist_pairs": (C.c_int, [_H, C.c_int32, _P(C.c_int32), C.c_int32, _dp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
     "bpm_trace_bins": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _dp, _dp, _P(C.c_int64), _dp]),
     "bpm_trace_chains": (C.c_int, [_H, C.c_int32, _P(C.c_int32), _dp, _dp]),
+    "bpm_check_device_function": (C.c_int, [C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64]),
+    "bpm_set_device_function": (C.c_int, [_H, C.c_char_p, C.c_int32, _dp, C.c_int32]),
+    "bpm_derive": (C.c_int, [_H, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _P(C.c_int64), _dp, C.c_int64]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only
@@ -152,7 +155,7 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h", "csrc/derived.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

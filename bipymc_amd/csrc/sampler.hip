@@ -44,6 +44,7 @@
 #endif
 #include "aql_queue.h"
 #include "user_likelihood.h"
+#include "derived.h"
 #include "embedded_src.h"
 
 using namespace bpm;
@@ -575,6 +576,12 @@ struct bpm_sampler {
     std::string user_fused_names[3];         // their lowered names ([2]: the burn-in instantiation): what the library's own queue dispatches them by (DirectQueue::kernel_by_name)
     bool user_fused_dq = false;              // ... and both were found among the loaded code objects
     std::string user_fused_why;              // why the fused form is not in use (bpm_get_device_likelihood_info)
+    // a caller's function of one sample, compiled around the window reduction of derived.h (bpm_set_device_function): kept until replaced or bpm_destroy
+    hipModule_t derive_mod = nullptr;
+    hipFunction_t derive_fn = nullptr;        // bpm_derive_rows of THIS module: launched by handle, never looked up by name
+    std::string derive_src;                   // the source bytes and n_out the module was built from: the same again only re-upload the parameters
+    int32_t derive_n_out = 0;
+    double* derive_params = nullptr;
     double* aux_buf = nullptr;
     int32_t* ids_buf = nullptr;
     int32_t* trace_i32 = nullptr;      // per-chain decision trace (bpm_set_trace: test variant only; always null in the product library)
@@ -1146,7 +1153,8 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     if (s->h_props) (void)hipHostFree(s->h_props);
     if (s->h_ll) (void)hipHostFree(s->h_ll);
     for (hipEvent_t e : s->chunk_ev) if (e) (void)hipEventDestroy(e);
-    if (free_buffers) { if (s->user_mod) (void)hipModuleUnload(s->user_mod); if (s->user_fused_mod) { if (s->dq) for (const std::string& nm : s->user_fused_names) s->dq->forget_named(nm); (void)hipModuleUnload(s->user_fused_mod); } if (s->user_params) (void)hipFree(s->user_params); }
+    if (free_buffers) { if (s->user_mod) (void)hipModuleUnload(s->user_mod); if (s->user_fused_mod) { if (s->dq) for (const std::string& nm : s->user_fused_names) s->dq->forget_named(nm); (void)hipModuleUnload(s->user_fused_mod); } if (s->user_params) (void)hipFree(s->user_params);
+                        if (s->derive_mod) (void)hipModuleUnload(s->derive_mod); if (s->derive_params) (void)hipFree(s->derive_params); }
     for (auto& B : s->tb) {
         if (B.count_h) (void)hipHostFree(B.count_h);
         if (B.built) (void)hipEventDestroy(B.built);
@@ -3819,6 +3827,139 @@ extern "C" int bpm_refresh_device_loglike(bpm_handle_t s) {
     CK(set_device(s));
     if (!s->user_fn) return fail("bpm_refresh_device_loglike: no device likelihood installed (bpm_set_device_likelihood)");
     return user_refresh_ll(s);
+}
+
+// ---- posterior summaries of a caller's derived quantities (derived.h; bipymc_amd/derived.py merges the ranks and finishes mean and sd) ------
+// What the reference's fitting scripts do on the host with param_est(n_burn)[2] (examples/ex_exp_fit.py:197-202: c_0 / c_inf per sample, its
+// mean and standard deviation; :176-192: the fitted model at every sample), taken where the history lives.
+static int check_n_out(const char* who, int32_t n_out) {
+    if (n_out < 1 || n_out > DERIVE_MAX_OUT)
+        return fail(std::string(who) + ": n_out must be 1 ... " + std::to_string(DERIVE_MAX_OUT) + " (got " + std::to_string(n_out) + ")");
+    return 0;
+}
+
+extern "C" int bpm_check_device_function(const char* hip_source, int32_t n_out, const char* arch, char* log, int64_t log_cap) {
+    if (!hip_source) return fail("bpm_check_device_function: null source");
+    CK(check_n_out("bpm_check_device_function", n_out));
+    std::vector<char> code;
+    std::string why;
+    { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_device_function(g_hiprtc, hip_source, (arch && *arch) ? arch : "gfx950", bpm_src_trace_acc_h, code); }
+    if (log && log_cap > 0) {
+        const size_t n = std::min(why.size(), (size_t)log_cap - 1);
+        std::memcpy(log, why.data(), n);
+        log[n] = '\0';
+    }
+    return why.empty() ? 0 : fail("bpm_check_device_function: " + why);
+}
+
+extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, int32_t n_out, const double* params, int32_t n_params) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_device_function: bad argument");
+    CK(check_n_out("bpm_set_device_function", n_out));
+    if (!s->derive_fn || s->derive_n_out != n_out || s->derive_src != hip_source) {
+        hipDeviceProp_t prop;
+        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
+        std::vector<char> code;
+        std::string why;
+        { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_device_function(g_hiprtc, hip_source, prop.gcnArchName, bpm_src_trace_acc_h, code); }
+        if (!why.empty()) return fail("bpm_set_device_function: " + why);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        HIPCK(hipModuleLoadData(&mod, code.data()));
+        if (hipModuleGetFunction(&fn, mod, "bpm_derive_rows") != hipSuccess || !fn) {
+            (void)hipGetLastError();
+            (void)hipModuleUnload(mod);
+            return fail("bpm_set_device_function: the compiled module has no bpm_derive_rows kernel");
+        }
+        HIPCK(hipStreamSynchronize(s->stream));                      // (a previous function's launches are done)
+        if (s->derive_mod) (void)hipModuleUnload(s->derive_mod);
+        s->derive_mod = mod; s->derive_fn = fn; s->derive_n_out = n_out; s->derive_src = hip_source;
+    }
+    HIPCK(hipStreamSynchronize(s->stream));
+    if (s->derive_params) { (void)hipFree(s->derive_params); s->derive_params = nullptr; }
+    CK(dev_alloc(&s->derive_params, (size_t)std::max(n_params, 1)));
+    HIPCK(hipMemsetAsync(s->derive_params, 0, (size_t)std::max(n_params, 1) * sizeof(double), s->stream));
+    if (n_params > 0) HIPCK(hipMemcpyAsync(s->derive_params, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));                          // (`params` is the caller's again)
+    return 0;
+}
+
+// Over this rank's super-chain rows >= n_burn (bpm_reduce_moments' selection: a partial first generation by chain index), per output m of
+// the installed function: counts = [2][n_out]: how many values are finite | NaN; sums = [5][n_out]: shift | S1 | S2 | min | max (bpm_trace_bins'
+// meaning).  *n_rows: the window's local rows, *n_first of them in a partial first generation (0: whole generations only).  values (may be
+// null): values[r * n_out + m] for the window's local rows r in order, at most values_cap doubles.  Keeps no state; every buffer is temporary.
+extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, double* sums, int64_t* n_rows, int64_t* n_first, double* values,
+                          int64_t values_cap) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!counts || !sums || !n_rows || !n_first) return fail("bpm_derive: null argument");
+    if (n_burn < 0) return fail("bpm_derive: n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
+    if (!s->derive_fn) return fail("bpm_derive: no device function installed (bpm_set_device_function)");
+    CK(require_resident_history(s, "bpm_derive"));
+    uint64_t lo = 0, hi = 0;
+    CK(super_chain_window(s, n_burn, &lo, &hi));
+    const uint64_t rows = hi - lo;
+    const uint32_t n_out = (uint32_t)s->derive_n_out;
+    *n_rows = (int64_t)rows;
+    *n_first = (int64_t)(rows % s->n_local);
+    std::fill(counts, counts + 2 * (size_t)n_out, (int64_t)0);
+    std::fill(sums, sums + 5 * (size_t)n_out, 0.0);
+    std::fill(sums + 3 * (size_t)n_out, sums + 4 * (size_t)n_out, HUGE_VAL);
+    std::fill(sums + 4 * (size_t)n_out, sums + 5 * (size_t)n_out, -HUGE_VAL);
+    if (rows == 0) return 0;
+    const uint64_t n_val = rows * n_out;
+    if (values) {
+        if (n_val >= (1ull << 31))
+            return fail("bpm_derive: the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string(n_out) + " outputs are " +
+                        std::to_string((unsigned long long)n_val) + " elements; fewer than 2^31 per rank can be returned");
+        if (values_cap < 0 || (uint64_t)values_cap < n_val)
+            return fail("bpm_derive: values holds " + std::to_string((long long)values_cap) + " doubles; the window needs " + std::to_string((unsigned long long)n_val));
+    }
+    CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
+    uint32_t R = 0, ldp = 0, ldo = 0, lds = 0;
+    // BPM_DERIVE_LDS_KB (16 ... 60; read at every call: tools/derived_time.py switches it): the LDS budget of a workgroup's tiles (A/B)
+    uint32_t budget = (uint32_t)DERIVE_LDS_BYTES;
+    if (const char* kb = getenv("BPM_DERIVE_LDS_KB")) budget = (uint32_t)std::min(std::max(atoi(kb), 16), DERIVE_LDS_BYTES / 1024) * 1024u;
+    derive_tile(s->dim, n_out, budget, R, ldp, ldo, lds);
+    uint64_t parts = 1;
+    CK(rows_grid(rows, 1, R, "bpm_derive", &parts));
+    // [part records | folded records]; with one part the part records are the folded ones
+    const uint64_t n_rec = parts * n_out;
+    const size_t o_fold = (size_t)TR_F_BINS * n_rec;
+    DevTemp<double> b, v;
+    CK(b.alloc(o_fold + (parts > 1 ? (size_t)TR_F_BINS * n_out : 0), "bpm_derive", "the part records of " + std::to_string((unsigned long long)parts) + " workgroups"));
+    if (values) CK(v.alloc((size_t)n_val, "bpm_derive", "the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string(n_out) + " outputs"));
+    {
+        const double* H = s->hist;
+        const double* LL = s->llhist;
+        unsigned int ld = s->ld, k_out = n_out, k_R = R, k_ldp = ldp, k_ldo = ldo;
+        int d = (int)s->dim;
+        unsigned long long k_lo = lo, k_hi = hi, k_rec = n_rec;
+        const double* params = s->derive_params;
+        double* rec = b.p;
+        double* vals = v.p;
+        void* args[] = {(void*)&H, (void*)&LL, (void*)&ld, (void*)&d, (void*)&k_lo, (void*)&k_hi, (void*)&params, (void*)&k_out, (void*)&k_R, (void*)&k_ldp,
+                        (void*)&k_ldo, (void*)&rec, (void*)&k_rec, (void*)&vals};
+        HIPCK(hipModuleLaunchKernel(s->derive_fn, (unsigned)parts, 1, 1, DERIVE_THREADS, 1, 1, lds, s->stream, args, nullptr));
+    }
+    const double* rec = b.p;
+    if (parts > 1) {
+        hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((n_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream, (const double*)b.p,
+                           (uint32_t)parts, n_out, (uint64_t)n_out, (uint32_t)TR_F_BINS, b.p + o_fold);
+        HIPCK(hipGetLastError());
+        rec = b.p + o_fold;
+    }
+    std::vector<double> h((size_t)TR_F_BINS * n_out);
+    HIPCK(hipMemcpyAsync(h.data(), rec, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (values) HIPCK(hipMemcpyAsync(values, v.p, (size_t)n_val * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    const int count_f[2] = {TR_N, TR_NAN}, sum_f[5] = {TR_C, TR_S1, TR_S2, TR_MIN, TR_MAX};
+    for (uint32_t m = 0; m < n_out; ++m) {
+        for (int f = 0; f < 2; ++f) std::memcpy(&counts[(size_t)f * n_out + m], &h[(size_t)count_f[f] * n_out + m], 8);
+        for (int f = 0; f < 5; ++f) sums[(size_t)f * n_out + m] = h[(size_t)sum_f[f] * n_out + m];
+    }
+    return 0;
 }
 
 // the caller-owned-buffer form of rounds 1-4, compacted to the active work items.  Since round 5 the read-back runs in pieces INSIDE the call: the

@@ -29,63 +29,20 @@
 #pragma once
 #include "kernels.h"
 #include "quantiles.h"
+#include "trace_acc.h"      // TrAcc, tr_init / tr_add / tr_merge_moments / tr_merge / tr_store, the field enum (shared with derived.h)
 
 namespace bpm {
 inline namespace BPM_VARIANT_NS {      // (philox.h: one kernel-symbol namespace per build variant)
 
 constexpr int TR_THREADS = 256;
 constexpr int TR_UNR = 4;                      // independent loads in flight per lane
-// fields of a record: the first TR_F_BINS of every record, all TR_F_LL of a ln-like record
-enum { TR_N = 0, TR_C, TR_S1, TR_S2, TR_NAN, TR_MIN, TR_MAX, TR_F_BINS, TR_PINF = TR_F_BINS, TR_NINF, TR_BKEY, TR_BROW, TR_F_LL };
 constexpr uint64_t TR_NO_ROW = ~0ull;          // arg-max: no value that is not NaN (its key is 0, below every key)
 
-struct TrAcc {
-    double c, s1, s2, mn, mx;
-    uint32_t n, n_nan;                         // (a workgroup sees fewer than 2^31 rows: the host sizes the parts so)
-};
 struct TrLlAcc {
     TrAcc m;
     uint32_t n_pinf, n_ninf;
     uint64_t bkey, brow;
 };
-
-__device__ __forceinline__ void tr_init(TrAcc& a) {
-    a.c = a.s1 = a.s2 = 0.0;
-    a.mn = __longlong_as_double(0x7FF0000000000000ll);
-    a.mx = -a.mn;
-    a.n = a.n_nan = 0u;
-}
-
-// -> x is finite and went into the moments
-__device__ __forceinline__ bool tr_add(TrAcc& a, double x) {
-    if (x != x) { ++a.n_nan; return false; }
-    a.mn = x < a.mn ? x : a.mn;
-    a.mx = x > a.mx ? x : a.mx;
-    if (x - x != 0.0) return false;
-    if (a.n == 0u) a.c = x;
-    const double d = x - a.c;
-    a.s1 += d;
-    a.s2 += d * d;
-    ++a.n;
-    return true;
-}
-
-template <class Count>
-__device__ __forceinline__ void tr_merge_moments(Count& n, double& c, double& s1, double& s2, Count nb, double cb, double s1b, double s2b) {
-    if (nb == 0) return;
-    if (n == 0) { n = nb; c = cb; s1 = s1b; s2 = s2b; return; }
-    const double d = cb - c, w = (double)nb;
-    s1 += s1b + w * d;
-    s2 += s2b + (2.0 * d * s1b + w * d * d);
-    n += nb;
-}
-
-__device__ __forceinline__ void tr_merge(TrAcc& a, const TrAcc& b) {
-    tr_merge_moments(a.n, a.c, a.s1, a.s2, b.n, b.c, b.s1, b.s2);
-    a.mn = b.mn < a.mn ? b.mn : a.mn;
-    a.mx = b.mx > a.mx ? b.mx : a.mx;
-    a.n_nan += b.n_nan;
-}
 
 // the larger key wins, the smaller row among equal keys
 __device__ __forceinline__ void tr_merge_best(uint64_t& key, uint64_t& row, uint64_t kb, uint64_t rb) {
@@ -99,17 +56,6 @@ __device__ __forceinline__ void tr_part(uint64_t t, uint32_t n_local, uint64_t g
     const uint64_t a = r0 + (uint64_t)blockIdx.y * chunk;
     *lo = a < r1 ? a : r1;
     *hi = *lo + chunk < r1 ? *lo + chunk : r1;
-}
-
-__device__ __forceinline__ void tr_store(double* __restrict__ rec, uint64_t n_rec, uint64_t j, const TrAcc& a) {
-    unsigned long long* u = reinterpret_cast<unsigned long long*>(rec);
-    u[TR_N * n_rec + j] = a.n;
-    rec[TR_C * n_rec + j] = a.c;
-    rec[TR_S1 * n_rec + j] = a.s1;
-    rec[TR_S2 * n_rec + j] = a.s2;
-    u[TR_NAN * n_rec + j] = a.n_nan;
-    rec[TR_MIN * n_rec + j] = a.mn;
-    rec[TR_MAX * n_rec + j] = a.mx;
 }
 
 // rec: TR_F_BINS fields of n_rec = bins * parts * ld part records

@@ -439,7 +439,7 @@ class DeMcMpi(HistoryStatistics):
         S2 = np.sum([p[2] for p in parts], axis=0)
         return sh + S1 / n, np.sqrt(np.maximum(S2 / n - (S1 / n) ** 2, 0.0))
 
-    # convergence_diagnostics, param_est_quantiles, param_est_cov, param_est_hist, param_est_trace: HistoryStatistics, through these two
+    # convergence_diagnostics, param_est_quantiles, param_est_cov, param_est_hist, param_est_trace, param_est_fn: HistoryStatistics, through these two
     def _stats_engine(self, who):
         return self._engine
 

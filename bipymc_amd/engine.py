@@ -521,6 +521,43 @@ class HipEngine(object):
         self._ck(self.lib.bpm_trace_chains(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(x), _dptr(ll)))
         return pos, x, ll
 
+    def set_device_function(self, source, n_out, params=()):
+        """A function of one sample as HIP source (include/bipymc_hip.h: bpm_set_device_function): compiled around the window reduction of
+        bipymc_amd/csrc/derived.h and kept on the handle; the same source and n_out again only copy `params`"""
+        p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+        src = source.encode() if isinstance(source, str) else bytes(source)
+        self._ck(self.lib.bpm_set_device_function(self._h, src, int(n_out), _dptr(p) if p.size else None, int(p.size)))
+        self._derive_n_out = int(n_out)
+
+    def derive_rows(self, n_burn, values=False):
+        """-> (counts (2, n_out) int64, sums (5, n_out), n_rows, n_first, values (n_rows, n_out) or None): the installed function over this
+        rank's super-chain rows >= n_burn -- per output how many values are finite | NaN, and a shift | the shifted sum | the shifted sum of
+        squares of the finite ones | min | max; n_first of the n_rows rows lie in a partial first generation (bpm_derive)"""
+        m = getattr(self, "_derive_n_out", 0)
+        n_burn = int(n_burn)
+        counts = np.zeros((2, max(m, 1)), dtype=np.int64); sums = np.zeros((5, max(m, 1)))
+        n_rows = C.c_int64(0); n_first = C.c_int64(0)
+        vals, cap = None, 0
+        if values and m and n_burn >= 0:
+            # this rank's rows of the window (super_chain_window's count: a partial first generation by chain index)
+            G = self.history_rows()
+            g0, first = n_burn // self.n_chains, min(max(n_burn % self.n_chains - self.lo, 0), self.n_local)
+            cap = max(0, (G - g0) * self.n_local - first) * m if g0 < G else 0
+            if cap >= 1 << 31:
+                raise ValueError("param_est_fn: the values of %d rows x %d outputs are %d elements; fewer than 2^31 per rank can be returned"
+                                 % (cap // m, m, cap))
+            vals = np.empty(max(cap, 1))
+        i64 = C.POINTER(C.c_int64)
+        self._ck(self.lib.bpm_derive(self._h, n_burn, counts.ctypes.data_as(i64), _dptr(sums), C.byref(n_rows), C.byref(n_first),
+                                     None if vals is None else _dptr(vals), cap))
+        n = int(n_rows.value)
+        return counts[:, :m], sums[:, :m], n, int(n_first.value), None if vals is None else vals[:n * m].reshape(n, m)
+
+    def derive(self, fn, n_burn, values=False):
+        """derived.compute's per-rank call: installs `fn` (a derived.HipFunction) and reduces (set_device_function + derive_rows)"""
+        self.set_device_function(fn.source, fn.n_out, fn.params)
+        return self.derive_rows(n_burn, values)
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

@@ -366,6 +366,32 @@ int bpm_hist_pairs(bpm_handle_t h, int32_t n_dims, const int32_t* dims, int32_t 
 int bpm_trace_bins(bpm_handle_t h, int64_t g_lo, int64_t g_hi, int64_t every, int64_t* bin_counts, double* bin_sums, int64_t* ll_counts,
                    double* ll_sums, double* best_ll, int64_t* best_row, double* best_x);
 int bpm_trace_chains(bpm_handle_t h, int32_t n, const int32_t* local_ids, double* out_x, double* out_ll);
+/* Posterior summaries of a caller's DERIVED QUANTITIES on the device: what the reference's fitting scripts do on the host with
+ * param_est(n_burn)[2] (examples/ex_exp_fit.py:197-202: c_0 / c_inf per sample, its mean and standard deviation; :176-192: the fitted model
+ * at every sample for the trajectory picture; ex_line_fit.py and ex_para_fit.py likewise), without moving the history.  `hip_source` defines
+ *     __device__ void derive(const double* x, int d, double ll, const double* p, double* out)
+ * (x: one super-chain row of d coordinates; ll: its stored ln-like; p: the caller's parameter block; out[0 .. n_out), 1 <= n_out <= 256: zero
+ * on entry, so an output the function does not write is 0.0; device math functions, INFINITY, NAN and M_PI as for ln_like; compiled -O3
+ * -ffp-contract=off).  The library compiles one window-reduction kernel around it with hiprtc (bipymc_amd/csrc/derived.h).
+ * bpm_check_device_function compiles only (no sampler, no GPU needed; arch NULL = "gfx950"): 0 or -1 with the reason in `log` (and
+ * bpm_last_error).  bpm_set_device_function compiles for the handle's device, loads the module and copies the n_params doubles of `params`;
+ * the handle keeps the module until another function replaces it or bpm_destroy.  The same source bytes and n_out again reuse the loaded
+ * module and only copy `params`.  Any sampler may carry one, whatever its target.
+ * bpm_derive: over this rank's super-chain rows >= n_burn (bpm_reduce_moments' selection: a partial first generation by chain index), per
+ * output m: counts = [2][n_out]: how many values are finite | NaN; sums = [5][n_out]: a shift c (a finite value of the output) | sum (v - c) |
+ * sum (v - c)^2 over the finite values | min | max over the values that are not NaN (+inf / -inf where there is none) -- bpm_trace_bins'
+ * records; *n_rows: the window's local rows, *n_first: how many of them belong to a partial first generation (0: whole generations only).
+ * values (may be NULL): values[r * n_out + m] = output m of the window's r-th local row, n_rows * n_out doubles, values_cap: what the buffer
+ * holds.  Every partial result is merged in a fixed order and there is no atomic: the same history gives the same bits.
+ * bipymc_amd/derived.py merges the ranks (traces.py: merge_moments / finish) and puts the values into super-chain order.
+ * Every device buffer is temporary; nothing the samplers read is written (a history kept in position order is put into chain order first,
+ * as bpm_get_history does).  Errors: n_out out of range, a source that does not compile (the compiler's log in bpm_last_error), no function
+ * installed, n_burn < 0, no resident history (keep_history = 0), values beyond values_cap or of 2^31 elements or more, records or values
+ * larger than the free device memory (the message names the requirement). */
+int bpm_check_device_function(const char* hip_source, int32_t n_out, const char* arch, char* log, int64_t log_cap);
+int bpm_set_device_function(bpm_handle_t h, const char* hip_source, int32_t n_out, const double* params, int32_t n_params);
+int bpm_derive(bpm_handle_t h, int64_t n_burn, int64_t* counts, double* sums, int64_t* n_rows, int64_t* n_first, double* values,
+               int64_t values_cap);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
