@@ -125,6 +125,7 @@ TEST_SIGNATURES = {
     "bpm_debug_destroy_plan": (C.c_int, [C.c_int32, C.c_int32]),
     "bpm_debug_fail_queue": (C.c_int, [_H, C.c_int32]),
     "bpm_debug_kernarg_layout": (C.c_int, [C.c_int32, _P(C.c_char_p), _ip, _P(C.c_int64), _P(C.c_int64)]),
+    "bpm_debug_check_user_fused": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64]),
     "bpm_debug_queue_pad": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int64)]),
     "bpm_debug_coherence_probe": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int64)]),
     "bpm_selftest_philox": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, _u32p, _u32p]),
@@ -155,7 +156,8 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/user_likelihood.h", "csrc/derived.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/user_likelihood.h", "csrc/derived.h",
+            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_target.h", "csrc/derive_rows.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

@@ -1,0 +1,72 @@
+// DEVICE CODE OF A RUN-TIME PROGRAM (hiprtc; derived.h: compile_device_function includes it behind the caller's source).
+// bpm_derive_rows: the window reduction around the caller's `derive` -- stage a tile of rows in LDS, call derive per row, add the outputs into
+// trace_acc.h's accumulators, merge by a halving tree; derived.h describes the three steps and the LDS layout, and holds the host's view of the
+// parameter list (DeriveRowsKernel).
+
+typedef unsigned int uint32_t; typedef unsigned long uint64_t;
+#define BPM_VARIANT_NS derived
+#include "trace_acc.h"
+extern "C" __global__ void __launch_bounds__(256) bpm_derive_rows(const double* H, const double* LL, unsigned int ld, int d, unsigned long long lo,
+                                                                  unsigned long long hi, const double* params, unsigned int n_out, unsigned int R,
+                                                                  unsigned int ldp, unsigned int ldo, double* rec, unsigned long long n_rec, double* values) {
+    using namespace bpm;
+    static_assert(sizeof(TrAcc) == 48, "the host sizes the merge tree by 48 bytes per accumulator");
+    extern __shared__ __attribute__((aligned(16))) double bpm_lds[];
+    double* const s_ll = bpm_lds + (unsigned long long)R * ldp;
+    double* const s_out = s_ll + R;
+    const unsigned int tid = threadIdx.x, cpw = 256u / n_out, m = tid % n_out, a = tid / n_out;
+    const unsigned long long chunk = (hi - lo + gridDim.x - 1) / gridDim.x;
+    unsigned long long r0 = lo + (unsigned long long)blockIdx.x * chunk;
+    r0 = r0 < hi ? r0 : hi;
+    const unsigned long long r1 = r0 + chunk < hi ? r0 + chunk : hi;
+    typedef double bpm_d2 __attribute__((ext_vector_type(2)));
+    TrAcc acc;
+    tr_init(acc);
+    for (unsigned long long t0 = r0; t0 < r1; t0 += R) {
+        const unsigned int nr = (unsigned int)(r1 - t0 < R ? r1 - t0 : R);
+        if (ldp != 0u) {
+            // pair k of the region -> row k / (ld / 2), 8 pairs per thread in flight
+            const bpm_d2* src = (const bpm_d2*)(H + t0 * ld);
+            const unsigned int h = ld >> 1, total = nr * h;
+            for (unsigned int k0 = 0; k0 < total; k0 += 256u * 8u) {
+                bpm_d2 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const unsigned int k = k0 + u * 256u + tid; v[u] = src[k < total ? k : total - 1u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const unsigned int k = k0 + u * 256u + tid;
+                    if (k < total) {
+                        const unsigned int r = k / h, j = 2u * (k - r * h);
+                        if (j < (unsigned int)d) bpm_lds[r * ldp + j] = v[u].x;
+                        if (j + 1u < (unsigned int)d) bpm_lds[r * ldp + j + 1u] = v[u].y;
+                    }
+                }
+            }
+        }
+        if (tid < nr) s_ll[tid] = LL[t0 + tid];
+        __syncthreads();
+        if (tid < nr) {
+            double* o = s_out + tid * ldo;
+            for (unsigned int q = 0; q < n_out; ++q) o[q] = 0.0;
+            derive(ldp != 0u ? bpm_lds + tid * ldp : H + (t0 + tid) * ld, d, s_ll[tid], params, o);
+        }
+        __syncthreads();
+        if (a < cpw)
+            for (unsigned int r = a; r < nr; r += cpw) tr_add(acc, s_out[r * ldo + m]);
+        if (values != nullptr) {
+            double* dst = values + (t0 - lo) * n_out;
+            for (unsigned int i = tid; i < nr * n_out; i += 256u) { const unsigned int r = i / n_out; dst[i] = s_out[r * ldo + (i - r * n_out)]; }
+        }
+    }
+    __syncthreads();
+    TrAcc* s_acc = reinterpret_cast<TrAcc*>(bpm_lds);
+    s_acc[tid] = acc;
+    __syncthreads();
+    unsigned int top = 1u;
+    while (top < cpw) top <<= 1;
+    for (unsigned int s = top >> 1; s > 0u; s >>= 1) {      // the cpw lanes of an output: a halving tree, the same pairs every time
+        if (a < s && a + s < cpw) tr_merge(s_acc[tid], s_acc[tid + s * n_out]);
+        __syncthreads();
+    }
+    if (a == 0u) tr_store(rec, n_rec, (unsigned long long)blockIdx.x * n_out + m, s_acc[tid]);
+}

@@ -292,6 +292,17 @@ static int launch_side(hipStream_t stream, void (*kernel)(P...), const char* nam
     if (then != Then::KEEP) d.mark_acquire(then == Then::ACQUIRE);
     return 0;
 }
+// A kernel of a module compiled at run time (user_likelihood.h, derived.h), on `stream`: K is its parameter list as a function type, declared once
+// beside the header that holds the kernel; the arguments are converted to exactly those types and the array of pointers is laid out from them.
+template <class K>
+struct ModuleLaunch;
+template <class... P>
+struct ModuleLaunch<void(P...)> {
+    static hipError_t on(hipStream_t stream, hipFunction_t fn, unsigned grid, unsigned block, unsigned lds_bytes, std::common_type_t<P>... args) {
+        void* ptrs[] = {static_cast<void*>(&args)...};
+        return hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, lds_bytes, stream, ptrs, nullptr);
+    }
+};
 static inline uint32_t grid_for(uint32_t n_items, int lpc) {
     const uint32_t cpw = (uint32_t)(block_for(lpc) / lpc);
     return (n_items + cpw - 1) / cpw;
@@ -482,6 +493,88 @@ struct HistorySnapshot {
     int check(const bpm_sampler* s, const char* who, const char* first_call) const;
 };
 
+// ---- what a program compiled at run time leaves on the device: owned from the moment it exists ------------------------------------------
+template <class T>
+static int dev_alloc(T** p, size_t n) {
+    HIPCK(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)));
+    return 0;
+}
+// A loaded code object: unloaded when its owner goes, unless leak()ed (bpm_destroy under a queue that may still run kernels).  The one place
+// that loads, looks up and unloads.
+struct Module {
+    hipModule_t mod = nullptr;
+    Module() = default;
+    Module(Module&& o) noexcept : mod(o.mod) { o.mod = nullptr; }
+    Module& operator=(Module&& o) noexcept {
+        if (this != &o) { unload(); mod = o.mod; o.mod = nullptr; }
+        return *this;
+    }
+    ~Module() { unload(); }
+    hipError_t load(const std::vector<char>& code) { unload(); return hipModuleLoadData(&mod, code.data()); }
+    hipFunction_t function(const std::string& name) const {      // null: not there (the HIP error is cleared)
+        hipFunction_t fn = nullptr;
+        if (hipModuleGetFunction(&fn, mod, name.c_str()) == hipSuccess && fn) return fn;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    void unload() { if (mod) (void)hipModuleUnload(mod); mod = nullptr; }
+    void leak() { mod = nullptr; }
+};
+// A caller's parameter block on the device: max(n, 1) doubles, zero-filled, then the caller's n -- enqueued on `stream`; the caller's array is
+// its own again once that stream has been waited for.
+struct DevParams {
+    double* p = nullptr;
+    DevParams() = default;
+    DevParams(DevParams&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevParams& operator=(DevParams&& o) noexcept {
+        if (this != &o) { release(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevParams() { release(); }
+    int upload(const double* src, int32_t n, hipStream_t stream) {
+        release();
+        CK(dev_alloc(&p, (size_t)std::max(n, 1)));
+        HIPCK(hipMemsetAsync(p, 0, (size_t)std::max(n, 1) * sizeof(double), stream));
+        if (n > 0) HIPCK(hipMemcpyAsync(p, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+    void leak() { p = nullptr; }
+};
+// The caller's ln_like_fn as a kernel compiled from HIP source (user_likelihood.h; bpm_set_device_likelihood): bpm_step then drives a host-callback sampler ...
+struct UserLikelihood {
+    Module mod;
+    hipFunction_t fn = nullptr;              // bpm_user_eval
+    DevParams params;
+    // ... and the update kernel itself compiled around it (user_likelihood.h: compile_user_fused): one launch per half generation; fn == nullptr: the three-kernel form
+    struct Fused {
+        Module mod;
+        hipFunction_t fn = nullptr;          // the general instantiation
+        hipFunction_t hot = nullptr;         // the steady-state one (HOT 1 / 2): launched when phase_args_hot(a, dream, with_plan, false) holds
+        hipFunction_t eval = nullptr;        // eval_ll_kernel with the same target: the current states' ln-likes by the update kernel's own arithmetic
+        hipFunction_t adapt = nullptr;       // DREAM's burn-in instantiation (HOT 3 / 4): level 1 of the CR reduction and the consumer-side fold inside the launch
+        unsigned block = 0, block_adapt = 0;
+        std::string names[3];                // their lowered names ([2]: the burn-in instantiation): what the library's own queue dispatches them by (DirectQueue::kernel_by_name)
+        bool dq = false;                     // ... and all were found among the loaded code objects
+        // the one way out: the queue forgets the names, then the module is unloaded
+        void drop(bpm::DirectQueue* q) {
+            if (mod.mod && q) for (const std::string& nm : names) q->forget_named(nm);
+            *this = Fused();
+        }
+    } fused;
+    std::string why;                         // why the fused form is not in use (bpm_get_device_likelihood_info)
+    void leak() { mod.leak(); params.leak(); fused.mod.leak(); }
+};
+// A caller's function of one sample, compiled around the window reduction of derived.h (bpm_set_device_function): kept until replaced or bpm_destroy
+struct DerivedFunction {
+    Module mod;
+    hipFunction_t fn = nullptr;              // bpm_derive_rows of THIS module: launched by handle, never looked up by name
+    std::string src;                         // the source bytes and n_out the module was built from: the same again only re-upload the parameters
+    int32_t n_out = 0;
+    DevParams params;
+    void leak() { mod.leak(); params.leak(); }
+};
+
 // ---- the sampler ------------------------------------------------------------------------
 struct bpm_sampler {
     bpm_config_t cfg{};
@@ -561,27 +654,8 @@ struct bpm_sampler {
     int64_t prop_active = 0;                 // its active work items
     bool prop_whole = false;                 // it was proposed through bpm_propose (caller-owned buffers): bpm_commit finishes it
     std::vector<uint8_t> prop_done;          // [prop_chunks] 1: the piece's ln-likes have been handed in
-    // the caller's ln_like_fn as a kernel compiled from HIP source (user_likelihood.h; bpm_set_device_likelihood): bpm_step then drives a host-callback sampler
-    hipModule_t user_mod = nullptr;
-    hipFunction_t user_fn = nullptr;
-    double* user_params = nullptr;
-    // ... and the update kernel itself compiled around it (user_likelihood.h: compile_user_fused): one launch per half generation; nullptr: the three-kernel form
-    hipModule_t user_fused_mod = nullptr;
-    hipFunction_t user_fused_fn = nullptr;     // the general instantiation
-    hipFunction_t user_fused_hot = nullptr;    // the steady-state one (HOT 1 / 2): launched when phase_args_hot(a, dream, with_plan, false) holds
-    hipFunction_t user_fused_eval = nullptr;   // eval_ll_kernel with the same target: the current states' ln-likes by the update kernel's own arithmetic
-    hipFunction_t user_fused_adapt = nullptr;  // DREAM's burn-in instantiation (HOT 3 / 4): level 1 of the CR reduction and the consumer-side fold inside the launch
-    unsigned user_fused_block_adapt = 0;
-    unsigned user_fused_block = 0;
-    std::string user_fused_names[3];         // their lowered names ([2]: the burn-in instantiation): what the library's own queue dispatches them by (DirectQueue::kernel_by_name)
-    bool user_fused_dq = false;              // ... and both were found among the loaded code objects
-    std::string user_fused_why;              // why the fused form is not in use (bpm_get_device_likelihood_info)
-    // a caller's function of one sample, compiled around the window reduction of derived.h (bpm_set_device_function): kept until replaced or bpm_destroy
-    hipModule_t derive_mod = nullptr;
-    hipFunction_t derive_fn = nullptr;        // bpm_derive_rows of THIS module: launched by handle, never looked up by name
-    std::string derive_src;                   // the source bytes and n_out the module was built from: the same again only re-upload the parameters
-    int32_t derive_n_out = 0;
-    double* derive_params = nullptr;
+    UserLikelihood like;                     // the caller's ln_like_fn given as HIP source (bpm_set_device_likelihood)
+    DerivedFunction derived;                 // the caller's function of one sample (bpm_set_device_function)
     double* aux_buf = nullptr;
     int32_t* ids_buf = nullptr;
     int32_t* trace_i32 = nullptr;      // per-chain decision trace (bpm_set_trace: test variant only; always null in the product library)
@@ -774,12 +848,6 @@ int StreamSection::end() {
 
 static int set_device(bpm_sampler* s) {
     HIPCK(hipSetDevice(s->cfg.device));
-    return 0;
-}
-
-template <class T>
-static int dev_alloc(T** p, size_t n) {
-    HIPCK(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)));
     return 0;
 }
 
@@ -1153,8 +1221,9 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     if (s->h_props) (void)hipHostFree(s->h_props);
     if (s->h_ll) (void)hipHostFree(s->h_ll);
     for (hipEvent_t e : s->chunk_ev) if (e) (void)hipEventDestroy(e);
-    if (free_buffers) { if (s->user_mod) (void)hipModuleUnload(s->user_mod); if (s->user_fused_mod) { if (s->dq) for (const std::string& nm : s->user_fused_names) s->dq->forget_named(nm); (void)hipModuleUnload(s->user_fused_mod); } if (s->user_params) (void)hipFree(s->user_params);
-                        if (s->derive_mod) (void)hipModuleUnload(s->derive_mod); if (s->derive_params) (void)hipFree(s->derive_params); }
+    // (the run-time modules and their parameter blocks go the way of the buffers)
+    if (free_buffers) { s->like.fused.drop(s->dq); s->like = UserLikelihood(); s->derived = DerivedFunction(); }
+    else { s->like.leak(); s->derived.leak(); }
     for (auto& B : s->tb) {
         if (B.count_h) (void)hipHostFree(B.count_h);
         if (B.built) (void)hipEventDestroy(B.built);
@@ -1863,7 +1932,7 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
     s->gen_fold_planned = false;
     if (s->cr_p1) s->cr_p1_cur = s->cr_p1 + (size_t)(s->t_abs & 1) * 2 * MAX_CR * s->cr_n1;
     // (a host-callback sampler: only while the update kernel compiled around its HIP-source likelihood drives it -- Dispatch::user_cur -- and has the burn-in flavour)
-    if (s->gen_cr_reduce && dream && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || (g_disp.user_cur == s && s->user_fused_adapt != nullptr && (s->cur_args[0].rec_tab != nullptr) == s->plan_on)) &&
+    if (s->gen_cr_reduce && dream && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || (g_disp.user_cur == s && s->like.fused.adapt != nullptr && (s->cur_args[0].rec_tab != nullptr) == s->plan_on)) &&
         s->shape.idx != SHAPE_WIDE && crp_shape(s->shape.lpc, s->shape.dpl) &&
         !test_path("nohot") && !test_path("crslots")) {
         bool ok = true;
@@ -2306,30 +2375,30 @@ static bool group_goes_direct(const Group& g, bool push, bool& group_direct) {
 }
 
 static int run_generations_user(bpm_sampler* s, int64_t n_gens);      // (a host-callback sampler with a device likelihood: below, beside the host-callback core)
-// the update kernel compiled at run time around a caller's likelihood (bpm_sampler::user_fused_fn): the general instantiation's launch, from a module
+// the update kernel compiled at run time around a caller's likelihood (bpm_sampler::like.fused): the general instantiation's launch, from a module
 static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
     Dispatch& d = g_disp;
     bpm_sampler* s = d.user_cur;
-    if (!s || !s->user_fused_fn) { d.user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
+    if (!s || !s->like.fused.fn) { d.user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
     PhaseArgs ka = a;
-    ka.tparams = s->user_params;                   // the caller's parameter block is the target's
+    ka.tparams = s->like.params.p;                   // the caller's parameter block is the target's
     static const bool no_hot = test_path("nohot");
     // burn-in: prepare_generation handed this launch the level-1 sums to write (cr_part1) only after phase_args_hot(a, true, plan, true) held for BOTH launches
-    const bool adapt = a.cr_part1 != nullptr && s->user_fused_adapt != nullptr;
+    const bool adapt = a.cr_part1 != nullptr && s->like.fused.adapt != nullptr;
     if (adapt) { ++d.crp_launched; if (a.cr_fold_part != nullptr) ++d.crfold_launched; }
-    const unsigned block = adapt ? s->user_fused_block_adapt : s->user_fused_block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
+    const unsigned block = adapt ? s->like.fused.block_adapt : s->like.fused.block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
     // (the steady-state instantiation was compiled for update records exactly when this sampler builds them: HOT 1 / HOT 2)
-    const bool hot = !adapt && !no_hot && s->user_fused_hot && (a.rec_tab != nullptr) == s->plan_on && phase_args_hot(a, s->cfg.algo == BPM_ALGO_DREAM, a.rec_tab != nullptr, false);
+    const bool hot = !adapt && !no_hot && s->like.fused.hot && (a.rec_tab != nullptr) == s->plan_on && phase_args_hot(a, s->cfg.algo == BPM_ALGO_DREAM, a.rec_tab != nullptr, false);
     // (launch_packed's two paths; the module's kernels take the argument block alone, no preloaded leading arguments)
-    if (d.dq) return update_packet(d, d.dq->kernel_by_name(s->user_fused_names[adapt ? 2 : (hot ? 1 : 0)]), grid, block, &ka, sizeof(ka));
-    update_on_stream(d, adapt ? s->user_fused_adapt : (hot ? s->user_fused_hot : s->user_fused_fn), grid, block, &ka, sizeof(ka), st);
+    if (d.dq) return update_packet(d, d.dq->kernel_by_name(s->like.fused.names[adapt ? 2 : (hot ? 1 : 0)]), grid, block, &ka, sizeof(ka));
+    update_on_stream(d, adapt ? s->like.fused.adapt : (hot ? s->like.fused.hot : s->like.fused.fn), grid, block, &ka, sizeof(ka), st);
 }
 static int run_generations(const Group& g, int64_t n_gens) {
     bpm_sampler* s0 = g.h[0];
     // a caller's likelihood compiled from HIP source (bpm_set_device_likelihood): the update kernel compiled around it runs the ordinary generation loop
     // (one launch per half generation, on the HIP stream); without it, the proposal / likelihood / commit kernels of run_generations_user
-    const bool user_fused = s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->user_fused_fn != nullptr && g.R == 1;
-    if (s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->user_fn && g.R == 1 && !user_fused) return run_generations_user(s0, n_gens);
+    const bool user_fused = s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->like.fused.fn != nullptr && g.R == 1;
+    if (s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->like.fn && g.R == 1 && !user_fused) return run_generations_user(s0, n_gens);
     if (user_fused && s0->world > 1 && !s0->comm) return fail("bpm_step: a host-callback sampler of a world needs an RCCL communicator (create it with a unique id)");
     PhaseLaunch fn = user_fused ? launch_user_fused : pick_fused(s0);
     if (!fn) return fail("bpm_step: host-callback target must be driven with bpm_propose / bpm_commit (or give it a device likelihood: bpm_set_device_likelihood)");
@@ -2354,7 +2423,7 @@ static int run_generations(const Group& g, int64_t n_gens) {
             // With the push exchange a rank of a world runs on its own queue too: nothing of its generation loop is a collective call.
             bool group_direct = false;
             // (a run-time module's kernels go through the library's queue when it found them by name, else on the stream)
-            const bool direct = group_goes_direct(g, push, group_direct) && (!user_fused || s0->user_fused_dq);
+            const bool direct = group_goes_direct(g, push, group_direct) && (!user_fused || s0->like.fused.dq);
             for (int r = 0; r < g.R; ++r) {
                 bpm_sampler* s = g.h[r];
                 if (direct && !s->dq_active) {
@@ -3652,30 +3721,24 @@ extern "C" int bpm_commit_end(bpm_handle_t s) {
 // ---- the caller's likelihood as a kernel compiled from HIP source (user_likelihood.h): proposal kernel -> the caller's kernel -> commit kernel, all on the
 // sampler's stream, no host code inside a generation.  samplers.py:36-43 evaluates ln_like_fn(theta, **ln_kwargs) row by row on the host; here `params` takes
 // the place of ln_kwargs.
-static bpm::Hiprtc g_hiprtc;
-static std::mutex g_hiprtc_mu;      // (the loader's state and hiprtc's own: one compilation at a time per process)
+static constexpr size_t N_EMBEDDED = sizeof(bpm_embedded) / sizeof(bpm_embedded[0]);      // (embedded_src.h: the headers a run-time program may include)
 static int user_eval_launch(bpm_sampler* s, const double* rows, const int32_t* ids, uint32_t n, double* out) {
     if (n == 0) return 0;
-    int n_i = (int)n, ld_i = (int)s->ld, d_i = (int)s->dim, rpb = 0, ldp = 0;
+    int rpb = 0, ldp = 0;
     bpm::user_eval_tile(s->dim, rpb, ldp);
-    const double* params = s->user_params;
-    void* args[] = {(void*)&rows, (void*)&ids, (void*)&n_i, (void*)&ld_i, (void*)&d_i, (void*)&params, (void*)&out, (void*)&rpb, (void*)&ldp};
     const unsigned block = (unsigned)bpm::USER_EVAL_BLOCK, per = rpb > 0 ? (unsigned)rpb : block, grid = (n + per - 1u) / per;
     const unsigned lds = rpb > 0 ? (unsigned)rpb * (unsigned)ldp * (unsigned)sizeof(double) : 0u;
-    HIPCK(hipModuleLaunchKernel(s->user_fn, grid, 1, 1, block, 1, 1, lds, s->stream, args, nullptr));
+    HIPCK(ModuleLaunch<bpm::UserEvalKernel>::on(s->stream, s->like.fn, grid, block, lds, rows, ids, (int)n, (int)s->ld, (int)s->dim, s->like.params.p, out, rpb, ldp));
     return 0;
 }
 // ln-like of the local chains' CURRENT states from the installed device likelihood (what bpm_set_loglike takes from the host)
 static int user_refresh_ll(bpm_sampler* s) {
-    if (s->user_fused_eval) {      // (the update kernel was compiled around the likelihood: the same Target::eval, the same bits)
-        const double* X = s->G + (uint64_t)s->rank * s->L.blk;
-        uint32_t n = s->n_local, ld = s->ld, dim = s->dim;
-        const double* tp = s->user_params;
-        double* out = s->ll;
-        void* args[] = {(void*)&X, (void*)&n, (void*)&ld, (void*)&dim, (void*)&tp, (void*)&out};
-        HIPCK(hipModuleLaunchKernel(s->user_fused_eval, grid_for(n, s->shape.lpc), 1, 1, s->user_fused_block, 1, 1, 0, s->stream, args, nullptr));
+    const double* X = s->G + (uint64_t)s->rank * s->L.blk;
+    if (s->like.fused.eval) {      // (the update kernel was compiled around the likelihood: the same Target::eval, the same bits)
+        HIPCK(ModuleLaunch<bpm::UserEvalLlKernel>::on(s->stream, s->like.fused.eval, grid_for(s->n_local, s->shape.lpc), s->like.fused.block, 0, X, s->n_local, s->ld,
+                                                      s->dim, s->like.params.p, s->ll));
     } else {
-        CK(user_eval_launch(s, s->G + (uint64_t)s->rank * s->L.blk, nullptr, s->n_local, s->ll));
+        CK(user_eval_launch(s, X, nullptr, s->n_local, s->ll));
     }
     if (s->hist_rows >= 1 && s->hist_rows == s->rows_logical)
         HIPCK(hipMemcpyAsync(s->llhist + (size_t)(s->hist_rows - 1) * s->n_local, s->ll, s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
@@ -3708,14 +3771,65 @@ static int run_generations_user(bpm_sampler* s, int64_t n_gens) {
 extern "C" int bpm_check_device_likelihood(const char* hip_source, const char* arch, char* log, int64_t log_cap) {
     if (!hip_source) return fail("bpm_check_device_likelihood: null source");
     std::vector<char> code;
-    std::string why;
-    { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_user_likelihood(g_hiprtc, hip_source, (arch && *arch) ? arch : "gfx950", code); }
-    if (log && log_cap > 0) {
-        const size_t n = std::min(why.size(), (size_t)log_cap - 1);
-        std::memcpy(log, why.data(), n);
-        log[n] = '\0';
-    }
+    const std::string why = bpm::compile_user_likelihood(hip_source, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
+    bpm::copy_text(why, log, log_cap);
     return why.empty() ? 0 : fail("bpm_check_device_likelihood: " + why);
+}
+
+#ifdef BPM_TEST_HOOKS
+static constexpr bool USER_FUSED_HOOKS = true;
+// Test hook: the update kernel's program around `hip_source` (compile_user_fused, as bpm_set_device_likelihood builds it for a sampler of this algorithm
+// and shape) compiled with no device in the machine; the reason comes back in `log` like bpm_check_device_likelihood's
+extern "C" int bpm_debug_check_user_fused(const char* hip_source, int32_t algo, int32_t lpc, int32_t dpl, int32_t np, int32_t dim, int32_t hot, const char* arch,
+                                          char* log, int64_t log_cap) {
+    if (!hip_source) return fail("bpm_debug_check_user_fused: null source");
+    std::vector<char> code;
+    std::string lowered[4];
+    const std::string why = bpm::compile_user_fused(hip_source, "v_user_check", (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED,
+                                                    algo == BPM_ALGO_DREAM ? ALGO_DREAM : ALGO_DEMC, lpc, dpl, np, (uint32_t)dim, USER_FUSED_HOOKS, hot, code, lowered);
+    bpm::copy_text(why, log, log_cap);
+    return why.empty() ? 0 : fail("bpm_debug_check_user_fused: " + why);
+}
+#else
+static constexpr bool USER_FUSED_HOOKS = false;
+#endif
+// The faster form: the update kernel itself compiled around the likelihood, built whole into `f` on the sampler's device.  -> "" or why it cannot be
+// used; whatever goes wrong leaves nothing behind (the module is owned from the moment it is loaded).
+static std::string build_user_fused(bpm_sampler* s, const char* hip_source, const char* arch, UserLikelihood::Fused& f) {
+    const int algo = s->cfg.algo == BPM_ALGO_DREAM ? ALGO_DREAM : ALGO_DEMC;
+    const int np = s->cfg.algo != BPM_ALGO_DREAM ? 1 : (s->cfg.del_pairs == 3 ? 3 : 0);
+    static std::atomic<int> module_no{0};
+    const std::string ns = "v_user" + std::to_string(module_no.fetch_add(1));
+    std::vector<char> code;
+    std::string lowered[4];
+    const std::string why = bpm::compile_user_fused(hip_source, ns, arch, bpm_embedded, N_EMBEDDED, algo, s->shape.lpc, s->shape.dpl, np, s->dim, USER_FUSED_HOOKS,
+                                                    s->plan_on ? 1 : 2, code, lowered);
+    if (!why.empty()) return why;
+    if (f.mod.load(code) != hipSuccess) { (void)hipGetLastError(); return "hipModuleLoadData failed"; }
+    f.fn = f.mod.function(lowered[0]);
+    f.hot = f.mod.function(lowered[1]);
+    f.eval = f.mod.function(lowered[2]);
+    const hipFunction_t fs = f.mod.function("bpm_user_sizeof");
+    if (!f.fn || !f.hot || !f.eval || !fs) return "the compiled module lacks " + lowered[0];
+    if (!lowered[3].empty()) f.adapt = f.mod.function(lowered[3]);
+    // the module's view of the argument block must be this library's
+    DevTemp<unsigned int> d_out;
+    unsigned int h_out[3] = {0u, 0u, 0u};
+    if (d_out.alloc(3) != 0) return "out of device memory";
+    const bool ran = ModuleLaunch<bpm::UserSizeofKernel>::on(s->stream, fs, 1, 1, 0, d_out.p) == hipSuccess &&
+                     hipMemcpyAsync(h_out, d_out.p, sizeof(h_out), hipMemcpyDeviceToHost, s->stream) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess;
+    if (!ran || h_out[0] != (unsigned)sizeof(PhaseArgs) || h_out[1] != (unsigned)block_for(s->shape.lpc)) {
+        (void)hipGetLastError();
+        return "the module's argument block differs from the library's (" + std::to_string(h_out[0]) + " against " + std::to_string(sizeof(PhaseArgs)) + " bytes)";
+    }
+    f.block = h_out[1];
+    f.block_adapt = h_out[2];
+    if (f.adapt && h_out[2] != (unsigned)block_for_hot(s->shape.lpc, 3, s->shape.dpl)) f.adapt = nullptr;
+    f.names[0] = lowered[0]; f.names[1] = lowered[1]; f.names[2] = lowered[3];
+    static const bool dq_wanted = !(getenv("BPM_USER_FUSED") && atoi(getenv("BPM_USER_FUSED")) == 2);      // (2: fused, but launched on the stream -- A/B)
+    f.dq = dq_wanted && s->dq && s->dq->kernel_by_name(lowered[0]) != nullptr && s->dq->kernel_by_name(lowered[1]) != nullptr &&
+           (!f.adapt || s->dq->kernel_by_name(lowered[3]) != nullptr);
+    return "";
 }
 
 extern "C" int bpm_set_device_likelihood(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params) {
@@ -3726,106 +3840,46 @@ extern "C" int bpm_set_device_likelihood(bpm_handle_t s, const char* hip_source,
     if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_device_likelihood: bad argument");
     hipDeviceProp_t prop;
     HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
+    // the new likelihood is built beside the installed one, which stays whole until nothing can fail any more ...
     std::vector<char> code;
-    std::string why;
-    { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_user_likelihood(g_hiprtc, hip_source, prop.gcnArchName, code); }
+    const std::string why = bpm::compile_user_likelihood(hip_source, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
     if (!why.empty()) return fail("bpm_set_device_likelihood: " + why);
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
-    HIPCK(hipModuleLoadData(&mod, code.data()));
-    if (hipModuleGetFunction(&fn, mod, "bpm_user_eval") != hipSuccess || !fn) {
-        (void)hipGetLastError();
-        (void)hipModuleUnload(mod);
-        return fail("bpm_set_device_likelihood: the compiled module has no bpm_user_eval kernel");
-    }
-    HIPCK(hipStreamSynchronize(s->stream));                      // (a previous likelihood's launches are done)
-    if (s->user_mod) (void)hipModuleUnload(s->user_mod);
-    if (s->user_params) { (void)hipFree(s->user_params); s->user_params = nullptr; }
-    s->user_mod = mod; s->user_fn = fn;
-    CK(dev_alloc(&s->user_params, (size_t)std::max(n_params, 1)));
-    HIPCK(hipMemsetAsync(s->user_params, 0, (size_t)std::max(n_params, 1) * sizeof(double), s->stream));
-    if (n_params > 0) HIPCK(hipMemcpyAsync(s->user_params, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    // the faster form: the update kernel itself compiled around the likelihood.  Whatever goes wrong here leaves the three-kernel form in place
-    // (bpm_get_device_likelihood_info says which is in use and why).  BPM_USER_FUSED=0: not attempted (A/B, tests).
-    if (s->user_fused_mod) {
-        if (s->dq) for (const std::string& nm : s->user_fused_names) s->dq->forget_named(nm);
-        (void)hipModuleUnload(s->user_fused_mod); s->user_fused_mod = nullptr;
-    }
-    s->user_fused_fn = nullptr; s->user_fused_hot = nullptr; s->user_fused_eval = nullptr; s->user_fused_adapt = nullptr; s->user_fused_dq = false; s->user_fused_why.clear();
+    UserLikelihood next;
+    HIPCK(next.mod.load(code));
+    next.fn = next.mod.function("bpm_user_eval");
+    if (!next.fn) return fail("bpm_set_device_likelihood: the compiled module has no bpm_user_eval kernel");
+    CK(next.params.upload(params, n_params, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));                      // (a previous likelihood's launches are done, the parameters are in place)
+    // ... and replaces it in one step: the old update kernel leaves with the old likelihood
+    s->like.fused.drop(s->dq);
+    s->like = std::move(next);
     CK(user_refresh_ll(s));      // (by the kernel of its own; again below by the update kernel's arithmetic once that one is built)
+    // the faster form.  Whatever goes wrong with it leaves the three-kernel form in place (bpm_get_device_likelihood_info says which is in use
+    // and why).  BPM_USER_FUSED=0: not attempted (A/B, tests).
     const bool want_fused = !(getenv("BPM_USER_FUSED") && atoi(getenv("BPM_USER_FUSED")) == 0);      // (read at every call: a test switches it)
-    if (!want_fused) { s->user_fused_why = "BPM_USER_FUSED=0"; return 0; }
-    if (s->shape.idx == SHAPE_WIDE) { s->user_fused_why = "rows wider than 512 coordinates run on the looped kernel, which has no run-time form"; return 0; }
-    {
-        const int algo = s->cfg.algo == BPM_ALGO_DREAM ? ALGO_DREAM : ALGO_DEMC;
-        const int np = s->cfg.algo != BPM_ALGO_DREAM ? 1 : (s->cfg.del_pairs == 3 ? 3 : 0);
-#ifdef BPM_TEST_HOOKS
-        const bool hooks = true;
-#else
-        const bool hooks = false;
-#endif
-        std::vector<char> fcode;
-        std::string lowered[4], fwhy, ns;
-        { std::lock_guard<std::mutex> lk(g_hiprtc_mu);
-          static std::atomic<int> module_no{0};
-          ns = "v_user" + std::to_string(module_no.fetch_add(1));
-          fwhy = bpm::compile_user_fused(g_hiprtc, hip_source, ns, prop.gcnArchName, bpm_src_kernels_h, bpm_src_philox_h, algo, s->shape.lpc, s->shape.dpl, np, s->dim, hooks,
-                                         s->plan_on ? 1 : 2, fcode, lowered); }
-        if (!fwhy.empty()) { s->user_fused_why = fwhy; return 0; }
-        hipModule_t fm = nullptr;
-        hipFunction_t ff = nullptr, fh = nullptr, fs = nullptr, fe = nullptr, fa = nullptr;
-        if (hipModuleLoadData(&fm, fcode.data()) != hipSuccess) { (void)hipGetLastError(); s->user_fused_why = "hipModuleLoadData failed"; return 0; }
-        if (hipModuleGetFunction(&ff, fm, lowered[0].c_str()) != hipSuccess || hipModuleGetFunction(&fh, fm, lowered[1].c_str()) != hipSuccess ||
-            hipModuleGetFunction(&fe, fm, lowered[2].c_str()) != hipSuccess || hipModuleGetFunction(&fs, fm, "bpm_user_sizeof") != hipSuccess || !ff || !fh || !fe || !fs) {
-            (void)hipGetLastError(); (void)hipModuleUnload(fm);
-            s->user_fused_why = "the compiled module lacks " + lowered[0];
-            return 0;
-        }
-        // the module's view of the argument block must be this library's
-        unsigned int* d_out = nullptr;
-        unsigned int h_out[3] = {0u, 0u, 0u};
-        if (!lowered[3].empty() && (hipModuleGetFunction(&fa, fm, lowered[3].c_str()) != hipSuccess || !fa)) { (void)hipGetLastError(); fa = nullptr; }
-        if (dev_alloc(&d_out, 3) != 0) { (void)hipModuleUnload(fm); s->user_fused_why = "out of device memory"; return 0; }
-        void* sargs[] = {(void*)&d_out};
-        const bool ran = hipModuleLaunchKernel(fs, 1, 1, 1, 1, 1, 1, 0, s->stream, sargs, nullptr) == hipSuccess &&
-                         hipMemcpyAsync(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, s->stream) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess;
-        (void)hipFree(d_out);
-        if (!ran || h_out[0] != (unsigned)sizeof(PhaseArgs) || h_out[1] != (unsigned)block_for(s->shape.lpc)) {
-            (void)hipGetLastError(); (void)hipModuleUnload(fm);
-            s->user_fused_why = "the module's argument block differs from the library's (" + std::to_string(h_out[0]) + " against " + std::to_string(sizeof(PhaseArgs)) + " bytes)";
-            return 0;
-        }
-        s->user_fused_mod = fm; s->user_fused_fn = ff; s->user_fused_hot = fh; s->user_fused_block = h_out[1];
-        s->user_fused_names[0] = lowered[0]; s->user_fused_names[1] = lowered[1];
-        s->user_fused_eval = fe;
-        s->user_fused_adapt = fa; s->user_fused_block_adapt = h_out[2]; s->user_fused_names[2] = lowered[3];
-        if (fa && h_out[2] != (unsigned)block_for_hot(s->shape.lpc, 3, s->shape.dpl)) s->user_fused_adapt = nullptr;
-        static const bool dq_wanted = !(getenv("BPM_USER_FUSED") && atoi(getenv("BPM_USER_FUSED")) == 2);      // (2: fused, but launched on the stream -- A/B)
-        s->user_fused_dq = dq_wanted && s->dq && s->dq->kernel_by_name(lowered[0]) != nullptr && s->dq->kernel_by_name(lowered[1]) != nullptr &&
-                           (!s->user_fused_adapt || s->dq->kernel_by_name(lowered[3]) != nullptr);
-        CK(user_refresh_ll(s));      // (again, now by the update kernel's own arithmetic: the per-coordinate form adds in the kernel's reduction order)
-    }
-    return 0;
+    UserLikelihood::Fused fused;
+    s->like.why = !want_fused ? "BPM_USER_FUSED=0"
+                  : s->shape.idx == SHAPE_WIDE ? "rows wider than 512 coordinates run on the looped kernel, which has no run-time form"
+                                               : build_user_fused(s, hip_source, prop.gcnArchName, fused);
+    if (!s->like.why.empty()) return 0;
+    s->like.fused = std::move(fused);
+    return user_refresh_ll(s);      // (again, now by the update kernel's own arithmetic: the per-coordinate form adds in the kernel's reduction order)
 }
 
 // which form of the device likelihood runs: *fused = 1 the update kernel compiled around it (one launch per half generation), 0 the three-kernel form
 // (then `why`, if given, says why: up to why_cap - 1 characters); error when no device likelihood is installed
 extern "C" int bpm_get_device_likelihood_info(bpm_handle_t s, int32_t* fused, char* why, int64_t why_cap) {
     CK(check_handle(s));
-    if (!s->user_fn) return fail("bpm_get_device_likelihood_info: no device likelihood installed (bpm_set_device_likelihood)");
-    if (fused) *fused = s->user_fused_fn ? 1 : 0;
-    if (why && why_cap > 0) {
-        const size_t n = std::min(s->user_fused_why.size(), (size_t)why_cap - 1);
-        std::memcpy(why, s->user_fused_why.data(), n);
-        why[n] = '\0';
-    }
+    if (!s->like.fn) return fail("bpm_get_device_likelihood_info: no device likelihood installed (bpm_set_device_likelihood)");
+    if (fused) *fused = s->like.fused.fn ? 1 : 0;
+    bpm::copy_text(s->like.why, why, why_cap);
     return 0;
 }
 
 extern "C" int bpm_refresh_device_loglike(bpm_handle_t s) {
     CK(check_handle(s));
     CK(set_device(s));
-    if (!s->user_fn) return fail("bpm_refresh_device_loglike: no device likelihood installed (bpm_set_device_likelihood)");
+    if (!s->like.fn) return fail("bpm_refresh_device_loglike: no device likelihood installed (bpm_set_device_likelihood)");
     return user_refresh_ll(s);
 }
 
@@ -3842,13 +3896,8 @@ extern "C" int bpm_check_device_function(const char* hip_source, int32_t n_out, 
     if (!hip_source) return fail("bpm_check_device_function: null source");
     CK(check_n_out("bpm_check_device_function", n_out));
     std::vector<char> code;
-    std::string why;
-    { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_device_function(g_hiprtc, hip_source, (arch && *arch) ? arch : "gfx950", bpm_src_trace_acc_h, code); }
-    if (log && log_cap > 0) {
-        const size_t n = std::min(why.size(), (size_t)log_cap - 1);
-        std::memcpy(log, why.data(), n);
-        log[n] = '\0';
-    }
+    const std::string why = bpm::compile_device_function(hip_source, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
+    bpm::copy_text(why, log, log_cap);
     return why.empty() ? 0 : fail("bpm_check_device_function: " + why);
 }
 
@@ -3857,31 +3906,25 @@ extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, i
     CK(set_device(s));
     if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_device_function: bad argument");
     CK(check_n_out("bpm_set_device_function", n_out));
-    if (!s->derive_fn || s->derive_n_out != n_out || s->derive_src != hip_source) {
+    // built beside the installed function, which stays whole until nothing can fail any more; the same source bytes and n_out: the parameters only
+    const bool rebuild = !s->derived.fn || s->derived.n_out != n_out || s->derived.src != hip_source;
+    DerivedFunction next;
+    if (rebuild) {
         hipDeviceProp_t prop;
         HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
         std::vector<char> code;
-        std::string why;
-        { std::lock_guard<std::mutex> lk(g_hiprtc_mu); why = bpm::compile_device_function(g_hiprtc, hip_source, prop.gcnArchName, bpm_src_trace_acc_h, code); }
+        const std::string why = bpm::compile_device_function(hip_source, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
         if (!why.empty()) return fail("bpm_set_device_function: " + why);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        HIPCK(hipModuleLoadData(&mod, code.data()));
-        if (hipModuleGetFunction(&fn, mod, "bpm_derive_rows") != hipSuccess || !fn) {
-            (void)hipGetLastError();
-            (void)hipModuleUnload(mod);
-            return fail("bpm_set_device_function: the compiled module has no bpm_derive_rows kernel");
-        }
-        HIPCK(hipStreamSynchronize(s->stream));                      // (a previous function's launches are done)
-        if (s->derive_mod) (void)hipModuleUnload(s->derive_mod);
-        s->derive_mod = mod; s->derive_fn = fn; s->derive_n_out = n_out; s->derive_src = hip_source;
+        HIPCK(next.mod.load(code));
+        next.fn = next.mod.function("bpm_derive_rows");
+        if (!next.fn) return fail("bpm_set_device_function: the compiled module has no bpm_derive_rows kernel");
+        next.src = hip_source;
+        next.n_out = n_out;
     }
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (s->derive_params) { (void)hipFree(s->derive_params); s->derive_params = nullptr; }
-    CK(dev_alloc(&s->derive_params, (size_t)std::max(n_params, 1)));
-    HIPCK(hipMemsetAsync(s->derive_params, 0, (size_t)std::max(n_params, 1) * sizeof(double), s->stream));
-    if (n_params > 0) HIPCK(hipMemcpyAsync(s->derive_params, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                          // (`params` is the caller's again)
+    CK(next.params.upload(params, n_params, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));                          // (a previous function's launches are done, and `params` is the caller's again)
+    if (rebuild) s->derived = std::move(next);
+    else s->derived.params = std::move(next.params);
     return 0;
 }
 
@@ -3895,12 +3938,12 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
     CK(set_device(s));
     if (!counts || !sums || !n_rows || !n_first) return fail("bpm_derive: null argument");
     if (n_burn < 0) return fail("bpm_derive: n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
-    if (!s->derive_fn) return fail("bpm_derive: no device function installed (bpm_set_device_function)");
+    if (!s->derived.fn) return fail("bpm_derive: no device function installed (bpm_set_device_function)");
     CK(require_resident_history(s, "bpm_derive"));
     uint64_t lo = 0, hi = 0;
     CK(super_chain_window(s, n_burn, &lo, &hi));
     const uint64_t rows = hi - lo;
-    const uint32_t n_out = (uint32_t)s->derive_n_out;
+    const uint32_t n_out = (uint32_t)s->derived.n_out;
     *n_rows = (int64_t)rows;
     *n_first = (int64_t)(rows % s->n_local);
     std::fill(counts, counts + 2 * (size_t)n_out, (int64_t)0);
@@ -3930,19 +3973,8 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
     DevTemp<double> b, v;
     CK(b.alloc(o_fold + (parts > 1 ? (size_t)TR_F_BINS * n_out : 0), "bpm_derive", "the part records of " + std::to_string((unsigned long long)parts) + " workgroups"));
     if (values) CK(v.alloc((size_t)n_val, "bpm_derive", "the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string(n_out) + " outputs"));
-    {
-        const double* H = s->hist;
-        const double* LL = s->llhist;
-        unsigned int ld = s->ld, k_out = n_out, k_R = R, k_ldp = ldp, k_ldo = ldo;
-        int d = (int)s->dim;
-        unsigned long long k_lo = lo, k_hi = hi, k_rec = n_rec;
-        const double* params = s->derive_params;
-        double* rec = b.p;
-        double* vals = v.p;
-        void* args[] = {(void*)&H, (void*)&LL, (void*)&ld, (void*)&d, (void*)&k_lo, (void*)&k_hi, (void*)&params, (void*)&k_out, (void*)&k_R, (void*)&k_ldp,
-                        (void*)&k_ldo, (void*)&rec, (void*)&k_rec, (void*)&vals};
-        HIPCK(hipModuleLaunchKernel(s->derive_fn, (unsigned)parts, 1, 1, DERIVE_THREADS, 1, 1, lds, s->stream, args, nullptr));
-    }
+    HIPCK(ModuleLaunch<bpm::DeriveRowsKernel>::on(s->stream, s->derived.fn, (unsigned)parts, DERIVE_THREADS, lds, s->hist, s->llhist, s->ld, (int)s->dim, lo, hi,
+                                                  s->derived.params.p, n_out, R, ldp, ldo, b.p, n_rec, v.p));
     const double* rec = b.p;
     if (parts > 1) {
         hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((n_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream, (const double*)b.p,

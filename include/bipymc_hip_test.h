@@ -39,6 +39,12 @@ int bpm_debug_fail_queue(bpm_handle_t h, int32_t refuse_quiesce);
  * the update kernels, then the update kernels: *name = the kernel's plain name (static storage), *n_args <= 8 explicit arguments, their byte offsets
  * and sizes as the host lays them out.  No GPU, no handle: a test holds them against the code object's metadata. */
 int bpm_debug_kernarg_layout(int32_t index, const char** name, int32_t* n_args, int64_t offsets[8], int64_t sizes[8]);
+/* the update kernel's run-time program around a likelihood given as HIP source (what bpm_set_device_likelihood builds for a sampler of `algo` with
+ * lpc lanes per chain, dpl doubles per lane, np difference pairs, `dim` coordinates and the steady-state flavour `hot`), compiled for `arch`
+ * (null / "": gfx950) with no device and no handle: 0, or an error with the reason (the compiler's log included) copied to `log` as
+ * bpm_check_device_likelihood does */
+int bpm_debug_check_user_fused(const char* hip_source, int32_t algo, int32_t lpc, int32_t dpl, int32_t np, int32_t dim, int32_t hot, const char* arch,
+                               char* log, int64_t log_cap);
 /* no-op packets on the handle's own AQL queue until its next packet takes position `pos` (0 ... 254) of an epoch of 256 packets;
  * *widx = the queue's write index afterwards (a test then puts a drain's packets at a chosen place of the ring) */
 int bpm_debug_queue_pad(bpm_handle_t h, int32_t pos, int64_t* widx);

@@ -268,3 +268,37 @@ def test_hip_source_likelihood_compiles_without_a_gpu():
     assert terms.check() and terms.source.startswith("#define BPM_LN_LIKE_TERMS 1")
     with pytest.raises(ValueError):
         HipLikelihood("", terms=9)
+
+
+_FUSED_PLAIN = ("__device__ double ln_like(const double* x, int d, const double* p) {\n"
+                "    double s = 0.0;\n"
+                "    for (int j = 0; j < d; ++j) { const double z = (x[j] - p[j]) * p[d + j]; s += z * z; }\n"
+                "    return -0.5 * s;\n}")
+_FUSED_TERMS = ("#define BPM_LN_LIKE_TERMS 1\n"
+                "__device__ void ln_like_terms(double xj, int j, int d, const double* p, double* acc) { const double z = (xj - p[j]) * p[d + j]; acc[0] += z * z; }\n"
+                "__device__ double ln_like_finish(const double* acc, int d, const double* p) { return -0.5 * acc[0]; }")
+
+
+def _check_user_fused(src, algo, lpc, dpl, np_, dim, hot):
+    import ctypes as C
+    from bipymc_amd import _lib
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load_test().bpm_debug_check_user_fused(src.encode(), algo, lpc, dpl, np_, dim, hot, b"gfx950", log, len(log))
+    return rc, log.value.decode("utf-8", "replace")
+
+
+@pytest.mark.parametrize("form", ["plain", "terms"])
+@pytest.mark.parametrize("algo,lpc,dpl,np_,dim,hot", [("dream", 64, 2, 3, 100, 1), ("dream", 4, 2, 3, 8, 1), ("demc", 1, 2, 1, 2, 2)])
+def test_update_kernel_compiles_around_a_hip_source_likelihood_without_a_gpu(built_test, form, algo, lpc, dpl, np_, dim, hot):
+    """bpm_debug_check_user_fused (include/bipymc_hip_test.h): the program bpm_set_device_likelihood builds around a likelihood -- kernels.h, the caller's
+    source, user_target.h, the instantiations -- compiles for gfx950 with no device in the machine, in the plain and in the per-coordinate form, for
+    the shapes of DREAM d = 100 and d = 8 and DE-MC d = 2."""
+    from bipymc_amd import _lib
+    rc, log = _check_user_fused(_FUSED_PLAIN if form == "plain" else _FUSED_TERMS, _lib.ALGO_DREAM if algo == "dream" else _lib.ALGO_DEMC, lpc, dpl, np_, dim, hot)
+    assert rc == 0 and log == "", log
+
+
+def test_update_kernel_around_a_broken_likelihood_reports_the_compilers_log(built_test):
+    rc, log = _check_user_fused("__device__ double ln_like(const double* x, int d, const double* p) { return x[0] }", 1, 64, 2, 3, 100, 1)
+    assert rc != 0
+    assert log.startswith("the update kernel does not compile around this likelihood") and "expected" in log, log

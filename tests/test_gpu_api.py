@@ -331,6 +331,62 @@ np.save(sys.argv[1], np.concatenate([o.reshape(-1) for o in out]))
         assert np.array_equal(res[0], r)
 
 
+def test_hip_source_likelihood_replaced_by_another(monkeypatch):
+    """bpm_set_device_likelihood on a sampler that already has one: the new likelihood -- its kernel, its parameter block and the update kernel compiled
+    around it -- takes the old one's place whole (the queue forgets the old kernels' names and finds the new ones), and an install that fails leaves the
+    installed one as it was.  Two engines built alike, one with the update kernel compiled around each likelihood, one with BPM_USER_FUSED=0 (the variable is
+    read at every install), go through A -> 6 generations -> B -> 6 generations (the rest of the burn-in and two steady ones: B's burn-in, steady and
+    general instantiations all run) -> a source that does not compile -> 2 generations: state, ln-likes, CR statistics and accept counts equal bit for bit."""
+    from bipymc_amd import _lib as L
+    from bipymc_amd.engine import HipEngine
+    N, d = 256, 8
+    src_a = """__device__ double ln_like(const double* x, int d, const double* p) {
+    double s = 0.0;
+    for (int j = 0; j < d; ++j) { const double z = (x[j] - p[j]) * p[d + j]; s += z * z; }
+    return -0.5 * s;
+}"""
+    src_b = src_a.replace("-0.5 * s", "-0.5 * (2.0 * s)")
+    assert src_b != src_a
+    par_a = np.concatenate([np.linspace(-1, 1, d), 1.0 / (1.0 + np.arange(d) % 3)])
+    par_b = np.concatenate([np.linspace(0.5, -0.5, d), 1.0 / (2.0 + np.arange(d) % 2)])
+    broken = "__device__ double ln_like(const double* x, int d, const double* p) { return x[0] }"
+    X0 = np.random.RandomState(5).normal(size=(N, d))
+
+    def run(fused):
+        if fused:
+            monkeypatch.delenv("BPM_USER_FUSED", raising=False)
+        else:
+            monkeypatch.setenv("BPM_USER_FUSED", "0")
+        e = HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=11, burnin_gen=10, n_cr_gen=2)
+        e.set_state(X0)
+        e.set_device_likelihood(src_a, par_a)
+        assert e.device_likelihood_info()[0] == fused, e.device_likelihood_info()[1]
+        e.begin_run()
+        d0 = e.launch_stats()["direct"]
+        e.step(6)
+        d1 = e.launch_stats()["direct"]
+        e.set_device_likelihood(src_b, par_b)
+        assert e.device_likelihood_info()[0] == fused, e.device_likelihood_info()[1]
+        e.step(6)
+        d2 = e.launch_stats()["direct"]
+        if fused and d1 > d0:
+            assert d2 > d1, (d0, d1, d2)      # the new kernels were found by their names after the old ones were forgotten
+        with pytest.raises(L.BpmError, match="does not compile"):
+            e.set_device_likelihood(broken, par_b)
+        assert e.device_likelihood_info()[0] == fused, e.device_likelihood_info()[1]
+        e.step(2)
+        st = e.stats()
+        return e, [e.get_state(), e.get_loglike(), np.asarray(st["p_cr"], dtype=float), np.array([st["local_n_accepted"], st["local_n_rejected"]])]
+
+    e1, r1 = run(True)
+    e2, r2 = run(False)
+    for a, b in zip(r1, r2):
+        assert np.array_equal(a, b)
+    assert np.all(np.isfinite(r1[1]))
+    e1.close()      # (raises if bpm_destroy reports an error)
+    e2.close()
+
+
 def test_bench_runs_without_torch_and_without_burn_in_for_the_kernel_trace():
     """tools/profile_bench.sh traces `python bench.py ... --no-torch --burnin-gens 0`: under rocprofv3 a process that loaded torch's HIP runtime, or has run the
     burn-in kernels, shows a mode of slow steady-state launches that un-profiled runs do not have (profiles/r05_rocprof_torch_artefact.txt).  The flags must
