@@ -13,4 +13,4 @@ from .device_likelihood import HipLikelihood  # noqa: F401
 from .covariance import PosteriorCovariance  # noqa: F401
 from .histograms import PosteriorHistograms  # noqa: F401
 from .traces import PosteriorTrace  # noqa: F401
-from .derived import HipFunction, PosteriorDerived  # noqa: F401
+from .derived import DerivedHistory, HipFunction, PosteriorDerived  # noqa: F401

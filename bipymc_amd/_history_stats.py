@@ -1,6 +1,7 @@
 """The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance,
 histograms, per-generation traces and summaries of user-written derived quantities (bipymc_amd/diagnostics.py, quantiles.py, covariance.py,
-histograms.py, traces.py, derived.py), each reduced where the history lives.
+histograms.py, traces.py, derived.py), each reduced where the history lives -- and derived_history, which makes the values of such a
+function a resident history of their own, with these same methods.
 
 The contract they share.  The window is the super-chain rows >= n_burn, param_est's selection (row g * n_chains + i = chain i at generation
 g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
@@ -74,3 +75,20 @@ class HistoryStatistics(object):
         from . import derived as _dv
         eng = self._stats_engine("param_est_fn")
         return _dv.compute(eng.derive, self._stats_allgather, fn, n_burn, self.n_chains, eng.history_rows(), values=values)
+
+    def derived_history(self, fn):
+        """A derived history is a history: `fn` (a derived.HipFunction) over every resident row, kept on the device as the history of a
+        second handle with dim = fn.n_out and this sampler's log-likelihoods -- so every method of this class answers about the derived
+        quantities: param_est_quantiles for the 5 / 50 / 95 % predictive band, convergence_diagnostics for R-hat and ESS of the quantity one
+        reports, param_est_hist, param_est_cov, param_est_trace and param_est_fn (a function of derived quantities).  A snapshot of the
+        history as it is now; costs rows x (n_out rounded up to even) x 8 bytes of device memory until closed.  Single rank only.
+        -> derived.DerivedHistory (a context manager: `with sampler.derived_history(fn) as dh: ...`)"""
+        from . import derived as _dv
+        who = "derived_history"
+        if not isinstance(fn, _dv.HipFunction):
+            raise TypeError("%s: fn must be a HipFunction (got %s)" % (who, type(fn).__name__))
+        n_ranks = int(getattr(getattr(self, "comm", None), "size", 1))
+        if n_ranks != 1:
+            raise NotImplementedError("%s: a derived history is built on a single rank only (this communicator has %d ranks)" % (who, n_ranks))
+        eng = self._stats_engine(who)
+        return _dv.DerivedHistory(eng.derive_history(fn), self.n_chains, self._stats_allgather)

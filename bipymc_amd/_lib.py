@@ -114,6 +114,7 @@ SIGNATURES = {
     "bpm_check_device_function": (C.c_int, [C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64]),
     "bpm_set_device_function": (C.c_int, [_H, C.c_char_p, C.c_int32, _dp, C.c_int32]),
     "bpm_derive": (C.c_int, [_H, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _P(C.c_int64), _dp, C.c_int64]),
+    "bpm_derive_history": (C.c_int, [_H, _H]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only

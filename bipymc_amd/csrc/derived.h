@@ -4,7 +4,7 @@
 // for the trajectory picture; ex_line_fit.py and ex_para_fit.py likewise).  Here the caller writes
 //     __device__ void derive(const double* x, int d, double ll, const double* p, double* out)
 // (x: one super-chain row, d coordinates, never the padding column; ll: that row's stored ln-like; p: the caller's parameter block; out[0 .. n_out):
-// zero on entry) and the library compiles ONE window-reduction kernel around it (hiprtc, as user_likelihood.h does for ln_like): per output the
+// zero on entry) and the library compiles a window-reduction kernel around it (hiprtc, as user_likelihood.h does for ln_like): per output the
 // count, shift and shifted sums of the finite values, the NaN count, min and max -- trace_acc.h's accumulator, merged in a fixed order without
 // atomics -- and, if asked, the values themselves.  bipymc_amd/derived.py merges the ranks and finishes mean and sd.
 //
@@ -22,6 +22,14 @@
 //                     record p * n_out + m (traces.h's structure of arrays, one bin, ld := n_out); the library's tr_fold_kernel folds the
 //                     parts in index order.  LDS is dynamic only: [rows R x ldp | ln-likes R | outputs R x ldo], and the merge tree's 256
 //                     accumulators over the same bytes afterwards.
+//   bpm_derive_fill   the DERIVED HISTORY (bpm_derive_history): the same grid over ALL local rows [0, hist_rows * n_local), the same steps 1 and 2
+//                     (derive_rows.h: bpm_derive_tile, the one staging routine of both kernels), and instead of step 3
+//                       3. store   the output tile leaves LDS straight into the history buffer D of a second, ordinary handle with dim = n_out:
+//                                  D[(t0 + r) * ldd + m] = m < n_out ? out[r][m] : 0 for m < ldd, ldd that handle's (even) row stride -- the
+//                                  padding column is written as 0, as bpm_set_history leaves it.  The tile's destination is contiguous:
+//                                  consecutive lanes store consecutive 16-byte pairs.
+//                     No accumulators, no merge tree.  Every statistic of the history (bpm_reduce_moments ... bpm_trace_chains, bpm_derive
+//                     itself) then serves the derived quantities through that handle, unchanged.
 #pragma once
 #include "user_likelihood.h"
 
@@ -37,6 +45,9 @@ constexpr int DERIVE_ACC_BYTES = 48;      // sizeof(TrAcc): the merge tree needs
 // rec, n_rec, values
 using DeriveRowsKernel = void(const double*, const double*, unsigned int, int, unsigned long long, unsigned long long, const double*, unsigned int, unsigned int,
                               unsigned int, unsigned int, double*, unsigned long long, double*);
+// bpm_derive_fill likewise: H, LL, ld, d, n_rows, params, n_out, R, ldp, ldo, D, ldd
+using DeriveFillKernel = void(const double*, const double*, unsigned int, int, unsigned long long, const double*, unsigned int, unsigned int, unsigned int,
+                              unsigned int, double*, unsigned int);
 
 // rows per tile R, the LDS strides (ldp == 0: rows are read where they lie) and the dynamic LDS of a launch, for rows of d coordinates and n_out outputs
 inline void derive_tile(uint32_t d, uint32_t n_out, uint32_t budget_bytes, uint32_t& R, uint32_t& ldp, uint32_t& ldo, uint32_t& lds_bytes) {

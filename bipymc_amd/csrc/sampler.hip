@@ -569,6 +569,7 @@ struct UserLikelihood {
 struct DerivedFunction {
     Module mod;
     hipFunction_t fn = nullptr;              // bpm_derive_rows of THIS module: launched by handle, never looked up by name
+    hipFunction_t fill = nullptr;            // bpm_derive_fill of the same module (bpm_derive_history)
     std::string src;                         // the source bytes and n_out the module was built from: the same again only re-upload the parameters
     int32_t n_out = 0;
     DevParams params;
@@ -3918,6 +3919,8 @@ extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, i
         HIPCK(next.mod.load(code));
         next.fn = next.mod.function("bpm_derive_rows");
         if (!next.fn) return fail("bpm_set_device_function: the compiled module has no bpm_derive_rows kernel");
+        next.fill = next.mod.function("bpm_derive_fill");
+        if (!next.fill) return fail("bpm_set_device_function: the compiled module has no bpm_derive_fill kernel");
         next.src = hip_source;
         next.n_out = n_out;
     }
@@ -3926,6 +3929,15 @@ extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, i
     if (rebuild) s->derived = std::move(next);
     else s->derived.params = std::move(next.params);
     return 0;
+}
+
+// tile and grid of a launch of the installed function's kernels over `rows` rows of s: rows per tile R, the LDS strides, the dynamic LDS, the workgroups
+static int derive_launch_shape(const bpm_sampler* s, uint64_t rows, const char* who, uint32_t& R, uint32_t& ldp, uint32_t& ldo, uint32_t& lds, uint64_t* parts) {
+    // BPM_DERIVE_LDS_KB (16 ... 60; read at every call: tools/derived_time.py switches it): the LDS budget of a workgroup's tiles (A/B)
+    uint32_t budget = (uint32_t)DERIVE_LDS_BYTES;
+    if (const char* kb = getenv("BPM_DERIVE_LDS_KB")) budget = (uint32_t)std::min(std::max(atoi(kb), 16), DERIVE_LDS_BYTES / 1024) * 1024u;
+    derive_tile(s->dim, (uint32_t)s->derived.n_out, budget, R, ldp, ldo, lds);
+    return rows_grid(rows, 1, R, who, parts);
 }
 
 // Over this rank's super-chain rows >= n_burn (bpm_reduce_moments' selection: a partial first generation by chain index), per output m of
@@ -3961,12 +3973,8 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
     }
     CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
     uint32_t R = 0, ldp = 0, ldo = 0, lds = 0;
-    // BPM_DERIVE_LDS_KB (16 ... 60; read at every call: tools/derived_time.py switches it): the LDS budget of a workgroup's tiles (A/B)
-    uint32_t budget = (uint32_t)DERIVE_LDS_BYTES;
-    if (const char* kb = getenv("BPM_DERIVE_LDS_KB")) budget = (uint32_t)std::min(std::max(atoi(kb), 16), DERIVE_LDS_BYTES / 1024) * 1024u;
-    derive_tile(s->dim, n_out, budget, R, ldp, ldo, lds);
     uint64_t parts = 1;
-    CK(rows_grid(rows, 1, R, "bpm_derive", &parts));
+    CK(derive_launch_shape(s, rows, "bpm_derive", R, ldp, ldo, lds, &parts));
     // [part records | folded records]; with one part the part records are the folded ones
     const uint64_t n_rec = parts * n_out;
     const size_t o_fold = (size_t)TR_F_BINS * n_rec;
@@ -3991,6 +3999,70 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
         for (int f = 0; f < 2; ++f) std::memcpy(&counts[(size_t)f * n_out + m], &h[(size_t)count_f[f] * n_out + m], 8);
         for (int f = 0; f < 5; ++f) sums[(size_t)f * n_out + m] = h[(size_t)sum_f[f] * n_out + m];
     }
+    return 0;
+}
+
+// A DERIVED HISTORY IS A HISTORY: the installed function of `src` over every resident row of src, written into the history buffer of `dst`, a
+// second, ordinary handle with dim = n_out -- whose bpm_reduce_moments ... bpm_trace_chains (and bpm_derive) then serve the derived quantities
+// with their own scratch, sized by their own ld, and their own state for bpm_reduce_moments' shift.  dst comes out as bpm_set_history leaves a
+// handle: rows in chain order, the state = the last row, the ln-likes = src's.  Every check runs before any launch; nothing src's sampler reads
+// is written (its history is put into chain order, as bpm_get_history does).
+extern "C" int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst) {
+    const char* who = "bpm_derive_history";
+    if (!src || !dst) return fail(std::string(who) + ": null handle");
+    if (src == dst) return fail(std::string(who) + ": the destination is the source itself (create a second handle with dim = n_out)");
+    CK(check_handle(src));
+    CK(check_handle(dst));
+    if (src->cfg.device != dst->cfg.device)
+        return fail(std::string(who) + ": source and destination are on different devices (" + std::to_string(src->cfg.device) + " and " +
+                    std::to_string(dst->cfg.device) + ")");
+    CK(set_device(src));
+    if (!src->derived.fill) return fail(std::string(who) + ": no device function installed on the source (bpm_set_device_function)");
+    CK(require_resident_history(src, who));
+    if (src->world != 1 || dst->world != 1)
+        return fail(std::string(who) + ": single rank only (world_size " + std::to_string(src->world) + " and " + std::to_string(dst->world) + ")");
+    const uint32_t n_out = (uint32_t)src->derived.n_out;
+    if (!dst->cfg.keep_history) return fail(std::string(who) + ": the destination needs keep_history=True");
+    if (dst->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(std::string(who) + ": the destination must have the host-callback target");
+    if (dst->dim != n_out)
+        return fail(std::string(who) + ": the destination has dim " + std::to_string(dst->dim) + "; the installed function has n_out " + std::to_string(n_out));
+    if (dst->N != src->N)
+        return fail(std::string(who) + ": the destination has n_chains " + std::to_string(dst->N) + "; the source has " + std::to_string(src->N));
+    if (dst->proposed) return fail(std::string(who) + ": the destination has proposals that are not committed");
+    const int64_t rows = src->hist_rows;
+    const uint64_t n = (uint64_t)rows * src->n_local;      // local rows of both
+    uint32_t R = 0, ldp = 0, ldo = 0, lds = 0;
+    uint64_t parts = 1;
+    CK(derive_launch_shape(src, n, who, R, ldp, ldo, lds, &parts));
+    if (rows > dst->hist_cap) {      // what ensure_history is about to allocate
+        const uint64_t cap = (uint64_t)std::max<int64_t>(rows, dst->hist_cap + dst->hist_cap / 2);
+        const uint64_t need = cap * dst->n_local * ((uint64_t)dst->ld + 1u) * sizeof(double);
+        size_t mem_free = 0, mem_total = 0;
+        HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+        if (need > mem_free)
+            return fail(std::string(who) + ": the derived history of " + std::to_string((long long)cap) + " generations x " + std::to_string(dst->n_local) +
+                        " chains x (" + std::to_string(dst->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(need >> 20)) +
+                        " MiB of device memory; " + std::to_string(mem_free >> 20) + " MiB are free");
+    }
+    CK(normalize_history(src, 0, src->hist_rows));
+    CK(ensure_history(dst, rows));
+    HIPCK(ModuleLaunch<bpm::DeriveFillKernel>::on(src->stream, src->derived.fill, (unsigned)parts, DERIVE_THREADS, lds, src->hist, src->llhist, src->ld,
+                                                  (int)src->dim, (unsigned long long)n, src->derived.params.p, n_out, R, ldp, ldo, dst->hist, dst->ld));
+    const size_t row_d = (size_t)dst->n_local * dst->ld;
+    const double* ll_last = src->llhist + (size_t)(rows - 1) * src->n_local;
+    HIPCK(hipMemcpyAsync(dst->llhist, src->llhist, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    // the state and the ln-like cache bpm_set_history + bpm_set_loglike leave behind: the last row (bpm_reduce_moments' shift: a value of the data)
+    HIPCK(hipMemcpyAsync(dst->G, dst->hist + (size_t)(rows - 1) * row_d, row_d * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    HIPCK(hipMemcpyAsync(dst->ll, ll_last, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    for (int64_t r = 0; r < rows && r < (int64_t)dst->hist_tag.size(); ++r) dst->hist_tag[(size_t)r] = -1;
+    dst->hist_rows = rows;
+    dst->rows_logical = rows;
+    dst->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
+    dst->ll_stale = false;
+    dst->state_set = true;
+    dst->phase = 0;
+    dst->hist_epoch += 1;
+    HIPCK(hipStreamSynchronize(src->stream));
     return 0;
 }
 

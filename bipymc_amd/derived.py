@@ -21,6 +21,14 @@ The library compiles one window-reduction kernel around the function (bpm_set_de
 module validates, merges the ranks in rank order with the trace summaries' own merge (traces.merge_moments / finish: moments over the finite
 values, NumPy's answer for a mean where some value is not finite, min / max over what is not NaN) and puts the values into super-chain order.
 Every rank runs the same arithmetic on the same gathered parts: every rank returns the same bits.
+
+A derived history is a history: `sampler.derived_history(fn)` writes fn of every resident row into the history of a second, ordinary handle
+with dim = n_out (bpm_derive_history; the fill kernel of bipymc_amd/csrc/derive_rows.h) and returns a DerivedHistory, which carries every
+statistic of _history_stats.HistoryStatistics over the derived quantities:
+
+    with sampler.derived_history(fn) as dh:
+        lo, med, hi = dh.param_est_quantiles(n_burn, q=(0.05, 0.5, 0.95))     # (3, n_out): the predictive band
+        dh.convergence_diagnostics(n_burn)                                     # R-hat / ESS of every output
 """
 from __future__ import division
 
@@ -29,7 +37,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._history_stats import check_n_burn, empty_window
+from ._history_stats import HistoryStatistics, check_n_burn, empty_window
 from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
 from .traces import finish, merge_moments
 
@@ -130,3 +138,39 @@ def compute(derive, allgather, fn, n_burn, n_chains, history_rows, values=False)
             rows = rank_rows(r, len(parts), n_chains, history_rows, int(p[2]), int(p[3]))
             vals[rows - n_burn] = np.asarray(p[4], dtype=np.float64).reshape(len(rows), m)
     return PosteriorDerived(mean, sd, mn, mx, n_nan, n, vals)
+
+
+class DerivedHistory(HistoryStatistics):
+    """The values of a HipFunction over a sampler's history as a resident history of their own (HistoryStatistics.derived_history): with
+    V = sampler.param_est_fn(fn, 0, values=True).values reshaped to (generations, n_chains, n_out), every method returns what it would return
+    on a sampler whose history is V and whose log-likelihood history is the parent's.  A snapshot: it keeps describing the parent's history as
+    it was when it was built.  Holds rows x (n_out rounded up to even) x 8 bytes of device memory until close(); a context manager."""
+
+    def __init__(self, engine, n_chains, allgather):
+        self._engine = engine
+        self._stats_allgather = allgather
+        self.n_chains = int(n_chains)
+        self.n_out = self.dim = int(engine.dim)
+        self.history_rows = int(engine.history_rows())
+
+    def _stats_engine(self, who):
+        if self._engine is None:
+            raise RuntimeError("%s: this derived history is closed" % who)
+        return self._engine
+
+    def param_est(self, n_burn):
+        """-> (mean, std, values): values = the derived quantities of the parent's super-chain rows >= n_burn, (rows, n_out)"""
+        w = self._stats_engine("param_est").get_history().reshape(-1, self.n_out)[n_burn:, :]
+        return np.mean(w, axis=0), np.std(w, axis=0), w
+
+    def close(self):
+        eng, self._engine = self._engine, None
+        if eng is not None:
+            eng.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -82,7 +82,7 @@ class HipEngine(object):
         self._h = C.c_void_p()
         self.lib = lib if lib is not None else L.load()
         self.n_chains, self.dim = int(n_chains), int(dim)
-        self.rank, self.world_size = int(rank), int(world_size)
+        self.rank, self.world_size, self.device = int(rank), int(world_size), int(device)
         if self.n_chains % self.world_size != 0:
             raise ValueError("n_chains must be divisible by the communicator size")
         self.n_local = self.n_chains // self.world_size
@@ -557,6 +557,22 @@ class HipEngine(object):
         """derived.compute's per-rank call: installs `fn` (a derived.HipFunction) and reduces (set_device_function + derive_rows)"""
         self.set_device_function(fn.source, fn.n_out, fn.params)
         return self.derive_rows(n_burn, values)
+
+    def derive_history(self, fn):
+        """-> HipEngine: a second, ordinary engine with dim = fn.n_out on the same library and device whose resident history is `fn` (a
+        derived.HipFunction) of every row of this one's, with this one's log-likelihood history (bpm_derive_history) -- every statistic above
+        then answers about the derived quantities through it.  A snapshot; the caller closes it.  Single rank only."""
+        if self.world_size != 1:
+            raise NotImplementedError("derive_history: a derived history is built on a single rank only (world_size = %d)" % self.world_size)
+        self.set_device_function(fn.source, fn.n_out, fn.params)
+        dst = HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=fn.n_out, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,
+                        device=self.device, burnin_gen=0, outlier_every=0, keep_history=True, lib=self.lib)
+        try:
+            self._ck(self.lib.bpm_derive_history(self._h, dst._h))
+        except BaseException:
+            dst.close()
+            raise
+        return dst
 
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None

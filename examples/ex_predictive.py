@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The posterior of a function of the parameters without moving the history: a derived quantity and a posterior-predictive band from
-`param_est_fn` (bipymc_amd.HipFunction).
+`param_est_fn` (bipymc_amd.HipFunction), then -- `derived_history` -- the 5 / 50 / 95 % quantile band of the same curve and the split
+R-hat / effective sample size of the ratio itself.
 
 The reference's fitting scripts end by copying the samples to the host and running a function over them (examples/ex_exp_fit.py:176-202: a
 ratio of two parameters with its mean and standard deviation, the fitted model at every sample for the band).  Here the function is a few
@@ -56,6 +57,15 @@ def main():
     # the values themselves, if a picture needs them: one row per sample, in param_est's order
     tail = sampler.param_est_fn(fn, n_burn=N * 1499, values=True)
     print("values of the last %d samples: %r" % (tail.n, tail.values.shape))
+    # A derived history is a history: the values stay on the GPU as the history of a second handle, and every statistic of the sampler
+    # answers about them -- the band a skewed output needs is a quantile band, and convergence is checked on the quantity one reports.
+    with sampler.derived_history(fn) as dh:
+        q05, q50, q95 = dh.param_est_quantiles(N * 700, q=(0.05, 0.5, 0.95))
+        cd = dh.convergence_diagnostics(N * 700)
+        print("x-intercept: median %.3f, 5-95 %% band [%.3f, %.3f]; split R-hat %.4f, ESS %.0f of %d draws"
+              % (q50[0], q05[0], q95[0], cd.r_hat[0], cd.ess[0], cd.n_half_chains * cd.n_draws))
+        for k in (0, 21, 42, 63):
+            print("  y(%5.2f): median %7.3f   5-95 %% band [%7.3f, %7.3f]   R-hat %.4f" % (grid[k], q50[2 + k], q05[2 + k], q95[2 + k], cd.r_hat[2 + k]))
     return pd
 
 

@@ -392,6 +392,20 @@ int bpm_check_device_function(const char* hip_source, int32_t n_out, const char*
 int bpm_set_device_function(bpm_handle_t h, const char* hip_source, int32_t n_out, const double* params, int32_t n_params);
 int bpm_derive(bpm_handle_t h, int64_t n_burn, int64_t* counts, double* sums, int64_t* n_rows, int64_t* n_first, double* values,
                int64_t values_cap);
+/* A DERIVED HISTORY IS A HISTORY: the installed function of `src` (bpm_set_device_function) over EVERY resident row of src, written into the
+ * history of `dst` -- a second, ordinary handle made by bpm_create with the host-callback target, keep_history = 1, dim = n_out and src's
+ * n_chains -- so that every statistic above (bpm_reduce_moments, bpm_diag_*, bpm_quantile_*, bpm_reduce_cov, bpm_hist_*, bpm_trace_*, bpm_derive
+ * itself) answers about the derived quantities through dst, unchanged: the quantile band of a predicted curve, R-hat and ESS of the ratio
+ * c_0 / c_inf one reports (what the reference computes on the host from param_est(n_burn)[2], examples/ex_exp_fit.py:176-202, and np.quantile
+ * would add).  dst's row g, chain i, column m = output m of derive on src's row g, chain i (the padding column of an odd n_out is 0); dst's
+ * ln-like history is src's; dst's state is its last row and its ln-like cache src's last ln-like row, what bpm_set_history and bpm_set_loglike
+ * leave behind.  A snapshot: dst keeps describing src's history as it was at the call.  Nothing src's sampler reads is written (a history kept
+ * in position order is put into chain order first, as bpm_get_history does): a run that continues is bit-identical to one that never made
+ * the call.  Costs hist_rows x n_local x ((n_out rounded up to even) + 1) x 8 bytes of device memory on dst.  Every check runs before any
+ * launch.  Errors: a null handle, dst == src, different devices, no function installed, no resident history on src (keep_history = 0), a dst
+ * without keep_history, with another target, dim != n_out or another n_chains, world_size != 1 on either (single rank only), a derived history
+ * larger than the free device memory (the message names the requirement). */
+int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */

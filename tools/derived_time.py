@@ -7,6 +7,12 @@ warm, for n_out = 1 (a ratio of two parameters) and n_out = 64 (a line on 64 abs
   (b) bpm_reduce_moments over the same window in the same run: the project's plain single-read pass,
 with the bytes the pass reads (rows x ld x 8) and the share of 8 TB/s they imply, the one-off compilation time, and whether device and
 NumPy agree.
+Then the derived history (sampler.derived_history: bpm_derive_history, the fill kernel bpm_derive_fill) for the same two functions over the
+whole resident history: the build host-to-host, the bytes it reads and writes (rows x ld x 8 + rows x ldd x 8) and the share of 8 TB/s they
+imply, dh.param_est_quantiles at 5 / 50 / 95 %, next to bpm_derive over the same rows in the same run and -- unless --device-only -- the
+route of the parent commit, param_est_fn(values=True) + np.quantile.  The fill kernel's own time comes from a run of
+`rocprofv3 --kernel-trace --stats -- python tools/derived_time.py --device-only` (kernel bpm_derive_fill); the record goes to
+profiles/derived_history_cfg2.txt.
 usage: derived_time.py [G] [--out FILE] [--device-only]   (--device-only: no host copy / NumPy)"""
 import argparse
 import os
@@ -29,6 +35,46 @@ LINE = HipFunction("""
 __device__ void derive(const double* x, int d, double ll, const double* p, double* out) {
     for (int k = 0; k < 64; ++k) out[k] = x[0] + x[1] * p[k];
 }""", n_out=64, params=np.linspace(0.0, 1.0, 64), python_fn=lambda X, ll, p: X[:, :1] + X[:, 1:2] * p[None, :])
+
+
+def derived_history_section(e, say, device_only):
+    from bipymc_amd._history_stats import HistoryStatistics
+
+    class Over(HistoryStatistics):
+        n_chains = e.N
+        _stats_allgather = staticmethod(DV.single_process_allgather)
+
+        def _stats_engine(self, who):
+            return e
+
+    s, q = Over(), (0.05, 0.5, 0.95)
+    rows = e.rows * e.N
+    say("# derived histories: every resident row (%d), not the window" % rows)
+    for name, fn in (("ratio x[2] / x[1], n_out = 1", RATIO), ("line on 64 abscissae, n_out = 64", LINE)):
+        ldd = fn.n_out + (fn.n_out & 1)
+        s.derived_history(fn).close()                  # compiles if need be; first launch
+
+        def build():
+            s.derived_history(fn).close()
+
+        t_build, _ = median_time(build)
+        t_der, _ = median_time(lambda: DV.compute(e.derive, DV.single_process_allgather, fn, 0, e.N, e.rows))
+        moved = rows * (e.ld + 1) * 8 + rows * (ldd + 1) * 8
+        with s.derived_history(fn) as dh:
+            dh.param_est_quantiles(e.n_burn, q=q)
+            t_q, got = median_time(lambda: dh.param_est_quantiles(e.n_burn, q=q))
+        say("%s: derived_history build (create + fill + close) host-to-host %.3f ms; it reads %.2f GB and writes %.3f GB (ln-likes included): "
+            "%.2f TB/s = %.3f of 8 TB/s; bpm_derive over the same rows in this run %.3f ms (%.2f x); dh.param_est_quantiles(5 / 50 / 95 %%) %.3f ms"
+            % (name, t_build * 1e3, rows * (e.ld + 1) * 8 / 1e9, rows * (ldd + 1) * 8 / 1e9, moved / t_build / 1e12, moved / t_build / PEAK_BW,
+               t_der * 1e3, t_build / t_der, t_q * 1e3))
+        if not device_only:
+            t0 = time.perf_counter()
+            V = s.param_est_fn(fn, e.n_burn, values=True).values
+            want = np.quantile(V, q, axis=0)
+            t_np = time.perf_counter() - t0
+            say("    the parent commit's route, param_est_fn(values=True) + np.quantile: %.2f s = %.0f x build + quantiles; equal to the device: %s"
+                % (t_np, t_np / (t_build + t_q), bool(np.array_equal(got, want, equal_nan=True))))
+            del V
 
 
 def main():
@@ -83,6 +129,7 @@ def main():
                 % (bool(np.array_equal(pd.min, mn) and np.array_equal(pd.max, mx)), float(np.max(np.abs(pd.mean - mean) / sd)),
                    float(np.max(np.abs(pd.sd / sd - 1.0)))))
             del V
+    derived_history_section(e, say, a.device_only)
     e.close()
     report.write(a.out)
 
