@@ -1,7 +1,7 @@
 """The statistics of a sampler's resident history, once for every sampler class: convergence diagnostics, quantiles, covariance,
 histograms, per-generation traces and summaries of user-written derived quantities (bipymc_amd/diagnostics.py, quantiles.py, covariance.py,
-histograms.py, traces.py, derived.py), each reduced where the history lives -- and derived_history, which makes the values of such a
-function a resident history of their own, with these same methods.
+histograms.py, traces.py, derived.py), each reduced where the history lives -- and derived_history and rank_history, which make the values
+of such a function, or the pooled ranks of the window (rank_diagnostics.py), a resident history of their own, with these same methods.
 
 The contract they share.  The window is the super-chain rows >= n_burn, param_est's selection (row g * n_chains + i = chain i at generation
 g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
@@ -33,6 +33,37 @@ class HistoryStatistics(object):
         eng = self._stats_engine("convergence_diagnostics")
         g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
         return _diag.compute(eng.diag_split_moments, eng.diag_autocov, self._stats_allgather, g0, g1, max_lag=max_lag)
+
+    def convergence_diagnostics_rank(self, n_burn=0, max_lag=None, prob=(0.05, 0.95)):
+        """The rank-normalized split-R-hat, bulk-ESS and tail-ESS of Vehtari et al. (2021), as Stan and ArviZ report them, over
+        convergence_diagnostics' window: r_hat = max(bulk, tail) sees chains that differ in scale as well as in location and is defined for
+        heavy tails; ess_tail = min over the indicators x <= np.quantile(prob) says how well those quantiles are estimated.  Pooled ranks,
+        normal scores and indicators are written into one scratch handle (four fills, each read by the classic pipeline), which costs the
+        window's rows x (dim rounded up to even + 1) x 8 bytes plus the sort's scratch while the call runs.  Single rank only.
+        -> rank_diagnostics.RankDiagnostics"""
+        from . import diagnostics as _diag
+        from . import rank_diagnostics as _rk
+        who = "convergence_diagnostics_rank"
+        _rk.check_single_rank(who, getattr(getattr(self, "comm", None), "size", 1))
+        _rk.check_prob(who, prob)
+        eng = self._stats_engine(who)
+        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
+        return _rk.compute(eng, self._stats_allgather, g0, g1, max_lag=max_lag, prob=prob, who=who)
+
+    def rank_history(self, n_burn=0, scale="z", folded=False):
+        """A ranked history is a history: the split rows of convergence_diagnostics' window (2n generations: the first and the last n of
+        the window) with every value replaced by the normal score of its pooled rank within its coordinate (scale="z"), or by that average
+        rank itself (scale="rank": what a rank plot bins); folded=True ranks |x - median| instead.  Kept on the device as the history of a
+        second handle, so every method of this class reads it.  A snapshot; single rank only.
+        -> derived.DerivedHistory (a context manager)"""
+        from . import derived as _dv
+        from . import diagnostics as _diag
+        from . import rank_diagnostics as _rk
+        who = "rank_history"
+        _rk.check_single_rank(who, getattr(getattr(self, "comm", None), "size", 1))
+        eng = self._stats_engine(who)
+        g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
+        return _dv.DerivedHistory(_rk.ranked_engine(eng, g0, g1, scale=scale, folded=folded, who=who), self.n_chains, self._stats_allgather)
 
     def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
         """np.quantile(param_est(n_burn)[2], q, axis=0), exactly (an MSD radix select).  -> (len(q), dim), or (dim,) for a scalar q"""

@@ -115,6 +115,7 @@ SIGNATURES = {
     "bpm_set_device_function": (C.c_int, [_H, C.c_char_p, C.c_int32, _dp, C.c_int32]),
     "bpm_derive": (C.c_int, [_H, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _P(C.c_int64), _dp, C.c_int64]),
     "bpm_derive_history": (C.c_int, [_H, _H]),
+    "bpm_rank_history": (C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _P(C.c_int64), _dp]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only
@@ -157,7 +158,7 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/user_likelihood.h", "csrc/derived.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/user_likelihood.h", "csrc/derived.h",
             "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_target.h", "csrc/derive_rows.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 

@@ -39,6 +39,14 @@
 #include "covariance.h"
 #include "histograms.h"
 #include "traces.h"
+#include "ranks.h"
+// bpm_rank_history's sort: rocPRIM's segmented radix sort (header-only).  Its kernels go into this variant's own inline namespace, like the
+// library's own (philox.h: BPM_VARIANT_NS) -- two variants in one process must not share a kernel symbol.  (After <cstring>, which one of
+// its headers needs.)
+#define ROCPRIM_INLINE_NAMESPACE BPM_VARIANT_NS
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
 #endif
@@ -4054,6 +4062,178 @@ extern "C" int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst) {
     // the state and the ln-like cache bpm_set_history + bpm_set_loglike leave behind: the last row (bpm_reduce_moments' shift: a value of the data)
     HIPCK(hipMemcpyAsync(dst->G, dst->hist + (size_t)(rows - 1) * row_d, row_d * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     HIPCK(hipMemcpyAsync(dst->ll, ll_last, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    for (int64_t r = 0; r < rows && r < (int64_t)dst->hist_tag.size(); ++r) dst->hist_tag[(size_t)r] = -1;
+    dst->hist_rows = rows;
+    dst->rows_logical = rows;
+    dst->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
+    dst->ll_stale = false;
+    dst->state_set = true;
+    dst->phase = 0;
+    dst->hist_epoch += 1;
+    HIPCK(hipStreamSynchronize(src->stream));
+    return 0;
+}
+
+// ---- pooled ranks of the history (ranks.h; bipymc_amd/rank_diagnostics.py drives the fills) ---------------------------------------------
+// segment kk of the sort = column kk of the batch: keys [kk * S, (kk + 1) * S)
+struct RankSegment {
+    uint32_t S;
+    __host__ __device__ uint32_t operator()(uint32_t kk) const { return kk * S; }
+};
+
+// the segmented radix sort of bc columns of S keys each (tmp == nullptr: only its temporaries' size into *tmp_bytes); on the HIP stream
+static hipError_t rank_sort(void* tmp, size_t* tmp_bytes, unsigned long long* in, unsigned long long* out, uint32_t bc, uint32_t S, hipStream_t st) {
+    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), RankSegment{S});
+    return rocprim::segmented_radix_sort_keys(tmp, *tmp_bytes, in, out, bc * S, bc, seg, seg + 1, 0u, 64u, st);
+}
+
+// A RANKED HISTORY IS A HISTORY: a transform of the split rows of src's history rows [g_lo, g_hi) -- n = (g_hi - g_lo) / 2 rows from g_lo,
+// then n rows up to g_hi -- written into the history of `dst`, a second, ordinary handle as bpm_derive_history takes one, with src's dim.
+// kind RK_RANK: the average rank of a value among the S = 2 n n_local values of its coordinate; RK_Z: its normal score; RK_RANK_FOLDED,
+// RK_Z_FOLDED: the same of |x - arg[k]|; RK_INDICATOR: x <= arg[k].  order_stats[j * dim + k] (sorted kinds): the pos[j]-th smallest value.  dst
+// comes out as bpm_set_history leaves a handle and may be filled again.  Every check and every allocation of scratch comes before any
+// launch; nothing src's sampler reads is written.
+extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
+                                const int64_t* pos, double* order_stats) {
+    const std::string who = "bpm_rank_history";
+    if (!src || !dst) return fail(who + ": null handle");
+    if (src == dst) return fail(who + ": the destination is the source itself (create a second handle with the same dim)");
+    CK(check_handle(src));
+    CK(check_handle(dst));
+    if (src->cfg.device != dst->cfg.device)
+        return fail(who + ": source and destination are on different devices (" + std::to_string(src->cfg.device) + " and " +
+                    std::to_string(dst->cfg.device) + ")");
+    CK(set_device(src));
+    if (kind < RK_RANK || kind > RK_RANK_FOLDED) return fail(who + ": kind must be 0 (rank), 1 (z), 2 (folded z), 3 (indicator) or 4 (folded rank); got " + std::to_string(kind));
+    const bool sorted = kind != RK_INDICATOR;
+    if ((rk_folded(kind) || kind == RK_INDICATOR) && !arg) return fail(who + ": kind " + std::to_string(kind) + " needs arg (one value per coordinate)");
+    if (n_pos < 0 || (n_pos > 0 && (!pos || !order_stats))) return fail(who + ": bad order-statistics arguments");
+    if (!sorted && n_pos != 0) return fail(who + ": the indicator sorts nothing and has no order statistics (n_pos must be 0)");
+    CK(require_resident_history(src, who.c_str()));
+    if (src->world != 1 || dst->world != 1)
+        return fail(who + ": single rank only (world_size " + std::to_string(src->world) + " and " + std::to_string(dst->world) + ")");
+    if (g_lo < 0 || g_hi < g_lo || g_hi > src->hist_rows) return fail(who + ": generation range out of bounds");
+    const int64_t n = (g_hi - g_lo) / 2;
+    if (n < 4)
+        return fail(who + ": a window of " + std::to_string((long long)(g_hi - g_lo)) + " history rows gives half-chains of " + std::to_string((long long)n) +
+                    " draws; at least 4 are needed");
+    if (!dst->cfg.keep_history) return fail(who + ": the destination needs keep_history=True");
+    if (dst->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(who + ": the destination must have the host-callback target");
+    if (dst->dim != src->dim) return fail(who + ": the destination has dim " + std::to_string(dst->dim) + "; the source has " + std::to_string(src->dim));
+    if (dst->N != src->N) return fail(who + ": the destination has n_chains " + std::to_string(dst->N) + "; the source has " + std::to_string(src->N));
+    if (dst->proposed) return fail(who + ": the destination has proposals that are not committed");
+    const uint64_t S64 = 2ull * (uint64_t)n * src->n_local;
+    if (S64 >= (1ull << 31))
+        return fail(who + ": the window holds " + std::to_string((unsigned long long)S64) + " values per coordinate; fewer than 2^31 can be ranked");
+    const uint32_t S = (uint32_t)S64, dim = src->dim, ld = src->ld;
+    for (int32_t j = 0; j < n_pos; ++j)
+        if (pos[j] < 0 || (uint64_t)pos[j] >= S64)
+            return fail(who + ": order statistic " + std::to_string((long long)pos[j]) + " is outside [0, " + std::to_string((unsigned long long)S64) + ")");
+    size_t mem_free = 0, mem_total = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    const int64_t rows = 2 * n;
+    if (rows > dst->hist_cap) {      // what ensure_history is about to allocate
+        const uint64_t cap = (uint64_t)std::max<int64_t>(rows, dst->hist_cap + dst->hist_cap / 2);
+        const uint64_t need = cap * dst->n_local * ((uint64_t)dst->ld + 1u) * sizeof(double);
+        if (need > mem_free)
+            return fail(who + ": the ranked history of " + std::to_string((long long)cap) + " generations x " + std::to_string(dst->n_local) + " chains x (" +
+                        std::to_string(dst->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(need >> 20)) + " MiB of device memory; " +
+                        std::to_string(mem_free >> 20) + " MiB are free");
+        mem_free -= (size_t)need;
+    }
+    // the batch: as many columns as the scratch budget holds (keys in | keys out | the sort's temporaries), batch * S < 2^31.
+    // The sort gives a column of this length to ONE workgroup, so the columns of a batch are its whole parallelism: at cfg2's shape with 1000
+    // generations a z fill takes 24.7 / 6.8 / 2.1 / 1.0 s with batches of 1 / 4 / 16 / 64 columns (profiles/rank_diagnostics_cfg2.txt).  Hence
+    // the default budget: a quarter of the free memory.  BPM_RANK_SCRATCH_MB: the budget; BPM_RANK_BATCH_COLS: the batch itself (tests, A/B;
+    // both read at every call)
+    uint32_t bc = 0;
+    size_t tmp_bytes = 0;
+    DevTemp<unsigned long long> keys;
+    DevTemp<unsigned char> tmp;
+    DevTemp<double> d_arg, d_os;
+    DevTemp<unsigned long long> d_pos;
+    if (sorted) {
+        uint64_t budget = mem_free / 4;
+        if (const char* mb = getenv("BPM_RANK_SCRATCH_MB")) budget = (uint64_t)std::max(atoll(mb), 0ll) << 20;
+        const uint32_t bc_max = std::min<uint32_t>(dim, (uint32_t)(((1ull << 31) - 1) / S));
+        auto need_of = [&](uint32_t b, uint64_t* need) -> int {
+            size_t t = 0;
+            HIPCK(rank_sort(nullptr, &t, nullptr, nullptr, b, S, src->stream));
+            tmp_bytes = t;
+            *need = 2ull * b * S * sizeof(unsigned long long) + t;
+            return 0;
+        };
+        uint64_t need = 0;
+        const char* forced = getenv("BPM_RANK_BATCH_COLS");
+        if (forced && atoi(forced) > 0) {
+            bc = std::min<uint32_t>((uint32_t)atoi(forced), bc_max);
+            CK(need_of(bc, &need));
+        } else {
+            bc = (uint32_t)std::min<uint64_t>(bc_max, std::max<uint64_t>(1, budget / (16ull * S)));
+            CK(need_of(bc, &need));
+            while (bc > 1 && need > budget) {
+                bc = std::max<uint32_t>(1, std::min<uint32_t>(bc - 1, (uint32_t)((uint64_t)bc * budget / need)));
+                CK(need_of(bc, &need));
+            }
+            if (need > budget)
+                return fail(who + ": sorting one column of " + std::to_string(S) + " keys needs " + std::to_string((unsigned long long)need) +
+                            " bytes of scratch (keys in, keys out and the sort's temporaries); the budget is " + std::to_string((unsigned long long)budget) +
+                            " bytes (BPM_RANK_SCRATCH_MB; by default a quarter of the free device memory: " + std::to_string(mem_free >> 20) +
+                            " MiB are free)");
+        }
+        const std::string what = "the scratch of " + std::to_string(bc) + " columns of " + std::to_string(S) + " keys";
+        CK(keys.alloc(2 * (size_t)bc * S, who.c_str(), what + " (keys in, keys out)"));
+        CK(tmp.alloc(std::max<size_t>(tmp_bytes, 1), who.c_str(), what + " (the sort's temporaries)"));
+        if (n_pos > 0) {
+            CK(d_os.alloc((size_t)n_pos * dim));
+            CK(d_pos.alloc((size_t)n_pos));
+        }
+    }
+    if (rk_folded(kind) || kind == RK_INDICATOR) CK(d_arg.alloc(dim));
+    // ---- nothing was launched so far ----
+    CK(normalize_history(src, g_lo, g_hi));
+    CK(ensure_history(dst, rows));
+    if (d_arg.p) HIPCK(hipMemcpyAsync(d_arg.p, arg, (size_t)dim * sizeof(double), hipMemcpyHostToDevice, src->stream));
+    RkWindow w;
+    w.g_lo = (uint64_t)g_lo; w.g_up = (uint64_t)(g_hi - n); w.n = (uint64_t)n; w.n_local = src->n_local; w.S = S64;
+    if (!sorted) {
+        const uint64_t total = S64 * ld;
+        const unsigned nb = (unsigned)std::min<uint64_t>(2048, (total + RK_THREADS - 1) / RK_THREADS);
+        hipLaunchKernelGGL(rk_indicator_kernel, dim3(nb), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, dim, w, (const double*)d_arg.p, dst->hist);
+        HIPCK(hipGetLastError());
+    } else {
+        std::vector<unsigned long long> hpos((size_t)n_pos);
+        for (int32_t j = 0; j < n_pos; ++j) hpos[(size_t)j] = (unsigned long long)pos[j];
+        if (n_pos > 0) HIPCK(hipMemcpyAsync(d_pos.p, hpos.data(), hpos.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, src->stream));
+        unsigned long long* k_in = keys.p;
+        unsigned long long* k_out = keys.p + (size_t)bc * S;
+        for (uint32_t k0 = 0; k0 < dim; k0 += bc) {
+            const uint32_t b = std::min(bc, dim - k0);
+            const uint32_t kw = std::min<uint32_t>(b, RK_THREADS), n_tiles = (b + kw - 1) / kw;
+            uint64_t nby = 1;
+            CK(rows_grid(S64, n_tiles, (uint64_t)(RK_THREADS / kw) * RK_UNR, who.c_str(), &nby));
+            hipLaunchKernelGGL(rk_keys_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, w, k0, b, kw,
+                               rk_folded(kind) ? 1u : 0u, (const double*)d_arg.p, k_in);
+            HIPCK(hipGetLastError());
+            size_t t = tmp_bytes;      // (the temporaries of a full batch hold those of the last, partial one)
+            HIPCK(rank_sort(tmp.p, &t, k_in, k_out, b, S, src->stream));
+            if (n_pos > 0) {
+                hipLaunchKernelGGL(rk_pick_kernel, dim3(((unsigned)n_pos * b + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, src->stream,
+                                   (const unsigned long long*)k_out, S64, k0, b, dim, (const unsigned long long*)d_pos.p, (uint32_t)n_pos, d_os.p);
+                HIPCK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(rk_score_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, dim, w, k0, b, kw,
+                               kind, (const double*)d_arg.p, (const unsigned long long*)k_out, dst->hist);
+            HIPCK(hipGetLastError());
+        }
+        if (n_pos > 0) HIPCK(hipMemcpyAsync(order_stats, d_os.p, (size_t)n_pos * dim * sizeof(double), hipMemcpyDeviceToHost, src->stream));
+    }
+    // the ln-likes of the same generations, and what bpm_set_history + bpm_set_loglike leave behind: the state = the last row, its ln-likes
+    const size_t half = (size_t)n * src->n_local, row_d = (size_t)dst->n_local * dst->ld;
+    HIPCK(hipMemcpyAsync(dst->llhist, src->llhist + (size_t)g_lo * src->n_local, half * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    HIPCK(hipMemcpyAsync(dst->llhist + half, src->llhist + (size_t)(g_hi - n) * src->n_local, half * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    HIPCK(hipMemcpyAsync(dst->G, dst->hist + (size_t)(rows - 1) * row_d, row_d * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
+    HIPCK(hipMemcpyAsync(dst->ll, src->llhist + (size_t)(g_hi - 1) * src->n_local, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     for (int64_t r = 0; r < rows && r < (int64_t)dst->hist_tag.size(); ++r) dst->hist_tag[(size_t)r] = -1;
     dst->hist_rows = rows;
     dst->rows_logical = rows;

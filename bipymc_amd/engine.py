@@ -574,6 +574,30 @@ class HipEngine(object):
             raise
         return dst
 
+    def rank_history(self, g_lo, g_hi, kind, arg=None, positions=(), dst=None):
+        """-> (HipEngine, order_stats (len(positions), dim)): a second, ordinary engine of this one's shape whose resident history is a
+        transform of the split rows of history rows [g_lo, g_hi) -- kind 0 the pooled average ranks, 1 their normal scores, 2 those of
+        |x - arg[k]|, 4 the ranks of |x - arg[k]|, 3 the indicator x <= arg[k] -- and the `positions`-th smallest values of every coordinate
+        (bpm_rank_history; bipymc_amd/rank_diagnostics.py).  dst: an engine an earlier call returned, to be filled again (None: a new one,
+        closed when the call fails).  A snapshot; the caller closes it.  Single rank only."""
+        if self.world_size != 1:
+            raise NotImplementedError("rank_history: pooled ranks are built on a single rank only (world_size = %d)" % self.world_size)
+        a = None if arg is None else np.ascontiguousarray(np.asarray(arg, dtype=np.float64).reshape(self.dim))
+        pos = np.ascontiguousarray(np.asarray(positions, dtype=np.int64).reshape(-1))
+        out = np.empty((len(pos), self.dim), dtype=np.float64)
+        own = dst is None
+        if own:
+            dst = HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=self.dim, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,
+                            device=self.device, burnin_gen=0, outlier_every=0, keep_history=True, lib=self.lib)
+        try:
+            self._ck(self.lib.bpm_rank_history(self._h, dst._h, int(g_lo), int(g_hi), int(kind), None if a is None else _dptr(a), len(pos),
+                                               pos.ctypes.data_as(C.POINTER(C.c_int64)) if len(pos) else None, _dptr(out) if len(pos) else None))
+        except BaseException:
+            if own:
+                dst.close()
+            raise
+        return dst, out
+
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None
                 for a in (p_cr, delta_m, n_cr_updates)]

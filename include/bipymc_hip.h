@@ -406,6 +406,33 @@ int bpm_derive(bpm_handle_t h, int64_t n_burn, int64_t* counts, double* sums, in
  * without keep_history, with another target, dim != n_out or another n_chains, world_size != 1 on either (single rank only), a derived history
  * larger than the free device memory (the message names the requirement). */
 int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst);
+/* A RANKED HISTORY IS A HISTORY: the one transform of a history that is no function of one sample -- the pooled rank of every value within
+ * its coordinate -- written into the history of `dst`, a second, ordinary handle as bpm_derive_history takes one (host-callback target,
+ * keep_history = 1, src's dim and n_chains), so that bpm_diag_split_moments / bpm_diag_autocov over dst give the rank-normalized split-R-hat
+ * and the bulk and tail ESS of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021), which Stan and ArviZ report (the reference stops at
+ * param_est's mean and standard deviation); bipymc_amd/rank_diagnostics.py drives the fills.
+ * The window is bpm_diag_split_moments': history rows [g_lo, g_hi), n = (g_hi - g_lo) / 2 (at least 4).  dst gets 2n rows: src's rows
+ * [g_lo, g_lo + n), then [g_hi - n, g_hi) (an odd window drops its middle row), so the split statistics over dst's rows [0, 2n) use exactly
+ * src's half-chains.  Per coordinate k over the S = 2 n n_local values of these rows, kind
+ *   0  the average rank r (1-based; ties share the mean of their ranks; -0.0 and +0.0 are ties): half-integers, exact;
+ *   1  z = Phi^-1((r - 3/8) / (S + 1/4)) of x;
+ *   2  the same z of |x - arg[k]|;     4  the same r of |x - arg[k]|;
+ *   3  1.0 where x <= arg[k], else 0.0 (no sort; n_pos must be 0).
+ * arg: dim doubles (kinds 2, 3, 4; otherwise not read, may be NULL).  A coordinate whose window holds a NaN is NaN throughout (all kinds but
+ * 3); +-inf are ordinary values.  order_stats[j * dim + k], j < n_pos (of |x - arg[k]| for kinds 2 and 4): the pos[j]-th smallest value
+ * (0-based, pos[j] < S; NaN sorts last, so position S - 1 tells whether there is one; a zero comes back as +0.0) -- what a median and
+ * np.quantile's interpolation need.  dst's ln-like history is src's rows of the same generations, its state its last row: dst comes out as
+ * bpm_set_history and bpm_set_loglike leave a handle, and may be filled again.  A snapshot.  The columns are sorted in batches (one segment
+ * of a segmented radix sort per column) of as many columns as fit a scratch budget -- keys in, keys out and the sort's temporaries, about
+ * 24 S bytes per column; a quarter of the free memory; BPM_RANK_SCRATCH_MB in the environment sets it, BPM_RANK_BATCH_COLS the batch itself
+ * -- and batch * S < 2^31; the result does not depend on the batch, the time does: the sort runs one workgroup per column.  Every check and every allocation comes before any launch;
+ * nothing src's sampler reads is written (a history kept in position order is put into chain order first, as bpm_get_history does); every
+ * temporary is freed on return.  Errors: a null handle, dst == src, different devices, an unknown kind, a missing arg, a position outside
+ * [0, S), no resident history on src (keep_history = 0), a range out of bounds, n < 4, a dst without keep_history, with another target, dim
+ * or n_chains, world_size != 1 on either (single rank only), S >= 2^31, one column's scratch beyond the budget or scratch or history beyond
+ * the free device memory (the message names the requirement). */
+int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
+                     const int64_t* pos, double* order_stats);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
