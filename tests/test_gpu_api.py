@@ -870,6 +870,49 @@ def test_serial_api_demc_class():
         t.run_mcmc(100, np.zeros(3), delayed_accept=False)
 
 
+@pytest.mark.parametrize("d", [6, 600])
+def test_serial_demc_class_device_and_host_paths_equal_the_oracle(d):
+    """bipymc_amd.samplers.DeMc with a fixed seed, run twice: on the bound ln_like of the shipped Gauss_100D (recognised: evaluated on the device, the
+    generation loop is bpm_step on BPM_ALGO_DEMC_SYNC) and on the same density behind a plain Python function (the host path: one bpm_propose / bpm_commit
+    round per generation, the commit kernel banks into x_next) -- d = 6 (16 lanes per chain) and d = 600 (the looped wide-row kernels).  The two runs and
+    OracleSampler(ALGO_DEMC_SYNC) started from the class's own jittered start (history row 0) with the class's run options (samplers.py:283: jitter std
+    sqrt(varepsilon * 1e-3), no shuffle) give the same chains: accept counts equal, the two paths 1e-11 / 1e-13 apart (two summation orders of one
+    formula), each 1e-10 / 1e-12 from the oracle (tests/test_gpu_shipped_path.py: floats after G generations).  varepsilon = 1e-21 with
+    inflate = 1e21 starts the chains with unit variance (samplers.py:255-259) and makes the per-generation jitter 1e-12, DREAM's default: the
+    float32 Box-Muller of a larger one would be the difference the test sees."""
+    from bipymc_amd.samplers import DeMc
+    from bipymc_amd.utils import d100_gauss
+    from oracle import sampler_ref as R
+    N, gens, seed = 16, 40, 4242
+    tgt = d100_gauss.Gauss_100D(rho=0.3, dim=d)
+    theta_0 = np.linspace(-1.0, 1.0, d)
+
+    def py_ll(theta):
+        return tgt.ln_like(theta)
+
+    runs = []
+    for fn, on_device in ((tgt.ln_like, True), (py_ll, False)):
+        s = DeMc(fn, n_chains=N, seed=seed)
+        s.run_mcmc(N * (gens + 1), theta_0, varepsilon=1e-21, inflate=1e21)
+        assert s._device_target == on_device
+        assert s.super_chain.shape == (N * (gens + 1), d)
+        runs.append((s.super_chain, s.n_accepted, s.n_rejected))
+        s._engine.close()          # (the class refers to itself through its frozen ln_like_fn: left alone, its device memory would wait for a garbage collection)
+    (dev, acc_dev, rej_dev), (host, acc_host, rej_host) = runs
+    X0 = dev[:N]
+    assert np.array_equal(X0, host[:N]) and np.all(np.std(X0, axis=0) > 0.3)       # the same jittered start, of unit variance
+    np.testing.assert_allclose(dev, host, rtol=1e-11, atol=1e-13)
+    assert acc_dev == acc_host and rej_dev == rej_host
+    params = R.gauss_equicorr_params(0.3, np.sqrt(np.arange(d) + 1.0))
+    ora = R.OracleSampler(R.ALGO_DEMC_SYNC, N, d, R.TARGET_GAUSS_EQUICORR, params, seed)
+    ora.set_state(X0)
+    ora.run(gens, flip=0.0, shuffle=False, epsilon=float(np.sqrt(1e-21 * 1e-3)), gamma=None)
+    assert 0 < ora.local_n_accepted < N * gens
+    assert acc_dev == 1 + ora.local_n_accepted and rej_dev == ora.local_n_rejected - 1          # samplers.py:30-31: the class starts at 1 / 0
+    np.testing.assert_allclose(dev, ora.super_chain(), rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(host, ora.super_chain(), rtol=1e-10, atol=1e-12)
+
+
 def test_posterior_moments_at_baseline_sizes():
     """'Posterior moments within 1 % of reference' (BASELINE.json north_star) at the BASELINE sizes, PER COORDINATE (the pooled form
     hid a per-coordinate spread of 0.988 ... 1.016 over 1200 generations, and 3.5 % was what this test allowed): every coordinate's variance within 1 %

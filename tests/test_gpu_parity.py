@@ -518,24 +518,42 @@ def test_demc_edge_shapes(N, d):
         _check_generation(eng, ora, N, d, False, 5)
 
 
-@pytest.mark.parametrize("N,d,tgt", [(8, 2, "banana"), (64, 2, "banana"), (33, 16, "gauss"), (10, 100, "gauss"), (5, 3, "gauss")])
+@pytest.mark.parametrize("N,d,tgt", [(8, 2, "banana"), (64, 2, "banana"), (33, 16, "gauss"), (10, 100, "gauss"), (5, 3, "gauss"),
+                                     (48, 200, "gauss"), (40, 400, "gauss"), (24, 640, "gauss"), (16, 1025, "gauss"),      # two / four pairs per lane, the looped kernel
+                                     (33, 8, "mix"), (24, 130, "mix"), (16, 514, "mix")])
 def test_demc_sync_mode_parity(N, d, tgt):
     """Synchronous DE-MC (serial `DeMc` of samplers.py:237-308, delayed_accept=True): pair from all OTHER
-    chains, updates banked, no gamma jumps -- engine vs oracle, generation by generation."""
+    chains, updates banked, no gamma jumps -- engine vs oracle, generation by generation.
+
+    Floats: epsilon = 1e-4 here, and the jitter is a float32 Box-Muller on both sides (1e-5 * epsilon = 1e-9 absolute apart: _check_generation), which
+    is this test's state tolerance; the ln-likes get _check_generation's allowance for that state difference (1e3 * 1e-9).  alpha = exp(ll_prop - ll_cur)
+    carries the ABSOLUTE error of that difference as its RELATIVE error: rtol = max(1e-8, twice the ln-like allowance) against the oracle -- and, free
+    of the jitter, 1e-12 against the same formula (samplers.py:328-332) over the engine's own ln-likes."""
     if tgt == "banana":
         tid, params = R.TARGET_BANANA_2D, R.banana_params()
+    elif tgt == "mix":
+        tid, params = R.TARGET_MIXTURE_PAIRS, _mix_params()
     else:
         tid, params = R.TARGET_GAUSS_EQUICORR, _gauss_params(d)
     eng, ora = _pair_traced(R.ALGO_DEMC_SYNC, N, d, tid, params, 31)
-    X = np.random.RandomState(6).normal(size=(N, d)) + 0.3
+    rs = np.random.RandomState(6)
+    X = rs.normal(size=(N, d)) + 0.3
+    if tgt == "mix":
+        X = np.where(rs.uniform(size=(N, 1)) < 0.3, 0.0, 2.0) + 0.3 * rs.normal(size=(N, d))
     eng.set_state(X); ora.set_state(X)
     eng.set_trace(True)
-    eng.begin_run(epsilon=1e-4, gamma=0.7, shuffle=False, flip=0.0)
+    gamma = 0.7 if d <= 100 else 2.38 / np.sqrt(2.0 * d)        # (the wide rows: demc.py:162's own scale, or nothing is ever accepted there)
+    eng.begin_run(epsilon=1e-4, gamma=gamma, shuffle=False, flip=0.0)
     ora.local_n_accepted, ora.local_n_rejected = 0, 1
+    atol_state = 1e-9                                      # epsilon = 1e-4 float32 jitter
+    atol_ll = max(1e-12, 1e3 * atol_state)
+    n_acc = 0
+    ll_prev = eng.get_loglike()
+    np.testing.assert_allclose(ll_prev, ora.ll, rtol=RTOL_STEP, atol=1e-12)
     for g in range(12):
         ora.trace = []
         eng.step(1)
-        ora._generation(g, 0.0, False, 1e-4, 1e-2, 0.7)
+        ora._generation(g, 0.0, False, 1e-4, 1e-2, gamma)
         tr = eng.get_trace()
         assert np.array_equal(tr["partners"][:, 0], ora.trace[-1]["pa"]) and np.array_equal(tr["partners"][:, 1], ora.trace[-1]["pb"])
         assert np.all(tr["partners"][:, 0] != np.arange(N)) and np.all(tr["partners"][:, 1] != np.arange(N))
@@ -543,9 +561,25 @@ def test_demc_sync_mode_parity(N, d, tgt):
         assert np.array_equal(tr["accepted"].astype(bool), ora.trace[-1]["accepted"])
         assert not tr["jump"].any()
         np.testing.assert_allclose(eng.get_state(), ora.X, rtol=1e-12, atol=1e-9)     # epsilon = 1e-4 float32 jitter
+        ll_now = eng.get_loglike()
+        err_ll = float(np.max(np.abs(ll_now - ora.ll)))
+        err_lp = float(np.max(np.abs(tr["ll_prop"] - ora.trace[-1]["ll_prop"])))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            err_al = float(np.nanmax(np.abs(tr["alpha"] - ora.trace[-1]["alpha"]) / ora.trace[-1]["alpha"]))
+        print("generation %d: max |ll - oracle| %.3e, |ll_prop - oracle| %.3e, alpha relative %.3e" % (g, err_ll, err_lp, err_al))
+        np.testing.assert_allclose(ll_now, ora.ll, rtol=RTOL_STEP, atol=atol_ll)
+        np.testing.assert_allclose(tr["ll_prop"], ora.trace[-1]["ll_prop"], rtol=RTOL_STEP, atol=atol_ll)
+        np.testing.assert_allclose(tr["alpha"], ora.trace[-1]["alpha"], rtol=max(1e-8, 2.0 * atol_ll), atol=1e-300)
+        np.testing.assert_allclose(tr["alpha"], R.mut_prop_ratio(ll_prev, tr["ll_prop"]), rtol=1e-12, atol=1e-300)
+        # an accepted chain's ln-like is its proposal's, a rejected one keeps its own (the banana's lean form re-evaluates it from the row on demand)
+        np.testing.assert_allclose(ll_now, np.where(tr["accepted"].astype(bool), tr["ll_prop"], ll_prev), rtol=RTOL_STEP, atol=1e-12)
+        ll_prev = ll_now
+        n_acc += int(np.count_nonzero(ora.trace[-1]["accepted"]))
+    assert 0 < n_acc < 12 * N                              # both branches ran: accepted, and banked unchanged
     st = eng.stats()
     assert st["local_n_accepted"] == ora.local_n_accepted and st["history_rows"] == 13
     np.testing.assert_allclose(eng.get_history(), ora.history_array(), rtol=1e-12, atol=1e-9)
+    np.testing.assert_allclose(eng.get_loglike_history(), np.stack(ora.ll_history), rtol=RTOL_STEP, atol=atol_ll)
 
 
 def test_gpu_reproduces_committed_engine_fixture(golden_dir):
@@ -582,6 +616,13 @@ def test_gpu_reproduces_committed_engine_fixture(golden_dir):
     (R.ALGO_DREAM, 600, 12, dict(burnin_gen=5, n_cr_gen=1)),         # 16 coordinates per lane
     (R.ALGO_DREAM, 1201, 10, dict(burnin_gen=4, n_cr_gen=1)),        # 32 coordinates per lane, odd d
     (R.ALGO_DEMC, 2000, 8, dict(p_snooker=0.3)),
+    # synchronous DE-MC, what DeMc(python_callable) drives: ONE propose / commit round per generation, the commit kernels' x_next branch (kernels.h at
+    # d = 3, 100, 200; phase_wide_commit_kernel at 600 and 1201, odd d)
+    (R.ALGO_DEMC_SYNC, 3, 10, dict()),
+    (R.ALGO_DEMC_SYNC, 100, 24, dict()),
+    (R.ALGO_DEMC_SYNC, 200, 12, dict()),
+    (R.ALGO_DEMC_SYNC, 600, 12, dict()),
+    (R.ALGO_DEMC_SYNC, 1201, 10, dict()),
 ])
 def test_propose_commit_path_against_oracle(algo, d, N, kw):
     """The propose / commit kernels (arbitrary Python ln_like_fn: samplers.py:36-43) compared with OracleSampler(ll_fn=...)
@@ -602,17 +643,26 @@ def test_propose_commit_path_against_oracle(algo, d, N, kw):
     eng.begin_run()
     n_gens = 9
     prev = X0
+    sync = algo == R.ALGO_DEMC_SYNC
+    n_acc = 0
     for g in range(n_gens):
         ora.trace = []
-        for ph in range(2):
+        for ph in range(1 if sync else 2):
             props, ids = eng.propose()
+            if sync:
+                assert np.array_equal(ids, np.arange(N))          # every chain proposes, in chain order (samplers.py:268)
             eng.commit(np.array([py_ll(p) for p in props]))
         # the oracle's generation g of the same run (k restarts at 0 in run(): drive _generation directly)
         ora._generation(g, 0.5, True, 1e-12 if algo == R.ALGO_DREAM else 1e-15, 1e-2, None)
         tr = ora.trace[0]
         acc_o = np.zeros(N, dtype=bool)
-        for phn in ("phase0", "phase1"):
-            acc_o[tr[phn]["ids"]] = tr[phn]["accepted"]
+        if sync:                                                  # _generation_sync's trace: one round, every chain
+            acc_o[:] = tr["accepted"]
+            assert np.all(tr["pa"] != np.arange(N)) and np.all(tr["pb"] != np.arange(N)) and np.all(tr["pa"] != tr["pb"])
+        else:
+            for phn in ("phase0", "phase1"):
+                acc_o[tr[phn]["ids"]] = tr[phn]["accepted"]
+        n_acc += int(np.count_nonzero(acc_o))
         now = eng.get_state()
         changed = np.any(now != prev, axis=1)        # (against the ENGINE's previous state: a snooker proposal of a wide row differs from the
         prev = now                                   #  oracle's in the last bits -- another summation order of its dot products)
@@ -620,12 +670,15 @@ def test_propose_commit_path_against_oracle(algo, d, N, kw):
         assert np.array_equal(changed, acc_o), g
         np.testing.assert_allclose(eng.get_state(), ora.X, rtol=1e-11, atol=1e-13)
         np.testing.assert_allclose(eng.get_loglike(), ora.ll, rtol=1e-11, atol=1e-12)
+    assert 0 < n_acc < n_gens * N                                 # accepted updates and unchanged rows both went through the commit kernel
     st = eng.stats()
     assert st["local_n_accepted"] == ora.local_n_accepted and st["local_n_rejected"] == ora.local_n_rejected
     if algo == R.ALGO_DREAM:
         np.testing.assert_allclose(st["p_cr"], ora.cr.p_cr, rtol=1e-9)
         np.testing.assert_allclose(st["n_cr_updates"], ora.cr.n_cr_updates, rtol=0)
     np.testing.assert_allclose(eng.get_history(), ora.history_array(), rtol=1e-11, atol=1e-13)
+    if sync:
+        np.testing.assert_allclose(eng.get_loglike_history(), np.stack(ora.ll_history), rtol=1e-11, atol=1e-12)
 
 
 # ------------------------------------------------------------------ ln_like_fn as HIP source (bpm_set_device_likelihood) against the oracle
@@ -658,6 +711,9 @@ __device__ double ln_like_finish(const double* acc, int d, const double* p) { re
     (R.ALGO_DEMC, 150, 40, dict(p_snooker=0.2)),
     (R.ALGO_DEMC_SYNC, 3, 10, dict()),
     (R.ALGO_DREAM, 600, 12, dict(burnin_gen=5, n_cr_gen=1)),
+    (R.ALGO_DEMC_SYNC, 100, 24, dict()),                 # synchronous DE-MC on the wide rows: one wavefront per chain, fused ...
+    (R.ALGO_DEMC_SYNC, 300, 12, dict()),                 # ... four pairs per lane ...
+    (R.ALGO_DEMC_SYNC, 600, 12, dict()),                 # ... and the looped kernel: never fused (d > 512), the three-kernel form with x_next
 ])
 def test_hip_source_likelihood_against_oracle(algo, d, N, kw, fused, monkeypatch):
     """Round 5: the caller's likelihood written as HIP source, compiled with hiprtc into a kernel between the proposal and the commit kernel, the

@@ -12,6 +12,7 @@ Tolerances.
                = 3.6e-15: the margin is there because the grid moves with S.
   R-hat / ESS  the project's criteria (tests/test_gpu_diagnostics.py): r_hat 1e-10 relative; ess 1e-8 relative where the pair sum that ended
                Geyer's sequence is further than 1e-6 from zero, which must hold for at least 80 % of the coordinates; capped equal."""
+import gc
 import os
 import sys
 
@@ -259,6 +260,9 @@ def test_no_side_effects_and_no_leak():
     a, b = start(), start()
     s = _over(a)
     r1 = s.convergence_diagnostics_rank(n_burn=256 * 3 + 9)          # (also loads whatever the first call loads)
+    # earlier tests' sampler objects refer to themselves (DeMc / DeMcMpi: _frozen_ln_like_fn) and give their device memory back only when the cycle
+    # collector runs: it runs HERE, not at some allocation between the two readings, where the memory it frees would look like a negative leak
+    gc.collect()
     free0 = _free_device_memory()
     r2 = s.convergence_diagnostics_rank(n_burn=256 * 3 + 9)
     with s.rank_history(n_burn=256 * 3 + 9, folded=True):

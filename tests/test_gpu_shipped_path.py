@@ -18,7 +18,9 @@ pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-10, 1e-12
 
 
-def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows):
+def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, launches=None):
+    """launches: (update dispatches on the library's own queue, on the HIP stream) the run has to add; None = the shipped path of DE-MC and
+    DREAM, two update launches per generation, every one through the own queue"""
     from bipymc_amd.engine import HipEngine
     eng = HipEngine(algo=algo, n_chains=N, dim=d, target_id=target_id, target_params=params, seed=seed, **okw)
     ora = R.OracleSampler(algo, N, d, target_id, params, seed, **okw)
@@ -31,7 +33,10 @@ def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows):
     eng.step(gens)                         # NO trace: phase_args_hot() holds, the HOT instantiations run
     eng.synchronize()
     ls = eng.launch_stats()
-    assert ls["direct"] - ls0["direct"] == 2 * gens and ls["stream"] == ls0["stream"], (ls0, ls)   # every update kernel through the own queue
+    if launches is None:
+        assert ls["direct"] - ls0["direct"] == 2 * gens and ls["stream"] == ls0["stream"], (ls0, ls)   # every update kernel through the own queue
+    else:
+        assert (ls["direct"] - ls0["direct"], ls["stream"] - ls0["stream"]) == tuple(launches), (ls0, ls)
     ora.run(gens)
     st = eng.stats()
     # ---- integers: exact
@@ -255,6 +260,16 @@ def _target_case(kind, N, d, rs):
 #   g_fused_gauss[v][shape]   v = 0, 1, 2; 0..6     -> test_every_dispatch_table_entry_equals_the_oracle[gauss-*]   (+ cfg2 / the wide-row / random tests above)
 #   g_fused_mixture[v][shape] v = 0, 1, 2; 0..6     -> test_every_dispatch_table_entry_equals_the_oracle[mix-*]     (+ cfg5's share; DE-MC: v = 0 was statistical only)
 #   g_fused_banana[v]         v = 0, 1, 2           -> test_every_dispatch_table_entry_equals_the_oracle[banana-*]  (+ cfg3; DREAM: v = 1, 2 were untested)
+# Synchronous DE-MC (BPM_ALGO_DEMC_SYNC: what bipymc_amd.samplers.DeMc runs on) takes row 0 of the same tables with PhaseArgs::mode == 2 and x_next set
+# (prepare_generation: the general instantiation, never a HOT one -- phase_args_hot wants x_next == nullptr), one launch per generation on the HIP stream:
+#   g_fused_gauss[0][0..6], mode 2                  -> test_synchronous_demc_on_every_kernel_shape_equals_the_oracle[gauss-*]  (+ its edge rows: N = 4 / d = 1, odd d
+#                                                      at 257, 513, 2047, 3001)
+#   g_fused_mixture[0][0..6], mode 2                -> test_synchronous_demc_on_every_kernel_shape_equals_the_oracle[mix-*]
+#   g_fused_banana[0], mode 2 (always lean)         -> test_synchronous_demc_on_every_kernel_shape_equals_the_oracle[banana-*]
+#   more chains than are resident at once           -> test_synchronous_demc_keeps_the_state_frozen_in_large_populations (shapes 0, 1, 3, 6)
+# generation by generation with the trace: tests/test_gpu_parity.py::test_demc_sync_mode_parity; g_propose / g_commit with x_next (kernels.h and kernels_wide.h):
+# ::test_propose_commit_path_against_oracle[2-*]; a HIP-source likelihood, fused and as three kernels: ::test_hip_source_likelihood_against_oracle[*-2-*];
+# the class itself on the device and on the host path: tests/test_gpu_api.py::test_serial_demc_class_device_and_host_paths_equal_the_oracle.
 # per-generation trace parity of the two combinations that had none: tests/test_gpu_parity.py::test_dream_banana_generation_parity,
 # ::test_demc_mixture_generation_parity; the reference's own scenarios (tests/test_banana.py:123-127, tests/test_dblgauss.py:130-133):
 # tests/test_gpu_api.py::test_dream_banana_reference_scenario, ::test_demc_bimodal_and_banana_reference_scenarios.
@@ -276,6 +291,63 @@ def test_every_dispatch_table_entry_equals_the_oracle(kind, v, shape):
         algo, N, gens, kw = R.ALGO_DREAM, (40 if d > 128 else 96), 9, dict(del_pairs=pairs, n_cr=3, burnin_gen=3, n_cr_gen=1)
     tid, params, X0 = _target_case(kind, N, d, rs)
     _run_both(algo, N, d, tid, params, 300 + 10 * v + shape, X0, gens, kw, hist_rows=(2, gens))
+
+
+def _sync_case(kind, N, d):
+    rs = np.random.RandomState(7000 + 13 * N + d + (0 if kind == "gauss" else 50 if kind == "mix" else 90))
+    return _target_case(kind, N, d, rs)
+
+
+# (N, d): the seven kernel shapes at the dispatch-table test's sizes for both targets of any width, the banana, then the edge rows
+_SYNC_TABLE = ([(kind, 48 if _SHAPE_DIMS[sh] > 128 else 130, _SHAPE_DIMS[sh]) for kind in ("gauss", "mix") for sh in range(7)] + [("banana", 130, 2)] +
+               [("gauss", 4, 1),          # the smallest population (samplers.py:249): a pool of 3
+                ("gauss", 5, 513),        # the looped kernel, odd d: one whole chunk of 256 pairs + a chunk of one pair
+                ("gauss", 9, 3001),       # ... five whole chunks + a partial one
+                ("gauss", 7, 257),        # two pairs per lane, odd d
+                ("gauss", 6, 2047)])
+
+
+@pytest.mark.parametrize("kind,N,d", _SYNC_TABLE, ids=["%s-N%d-d%d" % t for t in _SYNC_TABLE])
+def test_synchronous_demc_on_every_kernel_shape_equals_the_oracle(kind, N, d):
+    """Synchronous DE-MC (samplers.py:268-308 with delayed_accept: every chain proposes from the population at the START of the generation, the pair out
+    of all OTHER chains, updates banked in x_next and copied over the state after the launch) on the product library, no trace, default begin_run(), one
+    step(10): every kernel shape's x_next branch for the Gaussian and the mixture, the banana (lean form: the ln-like cache is not written by the kernel),
+    odd widths (the padding column travels through the double2 stores of x_next and back over the state) -- against the oracle's _generation_sync.
+    Launch counts: group_goes_direct() excludes the mode from the library's own queue and group_generation() launches cur_args[0] alone, once per
+    generation, on the HIP stream -- so 0 direct and `gens` stream dispatches."""
+    gens = 10
+    tid, params, X0 = _sync_case(kind, N, d)
+    _run_both(R.ALGO_DEMC_SYNC, N, d, tid, params, 500 + N + d, X0, gens, {}, hist_rows=(2, gens), launches=(0, gens))
+
+
+@pytest.mark.parametrize("N,d,kind", [(20001, 2, "banana"), (4097, 8, "mix"), (3001, 100, "gauss"), (700, 600, "gauss")])
+def test_synchronous_demc_keeps_the_state_frozen_in_large_populations(N, d, kind):
+    """More chains than the device holds wavefronts for at once (one lane / four lanes / one wavefront per chain, the looped kernel): a chain updated late in
+    the launch reads partner rows of chains that finished long before, so an update written into the state matrix instead of x_next would be seen.  Six
+    generations against the oracle as everywhere in this file; then, generation by generation over the first three (step(1) each), the state itself: a chain
+    the oracle did not accept keeps its row bit for bit (x_next carries the unchanged row back), an accepted one moved."""
+    from bipymc_amd.engine import HipEngine
+    tid, params, X0 = _sync_case(kind, N, d)
+    _run_both(R.ALGO_DEMC_SYNC, N, d, tid, params, 900 + d, X0, 6, {}, hist_rows=(1, 6), launches=(0, 6))
+    eng = HipEngine(algo=R.ALGO_DEMC_SYNC, n_chains=N, dim=d, target_id=tid, target_params=params, seed=900 + d)
+    ora = R.OracleSampler(R.ALGO_DEMC_SYNC, N, d, tid, params, 900 + d)
+    eng.set_state(X0)
+    ora.set_state(X0)
+    ora.trace = []
+    ora.run(3)
+    eng.begin_run()
+    prev = eng.get_state()
+    assert np.array_equal(prev, X0)
+    for g in range(3):
+        eng.step(1)
+        now = eng.get_state()
+        acc = ora.trace[g]["accepted"]
+        assert 0 < np.count_nonzero(acc) < N
+        assert np.array_equal(now[~acc], prev[~acc]), g
+        assert np.all(np.any(now[acc] != prev[acc], axis=1)), g
+        np.testing.assert_allclose(now, ora.history[g + 1], rtol=RTOL, atol=ATOL)
+        prev = now
+    eng.close()
 
 
 def _random_case(rs):
