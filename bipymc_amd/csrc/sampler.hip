@@ -501,12 +501,9 @@ struct HistorySnapshot {
     int check(const bpm_sampler* s, const char* who, const char* first_call) const;
 };
 
+#include "device_memory.h"      // MemKind, DevTemp, MemRegistry: the only code that allocates or frees device and pinned host memory
+
 // ---- what a program compiled at run time leaves on the device: owned from the moment it exists ------------------------------------------
-template <class T>
-static int dev_alloc(T** p, size_t n) {
-    HIPCK(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-}
 // A loaded code object: unloaded when its owner goes, unless leak()ed (bpm_destroy under a queue that may still run kernels).  The one place
 // that loads, looks up and unloads.
 struct Module {
@@ -530,24 +527,13 @@ struct Module {
 };
 // A caller's parameter block on the device: max(n, 1) doubles, zero-filled, then the caller's n -- enqueued on `stream`; the caller's array is
 // its own again once that stream has been waited for.
-struct DevParams {
-    double* p = nullptr;
-    DevParams() = default;
-    DevParams(DevParams&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevParams& operator=(DevParams&& o) noexcept {
-        if (this != &o) { release(); p = o.p; o.p = nullptr; }
-        return *this;
-    }
-    ~DevParams() { release(); }
+struct DevParams : DevTemp<double> {
     int upload(const double* src, int32_t n, hipStream_t stream) {
-        release();
-        CK(dev_alloc(&p, (size_t)std::max(n, 1)));
+        CK(alloc((size_t)std::max(n, 1)));
         HIPCK(hipMemsetAsync(p, 0, (size_t)std::max(n, 1) * sizeof(double), stream));
         if (n > 0) HIPCK(hipMemcpyAsync(p, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    void leak() { p = nullptr; }
 };
 // The caller's ln_like_fn as a kernel compiled from HIP source (user_likelihood.h; bpm_set_device_likelihood): bpm_step then drives a host-callback sampler ...
 struct UserLikelihood {
@@ -593,6 +579,7 @@ struct bpm_sampler {
     Layout L{};
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    MemRegistry mem;                  // owns every device and pinned host buffer named below
     // bpm_step_timed: ev0 rides on the first update launch of the call, ev1 on the last one
     bool timed_want_first = false;
     int64_t timed_skip = 0;           // update launches to let pass before ev0 is attached (see bpm_step_timed)
@@ -759,7 +746,7 @@ struct bpm_sampler {
     bool dq_enabled = true;           // bpm_set_launch_path
     bool shape_needs_scratch = false; // 1024 < d <= 2048 (16 coordinate pairs per lane): the update kernels spill to scratch memory, which the HIP
                                       // runtime provisions for ITS queues -- these samplers launch on the stream
-    bool coherent = false;            // state buffers live in cached-coherent device memory (dev_alloc_state)
+    bool coherent = false;            // state buffers live in cached-coherent device memory (state_mem)
     int dq_fence = bpm::DirectQueue::FENCED;   // fences of the update-kernel packets (run_generations)
     bool timed_direct = false;        // the last bpm_step_timed was timed by the queue's dispatch time stamps
     // run state
@@ -865,19 +852,15 @@ static int set_device(bpm_sampler* s) {
 // (hipDeviceMallocUncached on this runtime): local HBM mapped with the cached-coherent memory type, i.e. the XCDs' L2s stay coherent on
 // these lines by themselves (tools/micro/aql_direct.cpp: a dependent chain of kernels is correct on it with NO release fence between
 // the dispatches, wrong on hipMalloc memory).  Gathers from it cost 1-5 % more than from ordinary device memory.
-template <class T>
-static int dev_alloc_state(T** p, size_t n, bool coherent) {
+static MemKind state_mem(bool coherent) {
 #ifdef BPM_EXPERIMENT_COHERENT
-    if (coherent) {
-        HIPCK(hipExtMallocWithFlags(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T), hipDeviceMallocUncached));
-        return 0;
-    }
+    if (coherent) return MEM_UNCACHED;
 #endif
     (void)coherent;
-    return dev_alloc(p, n);
+    return MEM_DEVICE;
 }
 
-// Does memory from dev_alloc_state really stay coherent across the XCDs without a release fence?  What hipDeviceMallocUncached maps
+// Does memory of state_mem(true) really stay coherent across the XCDs without a release fence?  What hipDeviceMallocUncached maps
 // to is the runtime's choice (hsa_amd_pointer_info reports the same flags for it as for plain fine-grained memory, which is NOT
 // coherent that way), so the property itself is tested once per device: 48 dependent dispatches with acquire-only packets hand
 // every block of a 2 MB buffer from workgroup to workgroup; ordinary memory fails this in every element (tools/micro/aql_direct.cpp).
@@ -885,11 +868,12 @@ static int dev_alloc_state(T** p, size_t n, bool coherent) {
 #if defined(BPM_TEST_HOOKS) || defined(BPM_EXPERIMENT_COHERENT)
 static long long coherence_probe(bpm::DirectQueue* dq, bool coherent_alloc) {
     constexpr uint32_t NB = 4096, L = 48;
-    double* x = nullptr;
+    DevTemp<double> xb(state_mem(coherent_alloc));
     long long wrong = -1;
     const bpm::DqKernel* k = dq->kernel(reinterpret_cast<const void*>(coherence_probe_kernel));
     if (!dq->set_fence_kernel(reinterpret_cast<const void*>(queue_fence_kernel))) k = nullptr;      // (drain() behind release-less packets)
-    if (k && dev_alloc_state(&x, (size_t)NB * WAVE, coherent_alloc) == 0) {
+    if (k && xb.alloc((size_t)NB * WAVE) == 0) {
+        double* const x = xb.p;
         std::vector<double> h((size_t)NB * WAVE);
         bool run = hipMemset(x, 0, h.size() * sizeof(double)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
         for (uint32_t i = 0; i < L && run; ++i) {
@@ -903,7 +887,6 @@ static long long coherence_probe(bpm::DirectQueue* dq, bool coherent_alloc) {
         }
         (void)hipGetLastError();
     }
-    if (x) (void)hipFree(x);
     return wrong;
 }
 #endif
@@ -920,26 +903,38 @@ static bool state_memory_is_coherent(bpm::DirectQueue* dq, int device) {
 }
 #endif
 
-static int ensure_history(bpm_sampler* s, int64_t rows) {
+// The history's growth rule, stated once: the rows ensure_history(s, rows) allocates (0: it fits) ...
+static int64_t history_growth(const bpm_sampler* s, int64_t rows) {
     if (!s->cfg.keep_history) rows = std::min<int64_t>(rows, 1);
-    if (rows <= s->hist_cap) return 0;
+    return rows <= s->hist_cap ? 0 : std::max<int64_t>(rows, s->hist_cap + s->hist_cap / 2);
+}
+// ... and the same in bytes, for a caller that sizes its own scratch first: `what` ("derived", "ranked") names the history in the refusal
+static int history_growth_bytes(const bpm_sampler* s, int64_t rows, const std::string& who, const char* what, size_t mem_free, uint64_t* need) {
+    const uint64_t cap = (uint64_t)history_growth(s, rows);
+    *need = cap * s->n_local * ((uint64_t)s->ld + 1u) * sizeof(double);
+    if (*need > mem_free)
+        return fail(who + ": the " + what + " history of " + std::to_string((long long)cap) + " generations x " + std::to_string(s->n_local) + " chains x (" +
+                    std::to_string(s->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(*need >> 20)) + " MiB of device memory; " +
+                    std::to_string(mem_free >> 20) + " MiB are free");
+    return 0;
+}
+
+static int ensure_history(bpm_sampler* s, int64_t rows) {
+    const int64_t cap = history_growth(s, rows);
+    if (cap == 0) return 0;
     const bool was_direct = s->dq_active;
     CK(leave_direct(s));              // (kernels in flight on the library's own queue still write the old buffers)
-    int64_t cap = std::max<int64_t>(rows, s->hist_cap + s->hist_cap / 2);
     const size_t row_d = (size_t)s->n_local * s->ld;
-    double* nh = nullptr;
-    double* nl = nullptr;
-    CK(dev_alloc(&nh, (size_t)cap * row_d));
-    CK(dev_alloc(&nl, (size_t)cap * s->n_local));
+    DevTemp<double> nh, nl;
+    CK(nh.alloc((size_t)cap * row_d));
+    CK(nl.alloc((size_t)cap * s->n_local));
     if (s->hist_rows > 0) {
-        HIPCK(hipMemcpyAsync(nh, s->hist, (size_t)s->hist_rows * row_d * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        HIPCK(hipMemcpyAsync(nl, s->llhist, (size_t)s->hist_rows * s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        HIPCK(hipMemcpyAsync(nh.p, s->hist, (size_t)s->hist_rows * row_d * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        HIPCK(hipMemcpyAsync(nl.p, s->llhist, (size_t)s->hist_rows * s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     }
     HIPCK(hipStreamSynchronize(s->stream));
-    if (s->hist) HIPCK(hipFree(s->hist));
-    if (s->llhist) HIPCK(hipFree(s->llhist));
-    s->hist = nh;
-    s->llhist = nl;
+    s->mem.replace(&s->hist, nh);
+    s->mem.replace(&s->llhist, nl);
     s->hist_cap = cap;
     s->hist_tag.resize((size_t)cap, -1);
     s->dq_active = was_direct && g_disp.dq != nullptr;      // (inside a direct-mode generation: the stream is idle again, go on)
@@ -1023,37 +1018,23 @@ int HistorySnapshot::check(const bpm_sampler* s, const char* who, const char* fi
     return 0;
 }
 
-// Device memory that lives for one call: freed on every way out of it.  alloc() with a `what` first checks the free memory and names the
-// requirement in its error; without one it is dev_alloc.
+// How a buffer the sampler keeps between calls grows: the new one, n elements, belongs to this call until it holds the first n_kept of the old
+// one and (wait) the stream is done with the old one; only then does it take the old one's place in the registry, and the old one goes.  An
+// error on the way leaves the sampler as it was.
 template <class T>
-struct DevTemp {
-    T* p = nullptr;
-    DevTemp() = default;
-    DevTemp(DevTemp&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevTemp(const DevTemp&) = delete;
-    DevTemp& operator=(const DevTemp&) = delete;
-    ~DevTemp() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n, const char* who = nullptr, const std::string& what = std::string()) {
-        if (who) {
-            const size_t need = n * sizeof(T);
-            size_t mem_free = 0, mem_total = 0;
-            HIPCK(hipMemGetInfo(&mem_free, &mem_total));
-            if (need > mem_free)
-                return fail(std::string(who) + ": " + what + " need " + std::to_string(need >> 20) + " MiB of device memory; " +
-                            std::to_string(mem_free >> 20) + " MiB are free");
-        }
-        return dev_alloc(&p, n);
-    }
-};
-
-// A buffer the sampler keeps between calls (freed by bpm_destroy, which may decide to leak it), grown to `need` elements when it is smaller.
+static int regrow(bpm_sampler* s, T** p, size_t n, size_t n_kept, bool wait) {
+    DevTemp<T> fresh;
+    CK(fresh.alloc(n));
+    if (n_kept > 0) HIPCK(hipMemcpyAsync(fresh.p, *p, n_kept * sizeof(T), hipMemcpyDeviceToDevice, s->stream));
+    if (wait) HIPCK(hipStreamSynchronize(s->stream));
+    s->mem.replace(p, fresh);
+    return 0;
+}
+// ... to `need` elements when it is smaller, keeping nothing
 template <class T>
 static int grow_device(bpm_sampler* s, T** p, size_t* cap, size_t need) {
     if (need <= *cap) return 0;
-    if (*p) { HIPCK(hipStreamSynchronize(s->stream)); HIPCK(hipFree(*p)); *p = nullptr; *cap = 0; }
-    CK(dev_alloc(p, need));
+    CK(regrow(s, p, need, 0, *p != nullptr));
     *cap = need;
     return 0;
 }
@@ -1094,13 +1075,8 @@ static int ensure_gen_sums(bpm_sampler* s, int64_t rows) {
     const bool was_direct = s->dq_active;
     CK(leave_direct(s));
     const int64_t cap = std::max<int64_t>(std::max<int64_t>(rows, 1024), s->gen_sums_cap + s->gen_sums_cap / 2);
-    double* n = nullptr;
-    CK(dev_alloc(&n, (size_t)cap * 2 * s->ld));
-    if (s->gen_sums && s->rows_logical > 0)
-        HIPCK(hipMemcpyAsync(n, s->gen_sums, (size_t)std::min<int64_t>(s->rows_logical, s->gen_sums_cap) * 2 * s->ld * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (s->gen_sums) HIPCK(hipFree(s->gen_sums));
-    s->gen_sums = n;
+    const size_t n_kept = s->gen_sums && s->rows_logical > 0 ? (size_t)std::min<int64_t>(s->rows_logical, s->gen_sums_cap) * 2 * s->ld : 0;
+    CK(regrow(s, &s->gen_sums, (size_t)cap * 2 * s->ld, n_kept, true));
     s->gen_sums_cap = cap;
     s->dq_active = was_direct && g_disp.dq != nullptr;
     return 0;
@@ -1217,26 +1193,14 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
         if (s->peer_opened[p] && s->peer_base[p]) (void)hipIpcCloseMemHandle(s->peer_base[p]);
         if (s->peer_ctrl_opened[p] && s->peer_ctrl_base[p]) (void)hipIpcCloseMemHandle(s->peer_ctrl_base[p]);
     }
-    if (s->ctrl_fine && s->ctrl && free_buffers) (void)hipFree(s->ctrl);
-    if (s->arena) { s->G = nullptr; s->om = nullptr; }       // (both live inside the arena)
-    void* ptrs[] = {s->tb[0].chunk_count, s->tb[1].chunk_count, s->hist_tmp, s->gen_sums, s->gs_shift, s->gs_part, s->arena, s->tab_peerG, s->tab_all, s->om, s->sel, s->sel_state, s->okeys, s->olist, s->G, s->ll, s->hist, s->llhist, s->w_mean, s->tparams, s->cr_state_base, s->cr_p1, s->cr_p2[0], s->cr_p2[1], s->counters, s->acc_count,
-                    s->prop_buf, s->aux_buf, s->ids_buf, s->tb[0].perm, s->tb[0].inv, s->tb[0].plan, s->tb[0].sidx, s->tb[0].plan_count,
-                    s->tb[1].perm, s->tb[1].inv, s->tb[1].plan, s->tb[1].sidx, s->tb[1].plan_count, s->gamma_tab, s->x_next, s->accbits_all, s->PK, s->xstat, s->ckpt_G, s->ckpt_ll, s->ckpt_acc, s->ckpt_counters, s->trace_i32, s->trace_f64, s->trace_mask, s->scratch,
-                    s->dg_mean, s->dg_m2, s->dg_out, s->dg_part, s->qs_buf};
-    if (free_buffers)
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    if (s->h_ids) (void)hipHostFree(s->h_ids);
-    if (s->h_props) (void)hipHostFree(s->h_props);
-    if (s->h_ll) (void)hipHostFree(s->h_ll);
+    if (!free_buffers) s->mem.forget_all();
+    s->mem.free_all();
     for (hipEvent_t e : s->chunk_ev) if (e) (void)hipEventDestroy(e);
     // (the run-time modules and their parameter blocks go the way of the buffers)
     if (free_buffers) { s->like.fused.drop(s->dq); s->like = UserLikelihood(); s->derived = DerivedFunction(); }
     else { s->like.leak(); s->derived.leak(); }
-    for (auto& B : s->tb) {
-        if (B.count_h) (void)hipHostFree(B.count_h);
+    for (auto& B : s->tb)
         if (B.built) (void)hipEventDestroy(B.built);
-    }
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1380,7 +1344,9 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         const size_t om_bytes = want_om ? up((size_t)s->world * 2 * s->n_local * sizeof(double)) : 0;
         s->off_om = g_bytes; s->off_ctrl = g_bytes + om_bytes;
         s->arena_bytes = s->off_ctrl + up(sizeof(PushCtrl));
-        HIPCKD(hipMalloc(&s->arena, s->arena_bytes));
+        unsigned char* arena = nullptr;
+        CKD(s->mem.alloc(&arena, s->arena_bytes));
+        s->arena = arena;
         HIPCKD(hipMemsetAsync(s->arena, 0, s->arena_bytes, s->stream));
         s->G = reinterpret_cast<double*>(s->arena);
         if (want_om) s->om = reinterpret_cast<double*>(reinterpret_cast<char*>(s->arena) + s->off_om);
@@ -1388,44 +1354,43 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         {   // The flags are polled INSIDE a kernel while other agents write them: the memory model promises coherence across agents for
             // fine-grained memory only (coarse-grained: at kernel boundaries).  So the control block gets a fine-grained allocation of its own
             // when the runtime gives one that can be exported; else it stays in the arena (ranks sharing one GPU do not need more).
-            void* fg = nullptr;
+            DevTemp<unsigned char> fg(MEM_FINEGRAINED);
             hipIpcMemHandle_t probe;
-            if (!test_path("ctrlarena") && hipExtMallocWithFlags(&fg, up(sizeof(PushCtrl)), hipDeviceMallocFinegrained) == hipSuccess && fg &&
-                hipMemset(fg, 0, up(sizeof(PushCtrl))) == hipSuccess && hipIpcGetMemHandle(&probe, fg) == hipSuccess) {
-                s->ctrl = reinterpret_cast<PushCtrl*>(fg);
+            if (!test_path("ctrlarena") && fg.get(up(sizeof(PushCtrl))) == hipSuccess && fg.p &&
+                hipMemset(fg.p, 0, up(sizeof(PushCtrl))) == hipSuccess && hipIpcGetMemHandle(&probe, fg.p) == hipSuccess) {
+                s->ctrl = reinterpret_cast<PushCtrl*>(s->mem.keep(fg));
                 s->ctrl_fine = true;
             } else {
                 (void)hipGetLastError();
-                if (fg) (void)hipFree(fg);
             }
         }
-        CKD(dev_alloc(&s->tab_peerG, (size_t)MAX_PEERS));
-        CKD(dev_alloc(&s->tab_all, (size_t)3 * MAX_SEG));
+        CKD(s->mem.alloc(&s->tab_peerG, (size_t)MAX_PEERS));
+        CKD(s->mem.alloc(&s->tab_all, (size_t)3 * MAX_SEG));
         HIPCKD(hipMemsetAsync(s->tab_peerG, 0, MAX_PEERS * sizeof(unsigned long long), s->stream));
         HIPCKD(hipMemsetAsync(s->tab_all, 0, 3 * MAX_SEG * sizeof(unsigned long long), s->stream));
     } else {
-        CKD(dev_alloc_state(&s->G, (size_t)s->world * s->L.blk, s->coherent));
+        CKD(s->mem.alloc(&s->G, (size_t)s->world * s->L.blk, state_mem(s->coherent)));
         HIPCKD(hipMemsetAsync(s->G, 0, (size_t)s->world * s->L.blk * sizeof(double), s->stream));
     }
     s->L.G = s->G;
-    CKD(dev_alloc_state(&s->ll, s->n_local, s->coherent));
-    CKD(dev_alloc_state(&s->w_mean, 2 * row_d, s->coherent));      // one record per chain: [mean (ld) | m2 (ld)]
+    CKD(s->mem.alloc(&s->ll, s->n_local, state_mem(s->coherent)));
+    CKD(s->mem.alloc(&s->w_mean, 2 * row_d, state_mem(s->coherent)));      // one record per chain: [mean (ld) | m2 (ld)]
     s->w_m2 = s->w_mean + s->ld;
-    CKD(dev_alloc(&s->tparams, (size_t)np + 2));       // (+2: the wide-row kernels read the Gaussian's 1/sigma as pairs)
+    CKD(s->mem.alloc(&s->tparams, (size_t)np + 2));       // (+2: the wide-row kernels read the Gaussian's 1/sigma as pairs)
     HIPCKD(hipMemsetAsync(s->tparams, 0, ((size_t)np + 2) * sizeof(double), s->stream));
     if (np > 0) HIPCKD(hipMemcpyAsync(s->tparams, s->tparams_h.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    CKD(dev_alloc_state(&s->cr_state_base, 6 * MAX_CR, s->coherent));
+    CKD(s->mem.alloc(&s->cr_state_base, 6 * MAX_CR, state_mem(s->coherent)));
     s->cr_state = s->cr_state_base; s->cr_state_alt = s->cr_state_base + 3 * MAX_CR;
     if (cfg->algo == BPM_ALGO_DREAM) {       // the partial sums of the CR reduction (kernels.h)
         const uint32_t n_first = (s->N + 1u) / 2u;
         s->cr_g1 = (uint32_t)cr_g1(s->shape.lpc);
         s->cr_n1 = cr_chunks_of(n_first, s->cr_g1) + cr_chunks_of(s->N - n_first, s->cr_g1);
         const size_t n2 = ((size_t)s->cr_n1 + WAVE - 1) / WAVE;
-        CKD(dev_alloc_state(&s->cr_p1, (size_t)4 * MAX_CR * s->cr_n1, s->coherent));
+        CKD(s->mem.alloc(&s->cr_p1, (size_t)4 * MAX_CR * s->cr_n1, state_mem(s->coherent)));
         HIPCKD(hipMemsetAsync(s->cr_p1, 0, (size_t)4 * MAX_CR * s->cr_n1 * sizeof(double), s->stream));
         s->cr_p1_cur = s->cr_p1;
         if (s->cr_n1 > CR_FINAL_MAX)
-            for (auto& b : s->cr_p2) { CKD(dev_alloc_state(&b, (size_t)2 * MAX_CR * n2, s->coherent)); HIPCKD(hipMemsetAsync(b, 0, (size_t)2 * MAX_CR * n2 * sizeof(double), s->stream)); }
+            for (auto& b : s->cr_p2) { CKD(s->mem.alloc(&b, (size_t)2 * MAX_CR * n2, state_mem(s->coherent))); HIPCKD(hipMemsetAsync(b, 0, (size_t)2 * MAX_CR * n2 * sizeof(double), s->stream)); }
     }
     {
         double init[3 * MAX_CR] = {0};
@@ -1443,24 +1408,24 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
     // (a host-callback sampler: used only while the update kernel compiled around its HIP-source likelihood drives it -- prepare_generation asks Dispatch::user_cur;
     // the proposal / commit kernels of the host transports append by chain)
     s->hist_by_pos = s->world == 1 && s->shape.idx < 3 && cfg->keep_history != 0 && cfg->algo != BPM_ALGO_DEMC_SYNC && !test_path("histchain");
-    if (s->hist_by_pos) CKD(dev_alloc(&s->hist_tmp, (size_t)s->n_local * (s->ld + 1)));
+    if (s->hist_by_pos) CKD(s->mem.alloc(&s->hist_tmp, (size_t)s->n_local * (s->ld + 1)));
     if (s->cfg.running_moments) {
         s->gs_nb = (uint32_t)std::max<uint32_t>(1u, std::min<uint32_t>(256u, (s->n_local + 63u) / 64u));
-        CKD(dev_alloc(&s->gs_shift, (size_t)s->ld));
-        CKD(dev_alloc(&s->gs_part, (size_t)s->gs_nb * 2 * s->ld));
+        CKD(s->mem.alloc(&s->gs_shift, (size_t)s->ld));
+        CKD(s->mem.alloc(&s->gs_part, (size_t)s->gs_nb * 2 * s->ld));
     }
-    CKD(dev_alloc(&s->counters, 8));      // [2] NaN ratios of this run; [4] outlier resets since creation
-    CKD(dev_alloc_state(&s->acc_count, (size_t)s->n_local + ACC_SHARDS, s->coherent));      // per-chain counters | per-wavefront shards (kernels.h: lean_scalars)
+    CKD(s->mem.alloc(&s->counters, 8));      // [2] NaN ratios of this run; [4] outlier resets since creation
+    CKD(s->mem.alloc(&s->acc_count, (size_t)s->n_local + ACC_SHARDS, state_mem(s->coherent)));      // per-chain counters | per-wavefront shards (kernels.h: lean_scalars)
     HIPCKD(hipMemsetAsync(s->acc_count, 0, ((size_t)s->n_local + ACC_SHARDS) * sizeof(uint32_t), s->stream));
     HIPCKD(hipMemsetAsync(s->counters, 0, 8 * sizeof(unsigned long long), s->stream));
     if (want_om) {
-        if (!s->om) CKD(dev_alloc(&s->om, (size_t)s->world * 2 * s->n_local));
-        CKD(dev_alloc(&s->sel, 8));
+        if (!s->om) CKD(s->mem.alloc(&s->om, (size_t)s->world * 2 * s->n_local));
+        CKD(s->mem.alloc(&s->sel, 8));
         // (behind the state: one (value, index) pair per workgroup of a pass for the first maximum)
         const size_t sel_bytes = sizeof(SelState) + (size_t)sel_blocks(s->N) * (sizeof(double) + sizeof(uint32_t));
-        CKD(dev_alloc(&s->sel_state, sel_bytes));
+        CKD(s->mem.alloc(&s->sel_state, sel_bytes));
         HIPCKD(hipMemsetAsync(s->sel_state, 0, sel_bytes, s->stream));
-        CKD(dev_alloc(&s->olist, (size_t)s->n_local + 1));
+        CKD(s->mem.alloc(&s->olist, (size_t)s->n_local + 1));
     }
     // update records drawn ahead (plan_kernel) for the fused device kernels, while a launch is latency bound.  Measured
     // on cfg2's target (one wavefront per chain): 11.4 vs 11.8 us/generation at N=2048, 15.9 vs 16.4 at 8192, 24.9 vs
@@ -1479,19 +1444,19 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         s->sorted_on = s->world > 1 && s->world <= (uint32_t)MAX_SEG && tid != BPM_TARGET_HOST_CALLBACK;
     }
     for (auto& B : s->tb) {
-        CKD(dev_alloc(&B.perm, (size_t)s->win_K * s->N));
-        CKD(dev_alloc(&B.inv, (size_t)s->win_K * s->N));
-        if (s->plan_on) CKD(dev_alloc(&B.plan, (size_t)s->win_K * s->N * PLAN_WORDS));
+        CKD(s->mem.alloc(&B.perm, (size_t)s->win_K * s->N));
+        CKD(s->mem.alloc(&B.inv, (size_t)s->win_K * s->N));
+        if (s->plan_on) CKD(s->mem.alloc(&B.plan, (size_t)s->win_K * s->N * PLAN_WORDS));
         if (s->sorted_on) {
-            CKD(dev_alloc(&B.sidx, (size_t)s->win_K * s->N));
+            CKD(s->mem.alloc(&B.sidx, (size_t)s->win_K * s->N));
             HIPCKD(hipMemsetAsync(B.sidx, 0xFF, (size_t)s->win_K * s->N * sizeof(uint32_t), s->stream));      // "no slot": plan_kernel skips such positions
-            CKD(dev_alloc(&B.plan_count, (size_t)s->win_K * 2 * s->world));
-            HIPCKD(hipHostMalloc(reinterpret_cast<void**>(&B.count_h), (size_t)s->win_K * 2 * s->world * sizeof(uint32_t), hipHostMallocDefault));
+            CKD(s->mem.alloc(&B.plan_count, (size_t)s->win_K * 2 * s->world));
+            CKD(s->mem.alloc(&B.count_h, (size_t)s->win_K * 2 * s->world, MEM_PINNED));
         }
     }
     if (s->plan_on) s->plan_tab = s->tb[0].plan;       // (non-null from here on: "this sampler launches with records")
-    CKD(dev_alloc(&s->gamma_tab, (size_t)s->dim + 1));
-    if (cfg->algo == BPM_ALGO_DEMC_SYNC) CKD(dev_alloc(&s->x_next, row_d));
+    CKD(s->mem.alloc(&s->gamma_tab, (size_t)s->dim + 1));
+    if (cfg->algo == BPM_ALGO_DEMC_SYNC) CKD(s->mem.alloc(&s->x_next, row_d));
     {
         std::vector<double> gt(s->dim + 1, 0.0);      // dream.py:61, same operation order as the reference
         for (uint32_t dp = 1; dp <= s->dim; ++dp)
@@ -1500,14 +1465,14 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         HIPCKD(hipStreamSynchronize(s->stream));
     }
     s->scratch_doubles = 4 * (size_t)s->ld + 64;
-    CKD(dev_alloc(&s->scratch, s->scratch_doubles));
+    CKD(s->mem.alloc(&s->scratch, s->scratch_doubles));
     if (tid == BPM_TARGET_HOST_CALLBACK) {
-        CKD(dev_alloc(&s->prop_buf, row_d));
-        CKD(dev_alloc(&s->aux_buf, 2 * (size_t)s->n_local));
-        CKD(dev_alloc(&s->ids_buf, s->n_local));
-        HIPCKD(hipHostMalloc(reinterpret_cast<void**>(&s->h_ids), s->n_local * sizeof(int32_t), hipHostMallocDefault));
-        HIPCKD(hipHostMalloc(reinterpret_cast<void**>(&s->h_props), row_d * sizeof(double), hipHostMallocDefault));
-        HIPCKD(hipHostMalloc(reinterpret_cast<void**>(&s->h_ll), (size_t)s->n_local * sizeof(double), hipHostMallocDefault));
+        CKD(s->mem.alloc(&s->prop_buf, row_d));
+        CKD(s->mem.alloc(&s->aux_buf, 2 * (size_t)s->n_local));
+        CKD(s->mem.alloc(&s->ids_buf, s->n_local));
+        CKD(s->mem.alloc(&s->h_ids, s->n_local, MEM_PINNED));
+        CKD(s->mem.alloc(&s->h_props, row_d, MEM_PINNED));
+        CKD(s->mem.alloc(&s->h_ll, s->n_local, MEM_PINNED));
     }
     if (s->world > 1 && !cfg->nccl_uid) { bpm_destroy(s); return fail("bpm_create: nccl_uid required when world_size > 1"); }
     // Test mode: a uid starting with "BPMLOCAL" makes the ranks of a world handles of ONE process on one GPU;
@@ -1546,7 +1511,7 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         const bool want_rows = xe && std::strcmp(xe, "rows") == 0;
         s->replay_enabled = !want_dense && !want_rows && s->shape.idx != SHAPE_WIDE;      // (wide rows: dense, or push once connected)
         s->sparse_enabled = !want_dense && want_rows && s->shape.idx != SHAPE_WIDE;
-        CKD(dev_alloc(&s->accbits_all, (size_t)s->N));
+        CKD(s->mem.alloc(&s->accbits_all, (size_t)s->N));
         HIPCKD(hipMemsetAsync(s->accbits_all, 0, (size_t)s->N, s->stream));
         s->xnsub = 1u;
         // 4 sub-blocks: ~175 acceptances per counter and half generation at cfg2 cost the same on one GPU as 16
@@ -1557,14 +1522,14 @@ extern "C" int bpm_create(const bpm_config_t* cfg, bpm_handle_t* out) {
         s->xcap_max = ((s->n_local + s->xnsub - 1u) / s->xnsub + 1u) & ~1u;    // every chain of a sub-block accepted
         s->xcap = s->xcap_max;                               // first chunk: cannot overflow; then sized from the counts seen
         const size_t pk_doubles = (size_t)s->world * s->xnsub * s->xstride();
-        CKD(dev_alloc(&s->PK, pk_doubles));
+        CKD(s->mem.alloc(&s->PK, pk_doubles));
         HIPCKD(hipMemsetAsync(s->PK, 0, pk_doubles * sizeof(double), s->stream));
-        CKD(dev_alloc(&s->xstat, 2));
+        CKD(s->mem.alloc(&s->xstat, 2));
         HIPCKD(hipMemsetAsync(s->xstat, 0, 2 * sizeof(uint32_t), s->stream));
-        CKD(dev_alloc(&s->ckpt_G, (size_t)s->world * s->L.blk));
-        CKD(dev_alloc(&s->ckpt_ll, s->n_local));
-        CKD(dev_alloc(&s->ckpt_acc, (size_t)s->n_local + ACC_SHARDS));
-        CKD(dev_alloc(&s->ckpt_counters, 4));
+        CKD(s->mem.alloc(&s->ckpt_G, (size_t)s->world * s->L.blk));
+        CKD(s->mem.alloc(&s->ckpt_ll, s->n_local));
+        CKD(s->mem.alloc(&s->ckpt_acc, (size_t)s->n_local + ACC_SHARDS));
+        CKD(s->mem.alloc(&s->ckpt_counters, 4));
     }
     HIPCKD(hipStreamSynchronize(s->stream));
     *out = s;
@@ -1728,7 +1693,7 @@ static int build_window(bpm_sampler* s, int b, int64_t W, int shuffle) {
         if (B.sidx) {              // world > 1: every position's slot in the owner-sorted order, every rank's counts (they size the launches)
             if (own_only) {        // this rank's positions only: the other ranks' counts stay zero, its own run starts at the half's offset
                 const uint32_t n_chunks = ((s->N + 1u) / 2u + SLOT_CHUNK - 1u) / SLOT_CHUNK;
-                if (!B.chunk_count) CK(dev_alloc(&B.chunk_count, (size_t)s->win_K * 2 * n_chunks));
+                if (!B.chunk_count) CK(regrow(s, &B.chunk_count, (size_t)s->win_K * 2 * n_chunks, 0, false));
                 HIPCK(hipMemsetAsync(B.plan_count, 0, (size_t)K * 2 * s->world * sizeof(uint32_t), bs));
                 for (uint32_t assign = 0; assign < 2; ++assign)
                     hipLaunchKernelGGL(plan_slot_own_kernel, dim3(n_chunks, 2, (unsigned)K), dim3(SLOT_CHUNK), 0, bs, B.perm, s->N, s->lo, s->n_local, s->world,
@@ -2121,10 +2086,9 @@ static int outlier_row_keys(bpm_sampler* s) {
     const size_t rows = (size_t)s->hist_rows;
     HIPCK(hipStreamSynchronize(s->stream));      // (the previous check's kernels and copy are done with okeys / okeys_host)
     if (rows > s->okeys_cap) {
-        if (s->okeys) HIPCK(hipFree(s->okeys));
-        s->okeys = nullptr;
-        s->okeys_cap = std::max<size_t>(rows + rows / 2, 256);
-        HIPCK(hipMalloc(&s->okeys, 2 * s->okeys_cap * sizeof(PermKey)));
+        const size_t cap = std::max<size_t>(rows + rows / 2, 256);
+        CK(regrow(s, &s->okeys, 2 * cap, 0, false));
+        s->okeys_cap = cap;
     }
     PermKey id{};
     id.n = s->N; id.nbits = perm_nbits(s->N); id.on = 0u;
@@ -2778,9 +2742,8 @@ extern "C" int bpm_push_selftest(bpm_handle_t* handles, int32_t R, int32_t* ok) 
             if (p != s->rank && c.probe[p] != seed + p) ctrl_ok = false;
     }
     // ---- part 2: the arenas, on the path the update kernels take
-    std::vector<double*> save((size_t)R, nullptr);
-    struct FreeSave { std::vector<double*>& v; ~FreeSave() { for (double* p : v) if (p) (void)hipFree(p); } } free_save{save};
-    for (int r = 0; r < R; ++r) CK(dev_alloc(&save[(size_t)r], (size_t)handles[r]->world * (2 * handles[r]->ld + 8)));
+    std::vector<DevTemp<double>> save((size_t)R);
+    for (int r = 0; r < R; ++r) CK(save[(size_t)r].alloc((size_t)handles[r]->world * (2 * handles[r]->ld + 8)));
     bool group_direct = false;
     const bool direct = group_goes_direct(g, true, group_direct);
     for (int r = 0; r < R; ++r) {
@@ -2803,7 +2766,7 @@ extern "C" int bpm_push_selftest(bpm_handle_t* handles, int32_t R, int32_t* ok) 
                 rc = push_barrier(g);
                 for (int r = 0; r < R && rc == 0; ++r) {
                     bind_rank_queue(handles[r]);
-                    rc = launch_arena_probe(handles[r], mode, form, seed + 16u * (unsigned)form, save[(size_t)r], mode == 1 ? f_write : f_read);
+                    rc = launch_arena_probe(handles[r], mode, form, seed + 16u * (unsigned)form, save[(size_t)r].p, mode == 1 ? f_write : f_read);
                     if (d.dq) d.dq->flush();
                 }
             }
@@ -2970,6 +2933,19 @@ extern "C" int bpm_step_profiled(bpm_handle_t s, int64_t n_gens, double* kernel_
 }
 #endif   // BPM_TEST_HOOKS
 
+// How bpm_set_history leaves a handle, and whatever else fills a history from outside (bpm_derive_history, bpm_rank_history): `rows` rows in chain
+// order, the state = the last row with its ln-likes current, no proposals open, a new epoch for whoever remembered the old history
+static void history_installed(bpm_sampler* s, int64_t rows) {
+    for (int64_t r = 0; r < rows && r < (int64_t)s->hist_tag.size(); ++r) s->hist_tag[(size_t)r] = -1;
+    s->hist_rows = rows;
+    s->rows_logical = rows;
+    s->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
+    s->ll_stale = false;
+    s->state_set = true;
+    s->phase = 0;
+    s->hist_epoch += 1;
+}
+
 // Warm start (demc.py:46-51,217-233): install `rows` history rows of this rank's chains
 // (hist_local: rows x n_local x dim) and the full current state X (N x dim, = last row of every chain).
 extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_local, const double* X) {
@@ -2977,8 +2953,7 @@ extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_
     CK(set_device(s));
     if (rows < 1 || !hist_local || !X) return fail("bpm_set_history: bad argument");
     if (!s->cfg.keep_history && rows > 1) return fail("bpm_set_history: sampler keeps no history");
-    CK(bpm_set_state(s, X));
-    s->hist_epoch += 1;
+    CK(bpm_set_state(s, X));      // (reset_history: a new hist_epoch, the one row)
     if (rows > 1) {
         CK(ensure_history(s, rows));
         HIPCK(hipMemsetAsync(s->hist, 0, (size_t)rows * s->n_local * s->ld * sizeof(double), s->stream));
@@ -3000,10 +2975,7 @@ extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_
             HIPCK(hipMemcpyAsync(s->llhist, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
             HIPCK(hipStreamSynchronize(s->stream));
         }
-        s->hist_rows = rows;
-        s->rows_logical = rows;
-        for (int64_t r = 0; r < rows && r < (int64_t)s->hist_tag.size(); ++r) s->hist_tag[(size_t)r] = -1;
-        s->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
+        history_installed(s, rows);
         if (s->cfg.running_moments) {      // population sums of every installed row
             CK(ensure_gen_sums(s, rows));
             for (int64_t g = 0; g < rows; ++g) CK(push_gen_sums(s, g, s->hist + (uint64_t)g * s->n_local * s->ld));
@@ -3088,10 +3060,12 @@ extern "C" int bpm_diag_split_moments(bpm_handle_t s, int64_t g_lo, int64_t g_hi
     if (n >= (int64_t)1 << 31) return fail("bpm_diag_split_moments: window too long");
     CK(normalize_history(s, g_lo, g_hi));
     const uint64_t row_d = (uint64_t)s->n_local * s->ld;
-    if (!s->dg_mean) {
-        CK(dev_alloc(&s->dg_mean, 2 * (size_t)row_d));
-        CK(dev_alloc(&s->dg_m2, 2 * (size_t)row_d));
-        CK(dev_alloc(&s->dg_out, (size_t)std::max(3, DIAG_T) * s->ld));
+    if (!s->dg_mean) {      // (all three or none)
+        DevTemp<double> mean, m2, out;
+        CK(mean.alloc(2 * (size_t)row_d));
+        CK(m2.alloc(2 * (size_t)row_d));
+        CK(out.alloc((size_t)std::max(3, DIAG_T) * s->ld));
+        s->dg_mean = s->mem.keep(mean); s->dg_m2 = s->mem.keep(m2); s->dg_out = s->mem.keep(out);
     }
     const uint64_t n_pairs = row_d / 2u;
     hipLaunchKernelGGL(diag_split_moments_kernel, dim3((unsigned)((n_pairs + DIAG_THREADS - 1) / DIAG_THREADS), 2), dim3(DIAG_THREADS), 0, s->stream,
@@ -4010,6 +3984,34 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
     return 0;
 }
 
+// ---- a second handle as the destination of a history built from the first (bpm_derive_history, bpm_rank_history) -------------------------
+// The pair itself: two live handles, drained, on one device (made current).  `dim_hint`: what the refusal of src == dst recommends.
+static int second_handle_pair(const std::string& who, bpm_handle_t src, bpm_handle_t dst, const char* dim_hint) {
+    if (!src || !dst) return fail(who + ": null handle");
+    if (src == dst) return fail(who + ": the destination is the source itself (create a second handle with " + dim_hint + ")");
+    CK(check_handle(src));
+    CK(check_handle(dst));
+    if (src->cfg.device != dst->cfg.device)
+        return fail(who + ": source and destination are on different devices (" + std::to_string(src->cfg.device) + " and " +
+                    std::to_string(dst->cfg.device) + ")");
+    CK(set_device(src));
+    return 0;
+}
+static int second_handle_single_rank(const std::string& who, const bpm_sampler* src, const bpm_sampler* dst) {
+    if (src->world != 1 || dst->world != 1)
+        return fail(who + ": single rank only (world_size " + std::to_string(src->world) + " and " + std::to_string(dst->world) + ")");
+    return 0;
+}
+// The destination can take it: a history-keeping host-callback handle of `dim` coordinates (`dim_of`: whose dim that is) and src's chains, nothing open.
+static int second_handle_fits(const std::string& who, const bpm_sampler* src, const bpm_sampler* dst, uint32_t dim, const char* dim_of) {
+    if (!dst->cfg.keep_history) return fail(who + ": the destination needs keep_history=True");
+    if (dst->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(who + ": the destination must have the host-callback target");
+    if (dst->dim != dim) return fail(who + ": the destination has dim " + std::to_string(dst->dim) + "; " + dim_of + " " + std::to_string(dim));
+    if (dst->N != src->N) return fail(who + ": the destination has n_chains " + std::to_string(dst->N) + "; the source has " + std::to_string(src->N));
+    if (dst->proposed) return fail(who + ": the destination has proposals that are not committed");
+    return 0;
+}
+
 // A DERIVED HISTORY IS A HISTORY: the installed function of `src` over every resident row of src, written into the history buffer of `dst`, a
 // second, ordinary handle with dim = n_out -- whose bpm_reduce_moments ... bpm_trace_chains (and bpm_derive) then serve the derived quantities
 // with their own scratch, sized by their own ld, and their own state for bpm_reduce_moments' shift.  dst comes out as bpm_set_history leaves a
@@ -4017,41 +4019,21 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
 // is written (its history is put into chain order, as bpm_get_history does).
 extern "C" int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst) {
     const char* who = "bpm_derive_history";
-    if (!src || !dst) return fail(std::string(who) + ": null handle");
-    if (src == dst) return fail(std::string(who) + ": the destination is the source itself (create a second handle with dim = n_out)");
-    CK(check_handle(src));
-    CK(check_handle(dst));
-    if (src->cfg.device != dst->cfg.device)
-        return fail(std::string(who) + ": source and destination are on different devices (" + std::to_string(src->cfg.device) + " and " +
-                    std::to_string(dst->cfg.device) + ")");
-    CK(set_device(src));
+    CK(second_handle_pair(who, src, dst, "dim = n_out"));
     if (!src->derived.fill) return fail(std::string(who) + ": no device function installed on the source (bpm_set_device_function)");
     CK(require_resident_history(src, who));
-    if (src->world != 1 || dst->world != 1)
-        return fail(std::string(who) + ": single rank only (world_size " + std::to_string(src->world) + " and " + std::to_string(dst->world) + ")");
+    CK(second_handle_single_rank(who, src, dst));
     const uint32_t n_out = (uint32_t)src->derived.n_out;
-    if (!dst->cfg.keep_history) return fail(std::string(who) + ": the destination needs keep_history=True");
-    if (dst->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(std::string(who) + ": the destination must have the host-callback target");
-    if (dst->dim != n_out)
-        return fail(std::string(who) + ": the destination has dim " + std::to_string(dst->dim) + "; the installed function has n_out " + std::to_string(n_out));
-    if (dst->N != src->N)
-        return fail(std::string(who) + ": the destination has n_chains " + std::to_string(dst->N) + "; the source has " + std::to_string(src->N));
-    if (dst->proposed) return fail(std::string(who) + ": the destination has proposals that are not committed");
+    CK(second_handle_fits(who, src, dst, n_out, "the installed function has n_out"));
     const int64_t rows = src->hist_rows;
     const uint64_t n = (uint64_t)rows * src->n_local;      // local rows of both
     uint32_t R = 0, ldp = 0, ldo = 0, lds = 0;
     uint64_t parts = 1;
     CK(derive_launch_shape(src, n, who, R, ldp, ldo, lds, &parts));
-    if (rows > dst->hist_cap) {      // what ensure_history is about to allocate
-        const uint64_t cap = (uint64_t)std::max<int64_t>(rows, dst->hist_cap + dst->hist_cap / 2);
-        const uint64_t need = cap * dst->n_local * ((uint64_t)dst->ld + 1u) * sizeof(double);
-        size_t mem_free = 0, mem_total = 0;
-        HIPCK(hipMemGetInfo(&mem_free, &mem_total));
-        if (need > mem_free)
-            return fail(std::string(who) + ": the derived history of " + std::to_string((long long)cap) + " generations x " + std::to_string(dst->n_local) +
-                        " chains x (" + std::to_string(dst->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(need >> 20)) +
-                        " MiB of device memory; " + std::to_string(mem_free >> 20) + " MiB are free");
-    }
+    size_t mem_free = 0, mem_total = 0;
+    uint64_t need = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    CK(history_growth_bytes(dst, rows, who, "derived", mem_free, &need));
     CK(normalize_history(src, 0, src->hist_rows));
     CK(ensure_history(dst, rows));
     HIPCK(ModuleLaunch<bpm::DeriveFillKernel>::on(src->stream, src->derived.fill, (unsigned)parts, DERIVE_THREADS, lds, src->hist, src->llhist, src->ld,
@@ -4062,14 +4044,7 @@ extern "C" int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst) {
     // the state and the ln-like cache bpm_set_history + bpm_set_loglike leave behind: the last row (bpm_reduce_moments' shift: a value of the data)
     HIPCK(hipMemcpyAsync(dst->G, dst->hist + (size_t)(rows - 1) * row_d, row_d * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     HIPCK(hipMemcpyAsync(dst->ll, ll_last, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
-    for (int64_t r = 0; r < rows && r < (int64_t)dst->hist_tag.size(); ++r) dst->hist_tag[(size_t)r] = -1;
-    dst->hist_rows = rows;
-    dst->rows_logical = rows;
-    dst->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
-    dst->ll_stale = false;
-    dst->state_set = true;
-    dst->phase = 0;
-    dst->hist_epoch += 1;
+    history_installed(dst, rows);
     HIPCK(hipStreamSynchronize(src->stream));
     return 0;
 }
@@ -4096,32 +4071,20 @@ static hipError_t rank_sort(void* tmp, size_t* tmp_bytes, unsigned long long* in
 extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
                                 const int64_t* pos, double* order_stats) {
     const std::string who = "bpm_rank_history";
-    if (!src || !dst) return fail(who + ": null handle");
-    if (src == dst) return fail(who + ": the destination is the source itself (create a second handle with the same dim)");
-    CK(check_handle(src));
-    CK(check_handle(dst));
-    if (src->cfg.device != dst->cfg.device)
-        return fail(who + ": source and destination are on different devices (" + std::to_string(src->cfg.device) + " and " +
-                    std::to_string(dst->cfg.device) + ")");
-    CK(set_device(src));
+    CK(second_handle_pair(who, src, dst, "the same dim"));
     if (kind < RK_RANK || kind > RK_RANK_FOLDED) return fail(who + ": kind must be 0 (rank), 1 (z), 2 (folded z), 3 (indicator) or 4 (folded rank); got " + std::to_string(kind));
     const bool sorted = kind != RK_INDICATOR;
     if ((rk_folded(kind) || kind == RK_INDICATOR) && !arg) return fail(who + ": kind " + std::to_string(kind) + " needs arg (one value per coordinate)");
     if (n_pos < 0 || (n_pos > 0 && (!pos || !order_stats))) return fail(who + ": bad order-statistics arguments");
     if (!sorted && n_pos != 0) return fail(who + ": the indicator sorts nothing and has no order statistics (n_pos must be 0)");
     CK(require_resident_history(src, who.c_str()));
-    if (src->world != 1 || dst->world != 1)
-        return fail(who + ": single rank only (world_size " + std::to_string(src->world) + " and " + std::to_string(dst->world) + ")");
+    CK(second_handle_single_rank(who, src, dst));
     if (g_lo < 0 || g_hi < g_lo || g_hi > src->hist_rows) return fail(who + ": generation range out of bounds");
     const int64_t n = (g_hi - g_lo) / 2;
     if (n < 4)
         return fail(who + ": a window of " + std::to_string((long long)(g_hi - g_lo)) + " history rows gives half-chains of " + std::to_string((long long)n) +
                     " draws; at least 4 are needed");
-    if (!dst->cfg.keep_history) return fail(who + ": the destination needs keep_history=True");
-    if (dst->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(who + ": the destination must have the host-callback target");
-    if (dst->dim != src->dim) return fail(who + ": the destination has dim " + std::to_string(dst->dim) + "; the source has " + std::to_string(src->dim));
-    if (dst->N != src->N) return fail(who + ": the destination has n_chains " + std::to_string(dst->N) + "; the source has " + std::to_string(src->N));
-    if (dst->proposed) return fail(who + ": the destination has proposals that are not committed");
+    CK(second_handle_fits(who, src, dst, src->dim, "the source has"));
     const uint64_t S64 = 2ull * (uint64_t)n * src->n_local;
     if (S64 >= (1ull << 31))
         return fail(who + ": the window holds " + std::to_string((unsigned long long)S64) + " values per coordinate; fewer than 2^31 can be ranked");
@@ -4132,15 +4095,9 @@ extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo
     size_t mem_free = 0, mem_total = 0;
     HIPCK(hipMemGetInfo(&mem_free, &mem_total));
     const int64_t rows = 2 * n;
-    if (rows > dst->hist_cap) {      // what ensure_history is about to allocate
-        const uint64_t cap = (uint64_t)std::max<int64_t>(rows, dst->hist_cap + dst->hist_cap / 2);
-        const uint64_t need = cap * dst->n_local * ((uint64_t)dst->ld + 1u) * sizeof(double);
-        if (need > mem_free)
-            return fail(who + ": the ranked history of " + std::to_string((long long)cap) + " generations x " + std::to_string(dst->n_local) + " chains x (" +
-                        std::to_string(dst->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(need >> 20)) + " MiB of device memory; " +
-                        std::to_string(mem_free >> 20) + " MiB are free");
-        mem_free -= (size_t)need;
-    }
+    uint64_t hist_need = 0;
+    CK(history_growth_bytes(dst, rows, who, "ranked", mem_free, &hist_need));
+    mem_free -= (size_t)hist_need;      // (the scratch budget below is what ensure_history will leave)
     // the batch: as many columns as the scratch budget holds (keys in | keys out | the sort's temporaries), batch * S < 2^31.
     // The sort gives a column of this length to ONE workgroup, so the columns of a batch are its whole parallelism: at cfg2's shape with 1000
     // generations a z fill takes 24.7 / 6.8 / 2.1 / 1.0 s with batches of 1 / 4 / 16 / 64 columns (profiles/rank_diagnostics_cfg2.txt).  Hence
@@ -4234,14 +4191,7 @@ extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo
     HIPCK(hipMemcpyAsync(dst->llhist + half, src->llhist + (size_t)(g_hi - n) * src->n_local, half * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     HIPCK(hipMemcpyAsync(dst->G, dst->hist + (size_t)(rows - 1) * row_d, row_d * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     HIPCK(hipMemcpyAsync(dst->ll, src->llhist + (size_t)(g_hi - 1) * src->n_local, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
-    for (int64_t r = 0; r < rows && r < (int64_t)dst->hist_tag.size(); ++r) dst->hist_tag[(size_t)r] = -1;
-    dst->hist_rows = rows;
-    dst->rows_logical = rows;
-    dst->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
-    dst->ll_stale = false;
-    dst->state_set = true;
-    dst->phase = 0;
-    dst->hist_epoch += 1;
+    history_installed(dst, rows);
     HIPCK(hipStreamSynchronize(src->stream));
     return 0;
 }
@@ -4396,11 +4346,11 @@ static int d2h_rows_parallel(bpm_sampler* s, double* out, const double* src, siz
     const int device = s->cfg.device;
     auto work = [&]() {
         hipStream_t st = nullptr;
-        double* pin[2] = {nullptr, nullptr};
+        DevTemp<double> pinned[2] = {DevTemp<double>(MEM_PINNED), DevTemp<double>(MEM_PINNED)};
         auto ok = [&](hipError_t e) { if (e != hipSuccess) { err.store((int)e); return false; } return true; };
         if (ok(hipSetDevice(device)) && ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) &&
-            ok(hipHostMalloc((void**)&pin[0], chunk_rows * row_bytes, hipHostMallocDefault)) &&
-            ok(hipHostMalloc((void**)&pin[1], chunk_rows * row_bytes, hipHostMallocDefault))) {
+            ok(pinned[0].get(chunk_rows * dim)) && ok(pinned[1].get(chunk_rows * dim))) {
+            double* const pin[2] = {pinned[0].p, pinned[1].p};
             auto issue = [&](size_t ch, int b) {
                 const size_t r0 = ch * chunk_rows, nr = std::min(chunk_rows, rows - r0);
                 return ok(hipMemcpy2DAsync(pin[b], row_bytes, src + r0 * ld, (size_t)ld * sizeof(double), row_bytes, nr,
@@ -4422,8 +4372,6 @@ static int d2h_rows_parallel(bpm_sampler* s, double* out, const double* src, siz
             }
             if (st) (void)hipStreamSynchronize(st);
         }
-        if (pin[0]) (void)hipHostFree(pin[0]);
-        if (pin[1]) (void)hipHostFree(pin[1]);
         if (st) (void)hipStreamDestroy(st);
     };
     std::vector<std::thread> th;
@@ -4517,10 +4465,11 @@ extern "C" int bpm_eval_loglike(bpm_handle_t s, const double* X, int32_t n, doub
     CK(set_device(s));
     if (n <= 0) return 0;
     if (!X || !out) return fail("bpm_eval_loglike: null argument");
-    double* dX = nullptr;
-    double* dO = nullptr;
-    CK(dev_alloc(&dX, (size_t)n * s->ld));
-    CK(dev_alloc(&dO, (size_t)n));
+    DevTemp<double> bX, bO;
+    CK(bX.alloc((size_t)n * s->ld));
+    CK(bO.alloc((size_t)n));
+    double* const dX = bX.p;
+    double* const dO = bO.p;
     HIPCK(hipMemsetAsync(dX, 0, (size_t)n * s->ld * sizeof(double), s->stream));
     HIPCK(hipMemcpy2DAsync(dX, s->ld * sizeof(double), X, s->dim * sizeof(double), s->dim * sizeof(double), n,
                            hipMemcpyHostToDevice, s->stream));
@@ -4528,13 +4477,11 @@ extern "C" int bpm_eval_loglike(bpm_handle_t s, const double* X, int32_t n, doub
         case BPM_TARGET_GAUSS_EQUICORR: g_eval_gauss[s->shape.idx](dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
         case BPM_TARGET_MIXTURE_PAIRS: g_eval_mixture[s->shape.idx](dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
         case BPM_TARGET_BANANA_2D: launch_eval<TARGET_BANANA, 1, 2>(dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
-        default: (void)hipFree(dX); (void)hipFree(dO); return fail("bpm_eval_loglike: host-callback target has no device ln_like");
+        default: return fail("bpm_eval_loglike: host-callback target has no device ln_like");
     }
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(out, dO, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
-    HIPCK(hipFree(dX));
-    HIPCK(hipFree(dO));
     return 0;
 }
 
@@ -4545,15 +4492,14 @@ extern "C" int bpm_set_trace(bpm_handle_t s, int32_t on) {
     CK(set_device(s));
     HIPCK(hipStreamSynchronize(s->stream));
     if (on && !s->trace_i32) {
-        CK(dev_alloc(&s->trace_i32, (size_t)s->n_local * TRACE_I32));
-        CK(dev_alloc(&s->trace_f64, (size_t)s->n_local * TRACE_F64));
-        CK(dev_alloc(&s->trace_mask, (size_t)s->n_local * s->dim));
+        CK(s->mem.alloc(&s->trace_i32, (size_t)s->n_local * TRACE_I32));
+        CK(s->mem.alloc(&s->trace_f64, (size_t)s->n_local * TRACE_F64));
+        CK(s->mem.alloc(&s->trace_mask, (size_t)s->n_local * s->dim));
         HIPCK(hipMemset(s->trace_i32, 0xFF, (size_t)s->n_local * TRACE_I32 * sizeof(int32_t)));
         HIPCK(hipMemset(s->trace_f64, 0, (size_t)s->n_local * TRACE_F64 * sizeof(double)));
         HIPCK(hipMemset(s->trace_mask, 0, (size_t)s->n_local * s->dim));
     } else if (!on && s->trace_i32) {
-        HIPCK(hipFree(s->trace_i32)); HIPCK(hipFree(s->trace_f64)); HIPCK(hipFree(s->trace_mask));
-        s->trace_i32 = nullptr; s->trace_f64 = nullptr; s->trace_mask = nullptr;
+        s->mem.release(&s->trace_i32); s->mem.release(&s->trace_f64); s->mem.release(&s->trace_mask);
     }
     return 0;
 }
@@ -4587,14 +4533,13 @@ extern "C" int bpm_debug_perm(bpm_handle_t s, int64_t t, int32_t shuffle, double
 extern "C" int bpm_selftest_philox(int32_t device, int32_t n, uint64_t seed, uint32_t* out_mine, uint32_t* out_rocrand) {
     if (n <= 0 || !out_mine || !out_rocrand) return fail("bpm_selftest_philox: bad argument");
     HIPCK(hipSetDevice(device));
-    uint32_t* d = nullptr;
-    HIPCK(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * 8 * sizeof(uint32_t)));
-    launch_rocrand_check(d, n, seed);
+    DevTemp<uint32_t> d;
+    CK(d.alloc((size_t)n * 8));
+    launch_rocrand_check(d.p, n, seed);
     HIPCK(hipGetLastError());
     HIPCK(hipDeviceSynchronize());
     std::vector<uint32_t> h((size_t)n * 8);
-    HIPCK(hipMemcpy(h.data(), d, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCK(hipFree(d));
+    HIPCK(hipMemcpy(h.data(), d.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) {
         std::memcpy(out_mine + 4 * (size_t)i, h.data() + 8 * (size_t)i, 16);
         std::memcpy(out_rocrand + 4 * (size_t)i, h.data() + 8 * (size_t)i + 4, 16);
@@ -4705,7 +4650,7 @@ extern "C" int bpm_debug_stamps(bpm_handle_t s, unsigned long long* out, int64_t
     CK(check_handle(s));
     CK(set_device(s));
     if (!s->stamps) {
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&s->stamps), (size_t)s->n_local * 8 * sizeof(unsigned long long)));
+        CK(s->mem.alloc(&s->stamps, (size_t)s->n_local * 8));
         HIPCK(hipMemset(s->stamps, 0, (size_t)s->n_local * 8 * sizeof(unsigned long long)));
         return 0;
     }

@@ -558,6 +558,11 @@ class HipEngine(object):
         self.set_device_function(fn.source, fn.n_out, fn.params)
         return self.derive_rows(n_burn, values)
 
+    def _second_engine(self, dim):
+        """the destination of derive_history / rank_history: a history-keeping host-callback engine of this one's chains, library and device"""
+        return HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=dim, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,
+                         device=self.device, burnin_gen=0, outlier_every=0, keep_history=True, lib=self.lib)
+
     def derive_history(self, fn):
         """-> HipEngine: a second, ordinary engine with dim = fn.n_out on the same library and device whose resident history is `fn` (a
         derived.HipFunction) of every row of this one's, with this one's log-likelihood history (bpm_derive_history) -- every statistic above
@@ -565,8 +570,7 @@ class HipEngine(object):
         if self.world_size != 1:
             raise NotImplementedError("derive_history: a derived history is built on a single rank only (world_size = %d)" % self.world_size)
         self.set_device_function(fn.source, fn.n_out, fn.params)
-        dst = HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=fn.n_out, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,
-                        device=self.device, burnin_gen=0, outlier_every=0, keep_history=True, lib=self.lib)
+        dst = self._second_engine(fn.n_out)
         try:
             self._ck(self.lib.bpm_derive_history(self._h, dst._h))
         except BaseException:
@@ -587,8 +591,7 @@ class HipEngine(object):
         out = np.empty((len(pos), self.dim), dtype=np.float64)
         own = dst is None
         if own:
-            dst = HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=self.dim, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,
-                            device=self.device, burnin_gen=0, outlier_every=0, keep_history=True, lib=self.lib)
+            dst = self._second_engine(self.dim)
         try:
             self._ck(self.lib.bpm_rank_history(self._h, dst._h, int(g_lo), int(g_hi), int(kind), None if a is None else _dptr(a), len(pos),
                                                pos.ctypes.data_as(C.POINTER(C.c_int64)) if len(pos) else None, _dptr(out) if len(pos) else None))
