@@ -134,6 +134,7 @@ TEST_SIGNATURES = {
     "bpm_debug_perm": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_double, _ip, _ip, _ip]),
     "bpm_debug_outlier_select": (C.c_int, [_H, _dp, _dp]),
     "bpm_debug_time_kernels": (C.c_int, [_H, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "bpm_debug_flavour_counts": (C.c_int, [_H, _P(C.c_int64)]),
 }
 
 _lib = None

@@ -1379,21 +1379,33 @@ __host__ inline bool stamps_allow_hot(const PhaseArgs&) { return true; }
 #else
 __host__ inline bool stamps_allow_hot(const PhaseArgs& a) { return a.stamps == nullptr; }
 #endif
-// HOT: frequent cases as their own instantiations: 1 = single GPU, steady state, with plan records, 2 = the same without,
-// 3 / 4 = the same during DREAM's CR adaptation (burn-in), 5 / 6 = a rank of a multi-GPU world in the steady state
-// with the replay exchange (accept bytes; its compacted records when 5, none when 6); 0 = the general kernel.
-__host__ inline bool phase_args_hot_sharded(const PhaseArgs& a, bool dream, bool with_plan) {
-    return a.mode == 0 && (a.rec_tab != nullptr) == with_plan && trace_i32_of(a) == nullptr && a.pack == nullptr && a.x_next == nullptr &&
-           a.adapt_on == 0 && a.epsilon > 0.0 && a.L.world > 1 &&
-           a.perm_tab != nullptr && a.inv_tab != nullptr && a.stamps == nullptr && (a.accbits != nullptr || a.n_peers > 0) && a.replay == 0 &&
-           (!dream || (a.u_epsilon > 0.0 && a.n_cr == 3));
+// HOT: frequent cases as their own instantiations of the update kernel -- the flavours, named on the host only (the kernel's template takes the number).
+// The sixth, a rank of a world WITHOUT records (HOT == 6 below), is instantiated nowhere: a rank's work items are positions (mode 0) only
+// with owner-sorted records, and then it has records.
+enum Flavour {
+    FLAVOUR_GENERAL = 0,           // the general kernel
+    FLAVOUR_STEADY_PLAN = 1,       // single GPU, steady state, with plan records
+    FLAVOUR_STEADY = 2,            // the same without
+    FLAVOUR_ADAPT_PLAN = 3,        // single GPU during DREAM's CR adaptation (burn-in), with plan records
+    FLAVOUR_ADAPT = 4,             // the same without
+    FLAVOUR_SHARD_PLAN = 5,        // a rank of a multi-GPU world in the steady state with the replay exchange (accept bytes) and its compacted records
+    N_FLAVOURS = 7                 // (counters by flavour keep the kernel's numbering, 6 included)
+};
+// The flavour an argument block is launched with, for a shape that can read plan records or cannot (can_plan: one wavefront per chain, two
+// coordinates per lane) -- the ONLY code that knows when a flavour applies: steady state, then a rank of a world, then adapting.
+__host__ inline Flavour choose_flavour(const PhaseArgs& a, bool dream, bool can_plan) {
+    const bool plan = can_plan && a.rec_tab != nullptr;
+    // what every flavour fixes (phase_fused_kernel writes it into its private copy of the block and assumes it)
+    if (!(a.mode == 0 && (a.rec_tab != nullptr) == plan && trace_i32_of(a) == nullptr && a.pack == nullptr && a.x_next == nullptr && a.epsilon > 0.0 &&
+          a.perm_tab != nullptr && a.inv_tab != nullptr && a.replay == 0 && (!dream || (a.u_epsilon > 0.0 && a.n_cr == 3))))
+        return FLAVOUR_GENERAL;
+    const bool single = a.n_peers == 0 && a.L.world == 1 && a.lo == 0 && stamps_allow_hot(a) && a.accbits == nullptr;
+    if (single && a.adapt_on == 0) return plan ? FLAVOUR_STEADY_PLAN : FLAVOUR_STEADY;
+    if (plan && a.adapt_on == 0 && a.L.world > 1 && a.stamps == nullptr && (a.accbits != nullptr || a.n_peers > 0)) return FLAVOUR_SHARD_PLAN;
+    if (single && a.adapt_on != 0 && dream) return plan ? FLAVOUR_ADAPT_PLAN : FLAVOUR_ADAPT;
+    return FLAVOUR_GENERAL;
 }
-__host__ inline bool phase_args_hot(const PhaseArgs& a, bool dream, bool with_plan, bool adapting) {
-    return a.n_peers == 0 && a.mode == 0 && (a.rec_tab != nullptr) == with_plan && trace_i32_of(a) == nullptr && a.pack == nullptr && a.x_next == nullptr &&
-           (a.adapt_on != 0) == adapting && a.epsilon > 0.0 && a.L.world == 1 &&
-           a.perm_tab != nullptr && a.inv_tab != nullptr && a.lo == 0 && stamps_allow_hot(a) && a.accbits == nullptr && a.replay == 0 &&
-           (!dream || (a.u_epsilon > 0.0 && a.n_cr == 3));
-}
+constexpr bool flavour_is_steady(int f) { return f == FLAVOUR_STEADY_PLAN || f == FLAVOUR_STEADY; }
 template <int ALGO, int TARGET, int LPC, int DPL, int NP, int HOT = 0>
 __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kernel(
 #ifdef BPM_PRELOAD
@@ -1403,7 +1415,7 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     const uint32_t* pl_plan, uint32_t pl_upd_off, uint32_t pl_n_items, uint32_t pl_mode,
 #endif
     const PhaseArgs a_in) {
-    // HOT: the host launches this instantiation only when phase_args_hot() / phase_args_hot_sharded() holds.  What the
+    // HOT: the host launches this instantiation only where choose_flavour() returns it.  What the
     // predicate fixes is written into a private copy of the argument block (constants the compiler propagates; an
     // assumption on a POINTER loaded from the kernarg segment does not survive address-space inference), the positive /
     // non-null ones are assumed; every other path drops out -- cfg2's kernel: 637 instead of 2520 instructions, 33

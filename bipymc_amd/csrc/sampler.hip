@@ -161,6 +161,7 @@ static int load_rccl() {
 
 // ---- kernel dispatch ---------------------------------------------------------------
 typedef void (*PhaseLaunch)(const PhaseArgs&, hipStream_t);
+typedef void (*FusedLaunch)(const PhaseArgs&, int flavour, hipStream_t);      // an update launch: the flavour prepare_generation chose for it (kernels.h: Flavour)
 typedef void (*EvalLaunch)(const double*, uint32_t, uint32_t, uint32_t, const double*, double*, hipStream_t);
 
 // What the functions of the generation loop (run_generations -> group_generation -> prepare_generation / finish_generation -> the launch_*
@@ -212,18 +213,10 @@ struct Dispatch {
     // following one -- so no scope resets it.
     bool need_acquire = false;
 
-    // ---- tallies of the generation, restarted by prepare_generation and held against the host's prediction by finish_generation
-    // update launches that took a flavour which writes level 1 of the CR reduction ITSELF (kernels.h: CRP): what finish_generation holds against
-    // gen_cr_inkernel before it lets cr_final_kernel fold the partial sums
-    int crp_launched = 0;
-    // ... and those that were handed a pending fold of the previous generation's sums AND took a flavour that folds (PhaseArgs::cr_fold_part; bpm_sampler::cr_pending)
-    int crfold_launched = 0;
-
     // ---- per-thread counters, never reset: update-kernel dispatches by path (bpm_get_launch_stats) and altogether (bpm_step_timed)
     int64_t n_direct = 0, n_stream = 0;
     int64_t timed_launches = 0;
 
-    void restart_tallies() { crp_launched = 0; crfold_launched = 0; }
     void mark_acquire(bool v) { need_acquire = v; }
     // everything a DispatchScope owns, back to idle
     void idle() {
@@ -231,7 +224,6 @@ struct Dispatch {
         dq = nullptr; group_direct = false; dq_error = false; update_fence = bpm::DirectQueue::FENCED;
         wt_stores = false; call_last_gen = false; dq_call_last_gen = false;
         stop_event = nullptr; sig = -1; release_this = false;
-        restart_tallies();
     }
 };
 static thread_local Dispatch g_disp;
@@ -354,38 +346,24 @@ static inline void launch_packed(K kernel, hipFunction_t& fn, const PhaseArgs& a
 template <int ALGO, int T, int NP, int LPC, int DPL, int HOT>
 static void launch_hot(const PhaseArgs& a, hipStream_t s) {
     static hipFunction_t fn = nullptr;
-    if (ALGO == ALGO_DREAM && hot_is_adapt(HOT) && crp_shape(LPC, DPL)) {
-        Dispatch& d = g_disp;
-        ++d.crp_launched;
-        if (a.cr_fold_part != nullptr) ++d.crfold_launched;
-    }
     constexpr unsigned blk = (unsigned)block_for_hot(LPC, HOT, DPL), cpw = blk / (unsigned)LPC;      // (burn-in flavours of one wavefront per chain: 16 chains per workgroup)
     launch_packed(phase_fused_kernel<ALGO, T, LPC, DPL, NP, HOT>, fn, a, (a.n_items + cpw - 1u) / cpw, blk, s);
 }
+// The instantiation of the flavour chosen for the launch (prepare_generation; kernels.h: choose_flavour): same argument block, same two launch paths
+// for all of them.  A shape has the flavours choose_flavour can return for it: those with plan records only where the shape can read them, the
+// burn-in ones only for DREAM.
 template <int ALGO, int T, int NP, int LPC, int DPL>
-static void launch_fused(const PhaseArgs& a, hipStream_t s) {
-    {   // frequent cases take a specialised instantiation (kernels.h: HOT): steady state, DREAM's burn-in, a rank of a world
-        constexpr bool CAN_PLAN = (LPC == WAVE && DPL == 2);               // the shape that can read plan records
-        const bool wp = CAN_PLAN && a.rec_tab != nullptr;
-        constexpr bool DREAM_ = ALGO == ALGO_DREAM;
-        static const bool no_hot = test_path("nohot");
-        if (!no_hot && phase_args_hot(a, DREAM_, wp, false)) {
-            if (wp) launch_hot<ALGO, T, NP, LPC, DPL, (CAN_PLAN ? 1 : 2)>(a, s); else launch_hot<ALGO, T, NP, LPC, DPL, 2>(a, s);
-            return;
-        }
-        if (!no_hot && phase_args_hot_sharded(a, DREAM_, wp)) {
-            if (wp) launch_hot<ALGO, T, NP, LPC, DPL, (CAN_PLAN ? 5 : 6)>(a, s); else launch_hot<ALGO, T, NP, LPC, DPL, 6>(a, s);
-            return;
-        }
-        if (!no_hot && DREAM_ && phase_args_hot(a, true, wp, true)) {
-            if (wp) launch_hot<ALGO, T, NP, LPC, DPL, (DREAM_ ? (CAN_PLAN ? 3 : 4) : 2)>(a, s); else launch_hot<ALGO, T, NP, LPC, DPL, (DREAM_ ? 4 : 2)>(a, s);
-            return;
-        }
+static void launch_fused(const PhaseArgs& a, int flavour, hipStream_t s) {
+    constexpr bool CAN_PLAN = (LPC == WAVE && DPL == 2), DREAM_ = ALGO == ALGO_DREAM;
+    switch (flavour) {
+        case FLAVOUR_STEADY_PLAN: if constexpr (CAN_PLAN) return launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_STEADY_PLAN>(a, s); break;
+        case FLAVOUR_STEADY: return launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_STEADY>(a, s);
+        case FLAVOUR_ADAPT_PLAN: if constexpr (CAN_PLAN && DREAM_) return launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_ADAPT_PLAN>(a, s); break;
+        case FLAVOUR_ADAPT: if constexpr (DREAM_) return launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_ADAPT>(a, s); break;
+        case FLAVOUR_SHARD_PLAN: if constexpr (CAN_PLAN) return launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_SHARD_PLAN>(a, s); break;
+        default: break;
     }
-    {   // the general instantiation: same argument block, same two launch paths
-        static hipFunction_t fn = nullptr;
-        launch_packed(phase_fused_kernel<ALGO, T, LPC, DPL, NP>, fn, a, grid_for(a.n_items, LPC), (unsigned)block_for(LPC), s);
-    }
+    launch_hot<ALGO, T, NP, LPC, DPL, FLAVOUR_GENERAL>(a, s);
 }
 template <int ALGO, int LPC, int DPL>
 static void launch_propose(const PhaseArgs& a, hipStream_t s) {
@@ -432,7 +410,7 @@ constexpr int SHAPE_WIDE = 6;
 #define COMMA ,
 // ---- the looped wide-row kernels (kernels_wide.h): same argument block and launch paths as phase_fused_kernel
 template <int ALGO, int T, int NP>
-static void launch_wide(const PhaseArgs& a, hipStream_t s) {
+static void launch_wide(const PhaseArgs& a, int, hipStream_t s) {      // (one flavour: the general one)
     const unsigned grid = (unsigned)((a.n_items + (BPM_BLOCK_WAVE / WAVE) - 1) / (BPM_BLOCK_WAVE / WAVE));
     static hipFunction_t fn = nullptr;
     launch_packed(phase_wide_kernel<ALGO, T, NP, STAGE_FUSED>, fn, a, grid, (unsigned)BPM_BLOCK_WAVE, s);
@@ -452,13 +430,13 @@ static void launch_eval_wide(const double* X, uint32_t n, uint32_t ld, uint32_t 
     hipLaunchKernelGGL((eval_ll_wide_kernel<T>), dim3((n + (BPM_BLOCK_WAVE / WAVE) - 1) / (BPM_BLOCK_WAVE / WAVE)), dim3(BPM_BLOCK_WAVE), 0, s, X, n, ld, dim, tp, out);
 }
 // update-kernel variants: [DE-MC (1 pair) | DREAM del_pairs = 3 (compile-time) | DREAM any del_pairs][shape]
-static PhaseLaunch g_fused_gauss[3][7] = {SHAPE_TABLE(launch_fused, launch_wide<ALGO_DEMC COMMA TARGET_GAUSS COMMA 1>, ALGO_DEMC COMMA TARGET_GAUSS COMMA 1 COMMA),
+static FusedLaunch g_fused_gauss[3][7] = {SHAPE_TABLE(launch_fused, launch_wide<ALGO_DEMC COMMA TARGET_GAUSS COMMA 1>, ALGO_DEMC COMMA TARGET_GAUSS COMMA 1 COMMA),
                                           SHAPE_TABLE(launch_fused, launch_wide<ALGO_DREAM COMMA TARGET_GAUSS COMMA 3>, ALGO_DREAM COMMA TARGET_GAUSS COMMA 3 COMMA),
                                           SHAPE_TABLE(launch_fused, launch_wide<ALGO_DREAM COMMA TARGET_GAUSS COMMA 0>, ALGO_DREAM COMMA TARGET_GAUSS COMMA 0 COMMA)};
-static PhaseLaunch g_fused_mixture[3][7] = {SHAPE_TABLE(launch_fused, launch_wide<ALGO_DEMC COMMA TARGET_MIXTURE COMMA 1>, ALGO_DEMC COMMA TARGET_MIXTURE COMMA 1 COMMA),
+static FusedLaunch g_fused_mixture[3][7] = {SHAPE_TABLE(launch_fused, launch_wide<ALGO_DEMC COMMA TARGET_MIXTURE COMMA 1>, ALGO_DEMC COMMA TARGET_MIXTURE COMMA 1 COMMA),
                                             SHAPE_TABLE(launch_fused, launch_wide<ALGO_DREAM COMMA TARGET_MIXTURE COMMA 3>, ALGO_DREAM COMMA TARGET_MIXTURE COMMA 3 COMMA),
                                             SHAPE_TABLE(launch_fused, launch_wide<ALGO_DREAM COMMA TARGET_MIXTURE COMMA 0>, ALGO_DREAM COMMA TARGET_MIXTURE COMMA 0 COMMA)};
-static PhaseLaunch g_fused_banana[3] = {launch_fused<ALGO_DEMC, TARGET_BANANA, 1, 1, 2>, launch_fused<ALGO_DREAM, TARGET_BANANA, 3, 1, 2>,
+static FusedLaunch g_fused_banana[3] = {launch_fused<ALGO_DEMC, TARGET_BANANA, 1, 1, 2>, launch_fused<ALGO_DREAM, TARGET_BANANA, 3, 1, 2>,
                                         launch_fused<ALGO_DREAM, TARGET_BANANA, 0, 1, 2>};
 static PhaseLaunch g_propose[2][7] = {SHAPE_TABLE(launch_propose, launch_wide_propose<ALGO_DEMC>, ALGO_DEMC COMMA),
                                       SHAPE_TABLE(launch_propose, launch_wide_propose<ALGO_DREAM>, ALGO_DREAM COMMA)};
@@ -544,7 +522,7 @@ struct UserLikelihood {
     struct Fused {
         Module mod;
         hipFunction_t fn = nullptr;          // the general instantiation
-        hipFunction_t hot = nullptr;         // the steady-state one (HOT 1 / 2): launched when phase_args_hot(a, dream, with_plan, false) holds
+        hipFunction_t hot = nullptr;         // the steady-state one (HOT 1 with update records, 2 without: compiled for what the sampler builds)
         hipFunction_t eval = nullptr;        // eval_ll_kernel with the same target: the current states' ln-likes by the update kernel's own arithmetic
         hipFunction_t adapt = nullptr;       // DREAM's burn-in instantiation (HOT 3 / 4): level 1 of the CR reduction and the consumer-side fold inside the launch
         unsigned block = 0, block_adapt = 0;
@@ -628,14 +606,13 @@ struct bpm_sampler {
     // one wavefront at the floor of a dependent launch, 4.5 us of cfg2's 20.6 us burn-in generation): it stays pending, and every workgroup of the NEXT
     // generation's first update launch folds the sums itself (PhaseArgs::cr_fold_part: a wavefront per array of partial sums, the same additions in the same order), workgroup 0 stores
     // the new totals into the other totals block, which the second launch and everything later read.  What cannot consume a pending fold -- the last generation
-    // of a bpm_step call, the first steady-state generation, a launch that takes another flavour -- gets cr_final_kernel as before (cr_flush_pending).
+    // of a bpm_step call, the first steady-state generation, a launch of another flavour -- gets cr_final_kernel as before (cr_flush_pending).
     bool cr_pending = false;
     const double* cr_pend_src = nullptr;      // (the generation's level-1 sums, or what the cr_mid_kernel passes left of them: cr_pend_cnt <= CR_FINAL_MAX per array)
     uint32_t cr_pend_cnt = 0;
-    bool gen_fold_planned = false;    // this generation's first update launch was given a pending fold: finish_generation checks that it took a flavour that folds
     double* cr_p2[2] = {nullptr, nullptr};
     uint32_t cr_g1 = 16, cr_n1 = 0;
-    bool gen_cr_inkernel = false;     // this generation's update kernels write level 1 themselves (both launches are burn-in flavours: HOT 3 / 4)
+    bool gen_cr_inkernel = false;     // this generation's update kernels write level 1 themselves (every launch has a burn-in flavour, HOT 3 / 4, of a shape that sums)
     unsigned long long* counters = nullptr;  // device: [2] = NaN ratios
     uint32_t* acc_count = nullptr;           // device: accepted updates per local chain, this run
     int64_t gens_this_run_local = 0;
@@ -788,6 +765,11 @@ struct bpm_sampler {
     bool outlier_due = false;    // set by finish_generation, served by the group driver (all ranks take part)
     // per-generation cache (host-callback path keeps it between propose and commit)
     PhaseArgs cur_args[2];
+    // ... and beside it what prepare_generation chose for the two update launches: the kernel flavour (kernels.h: Flavour) and who launches it
+    // (the shipped target's table entry, or the run-time module's launcher) -- launch_update launches exactly this
+    int cur_hot[2] = {0, 0};
+    FusedLaunch cur_launch = nullptr;
+    int64_t n_by_flavour[N_FLAVOURS] = {};      // update launches of this handle by flavour, never reset (bpm_debug_flavour_counts)
     // several chains per wavefront + device target (kernels.h: lean_scalars): the update kernels neither read nor write the ln-like cache `ll`
     // (they re-evaluate it from the own row); ll_stale says that generations have run since it was last evaluated -- refresh_ll brings it up
     // to date for whoever reads it (bpm_get_loglike, the outlier check)
@@ -797,7 +779,7 @@ struct bpm_sampler {
 };
 
 
-static PhaseLaunch pick_fused(const bpm_sampler* s) {
+static FusedLaunch pick_fused(const bpm_sampler* s) {
     const int v = s->cfg.algo != BPM_ALGO_DREAM ? 0 : (s->cfg.del_pairs == 3 ? 1 : 2);
     switch (s->cfg.target_id) {
         case BPM_TARGET_GAUSS_EQUICORR: return g_fused_gauss[v][s->shape.idx];
@@ -805,6 +787,13 @@ static PhaseLaunch pick_fused(const bpm_sampler* s) {
         case BPM_TARGET_BANANA_2D: return g_fused_banana[v];
         default: return nullptr;
     }
+}
+static void launch_user_fused(const PhaseArgs& a, int flavour, hipStream_t st);      // (the run-time module's launcher: below, beside run_generations)
+// One update launch of the generation prepare_generation laid out: the argument block, the flavour and the launcher it chose
+static inline void launch_update(bpm_sampler* s, int ph) {
+    const int f = s->cur_hot[ph];
+    ++s->n_by_flavour[f];
+    s->cur_launch(s->cur_args[ph], f, s->stream);
 }
 
 // leave direct mode: everything dispatched on the library's own queue has finished and is visible to the HIP stream and the host
@@ -941,15 +930,19 @@ static int ensure_history(bpm_sampler* s, int64_t rows) {
     return 0;
 }
 
+// ln_like of n rows (ld doubles apart) by the sampler's shipped target, on its stream; false: a host-callback target has no kernel of its own
+static bool launch_eval_target(bpm_sampler* s, const double* X, uint32_t n, double* out) {
+    switch (s->cfg.target_id) {
+        case BPM_TARGET_GAUSS_EQUICORR: g_eval_gauss[s->shape.idx](X, n, s->ld, s->dim, s->tparams, out, s->stream); return true;
+        case BPM_TARGET_MIXTURE_PAIRS: g_eval_mixture[s->shape.idx](X, n, s->ld, s->dim, s->tparams, out, s->stream); return true;
+        case BPM_TARGET_BANANA_2D: launch_eval<TARGET_BANANA, 1, 2>(X, n, s->ld, s->dim, s->tparams, out, s->stream); return true;
+        default: return false;
+    }
+}
+
 static int eval_local_ll(bpm_sampler* s) {
     // ln_like of the local chains' current state into the cache (device targets only)
-    const double* Xl = s->G + (uint64_t)s->rank * s->L.blk;
-    switch (s->cfg.target_id) {
-        case BPM_TARGET_GAUSS_EQUICORR: g_eval_gauss[s->shape.idx](Xl, s->n_local, s->ld, s->dim, s->tparams, s->ll, s->stream); break;
-        case BPM_TARGET_MIXTURE_PAIRS: g_eval_mixture[s->shape.idx](Xl, s->n_local, s->ld, s->dim, s->tparams, s->ll, s->stream); break;
-        case BPM_TARGET_BANANA_2D: launch_eval<TARGET_BANANA, 1, 2>(Xl, s->n_local, s->ld, s->dim, s->tparams, s->ll, s->stream); break;
-        default: return 0;  // host callback: caller supplies values via bpm_set_loglike
-    }
+    if (!launch_eval_target(s, s->G + (uint64_t)s->rank * s->L.blk, s->n_local, s->ll)) return 0;      // host callback: caller supplies values via bpm_set_loglike
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1899,33 +1892,44 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
             a.x_next = s->x_next;
         }
     }
-    // CR reduction, level 1 (kernels.h): written by the update kernels themselves when BOTH launches of the generation take a burn-in flavour
-    // (HOT 3 / 4: single GPU, work item = position, no trace ...: the predicate launch_fused applies), else computed from the slots in finish_generation
-    s->gen_cr_inkernel = false;
-    g_disp.restart_tallies();
-    s->gen_fold_planned = false;
+    // The flavour of each update launch, chosen HERE and nowhere else (kernels.h: choose_flavour): launch_update launches what cur_hot says, and the plan
+    // of the CR reduction below is a function of it.  The looped wide-row kernel and the synchronous mode have the general flavour only, and so has a
+    // host-callback sampler nothing launches an update kernel for (cur_launch == nullptr: its generation is the proposal and commit kernels).
+    static const bool no_hot = test_path("nohot"), cr_slots = test_path("crslots");
+    const bool user_driven = g_disp.user_cur == s;      // the update kernel compiled around a HIP-source likelihood drives this (host-callback) sampler
+    const UserLikelihood::Fused& mod = s->like.fused;
+    s->cur_launch = user_driven ? launch_user_fused : pick_fused(s);
+    for (int ph = 0; ph < 2; ++ph) {
+        const PhaseArgs& a = s->cur_args[ph];
+        int f = (no_hot || sync || s->shape.idx == SHAPE_WIDE || !s->cur_launch) ? FLAVOUR_GENERAL : choose_flavour(a, dream, s->shape.lpc == WAVE && s->shape.dpl == 2);
+        // a run-time module holds the general instantiation, ONE steady-state flavour and (DREAM) ONE burn-in flavour, each compiled with update
+        // records exactly when this sampler builds them (plan_on)
+        if (user_driven && !(((flavour_is_steady(f) && mod.hot != nullptr) || (hot_is_adapt(f) && mod.adapt != nullptr)) && (a.rec_tab != nullptr) == s->plan_on))
+            f = FLAVOUR_GENERAL;
+        s->cur_hot[ph] = f;
+    }
+    // CR reduction, level 1 (kernels.h): written by the update kernels themselves when EVERY non-empty launch of the generation has a burn-in flavour
+    // (HOT 3 / 4) of a shape that sums (crp_shape), else computed from the slots in finish_generation
     if (s->cr_p1) s->cr_p1_cur = s->cr_p1 + (size_t)(s->t_abs & 1) * 2 * MAX_CR * s->cr_n1;
-    // (a host-callback sampler: only while the update kernel compiled around its HIP-source likelihood drives it -- Dispatch::user_cur -- and has the burn-in flavour)
-    if (s->gen_cr_reduce && dream && (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK || (g_disp.user_cur == s && s->like.fused.adapt != nullptr && (s->cur_args[0].rec_tab != nullptr) == s->plan_on)) &&
-        s->shape.idx != SHAPE_WIDE && crp_shape(s->shape.lpc, s->shape.dpl) &&
-        !test_path("nohot") && !test_path("crslots")) {
-        bool ok = true;
+    s->gen_cr_inkernel = s->gen_cr_reduce && !cr_slots && crp_shape(s->shape.lpc, s->shape.dpl);
+    for (int ph = 0; ph < 2; ++ph)
+        if (s->cur_args[ph].n_items > 0 && !hot_is_adapt(s->cur_hot[ph])) s->gen_cr_inkernel = false;
+    if (s->gen_cr_inkernel) {
+        const uint32_t n_first = (s->N + 1u) / 2u;
         for (int ph = 0; ph < 2; ++ph) {
-            const PhaseArgs& a = s->cur_args[ph];
-            ok = ok && (a.n_items == 0 || phase_args_hot(a, true, a.rec_tab != nullptr, true));
-        }
-        if (ok) {
-            const uint32_t n_first = (s->N + 1u) / 2u;
-            for (int ph = 0; ph < 2; ++ph) {
-                PhaseArgs& a = s->cur_args[ph];
-                a.cr_part1 = s->cr_p1_cur;
-                a.cr_chunk0 = a.upd_off == 0u ? 0u : cr_chunks_of(n_first, s->cr_g1);
-            }
-            s->gen_cr_inkernel = true;
+            PhaseArgs& a = s->cur_args[ph];
+            a.cr_part1 = s->cr_p1_cur;
+            a.cr_chunk0 = a.upd_off == 0u ? 0u : cr_chunks_of(n_first, s->cr_g1);
         }
     }
+    // Two rules that differ on purpose.  A SHIPPED target's launch keeps its burn-in flavour in every adapting generation, whether or not level 1 is
+    // written in-kernel (cr_part1 may be null: the kernel then writes the chains' slots).  A run-time MODULE's burn-in flavour is taken only when
+    // in-kernel level 1 was planned: its other adapting generations run on the general instantiation.
+    if (user_driven && !s->gen_cr_inkernel)
+        for (int ph = 0; ph < 2; ++ph)
+            if (hot_is_adapt(s->cur_hot[ph])) s->cur_hot[ph] = FLAVOUR_GENERAL;
     // a pending fold of the previous generation's CR statistics (bpm_sampler::cr_pending): consumed by this generation's first update launch when that one
-    // takes a flavour that can (a burn-in flavour that sums level 1 itself: HOT 3 / 4), else dispatched now, ahead of the update launches
+    // has a flavour that can (a burn-in flavour that sums level 1 itself: HOT 3 / 4), else dispatched now, ahead of the update launches
     if (s->cr_pending) {
         PhaseArgs& a0 = s->cur_args[0];
         if (s->gen_cr_inkernel && a0.n_items > 0 && a0.cr_part1 != nullptr) {
@@ -1933,7 +1937,6 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
             std::swap(s->cr_state, s->cr_state_alt);
             s->cur_args[1].cr_state = s->cr_state;      // (the second launch reads what workgroup 0 of the first one stored; the first takes p_cr from its own fold)
             s->cr_pending = false;
-            s->gen_fold_planned = true;
         } else {
             CK(cr_flush_pending(s));
         }
@@ -1951,20 +1954,8 @@ static int finish_generation(bpm_sampler* s) {
         const int fence = s->dq_fence | bpm::DirectQueue::ACQUIRE;      // (a few hundred bytes, all through agent-scope stores: no release on these packets)
         Dispatch& d = g_disp;
         if (d.dq) d.mark_acquire(false);
-        // The host PREDICTED (prepare_generation) that both launches take a flavour that writes level 1 itself; what was launched decides.  Every
-        // flavour that does not write level 1 writes the chains' slots (kernels.h: finish_update<..., CRP_W>), so "none did" falls back to
-        // cr_level1_kernel over the slots; a mix of the two would fold stale partial sums into p_cr -- an error, never a silent result.
-        bool level1_from_slots = !s->gen_cr_inkernel;
-        if (s->gen_fold_planned && d.crfold_launched != 1)
-            return fail("CR reduction: the first update launch of generation " + std::to_string((long long)s->t_abs) + " was handed the previous generation's fold and took a flavour that "
-                        "does not fold (launch_fused's flavour choice and prepare_generation's prediction disagree)");
-        if (s->gen_cr_inkernel) {
-            const int want = (s->cur_args[0].n_items > 0 ? 1 : 0) + (s->cur_args[1].n_items > 0 ? 1 : 0);
-            if (d.crp_launched == 0 && want > 0) level1_from_slots = true;
-            else if (d.crp_launched != want)
-                return fail("CR reduction: " + std::to_string(d.crp_launched) + " of " + std::to_string(want) + " update launches of generation " + std::to_string((long long)s->t_abs) +
-                            " wrote their level-1 partial sums (launch_fused's flavour choice and prepare_generation's prediction disagree)");
-        }
+        // (every flavour that does not write level 1 itself writes the chains' slots: kernels.h, finish_update<..., CRP_W>)
+        const bool level1_from_slots = !s->gen_cr_inkernel;
         if (level1_from_slots) {
             const PhaseArgs& a0 = s->cur_args[0];
             typedef void (*L1K)(Layout, PermKey, const uint32_t*, uint32_t, uint32_t, uint32_t, double*);
@@ -2264,7 +2255,7 @@ static int exchange_replay(const Group& g, int ph) {
 
 // xmode: how the half generations' updates reach the other ranks: 0 dense all-gather, 1 accepted rows, 2 accept bytes + replay,
 // 3 pushed by their owners from inside the update kernel (then only the cross-rank barrier follows a half generation)
-static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLaunch fn) {
+static int group_generation(const Group& g, int64_t n_ahead, int xmode) {
     Dispatch& d = g_disp;
     const long long tp0 = g_host_timing ? now_ns() : 0;
     for (int r = 0; r < g.R; ++r) {
@@ -2278,7 +2269,7 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
     if (g.h[0]->cfg.algo == BPM_ALGO_DEMC_SYNC) {
         for (int r = 0; r < g.R; ++r) {
             bpm_sampler* s = g.h[r];
-            fn(s->cur_args[0], s->stream);
+            launch_update(s, 0);
             HIPCK(hipMemcpyAsync(s->G + (uint64_t)s->rank * s->L.blk, s->x_next, (size_t)s->n_local * s->ld * sizeof(double),
                                  hipMemcpyDeviceToDevice, s->stream));      // apply the banked updates
         }
@@ -2304,7 +2295,7 @@ static int group_generation(const Group& g, int64_t n_ahead, int xmode, PhaseLau
                         d.stop_event = s->ev1; s->timed_l1 = d.timed_launches;
                     }
                     const long long tl0 = g_host_timing ? now_ns() : 0;
-                    fn(s->cur_args[ph], s->stream);
+                    launch_update(s, ph);
                     if (g_host_timing) { const long long tl1 = now_ns(); g_ns_launch += tl1 - tl0; ++g_n_launch; if (s->timed_last_gen >= 0) { g_launch_log.push_back(tl0); g_launch_log.push_back(tl1); } }
                 }
                 if (local_serial(g)) HIPCK(hipStreamSynchronize(g.h[r]->stream));
@@ -2349,22 +2340,19 @@ static bool group_goes_direct(const Group& g, bool push, bool& group_direct) {
 
 static int run_generations_user(bpm_sampler* s, int64_t n_gens);      // (a host-callback sampler with a device likelihood: below, beside the host-callback core)
 // the update kernel compiled at run time around a caller's likelihood (bpm_sampler::like.fused): the general instantiation's launch, from a module
-static void launch_user_fused(const PhaseArgs& a, hipStream_t st) {
+static void launch_user_fused(const PhaseArgs& a, int flavour, hipStream_t st) {
     Dispatch& d = g_disp;
     bpm_sampler* s = d.user_cur;
     if (!s || !s->like.fused.fn) { d.user_launch_failed = true; return; }      // (never: run_generations routes here only with the module in place -- and says so if not)
     PhaseArgs ka = a;
     ka.tparams = s->like.params.p;                   // the caller's parameter block is the target's
-    static const bool no_hot = test_path("nohot");
-    // burn-in: prepare_generation handed this launch the level-1 sums to write (cr_part1) only after phase_args_hot(a, true, plan, true) held for BOTH launches
-    const bool adapt = a.cr_part1 != nullptr && s->like.fused.adapt != nullptr;
-    if (adapt) { ++d.crp_launched; if (a.cr_fold_part != nullptr) ++d.crfold_launched; }
-    const unsigned block = adapt ? s->like.fused.block_adapt : s->like.fused.block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
-    // (the steady-state instantiation was compiled for update records exactly when this sampler builds them: HOT 1 / HOT 2)
-    const bool hot = !adapt && !no_hot && s->like.fused.hot && (a.rec_tab != nullptr) == s->plan_on && phase_args_hot(a, s->cfg.algo == BPM_ALGO_DREAM, a.rec_tab != nullptr, false);
+    // [0] the general instantiation, [1] the steady-state one, [2] the burn-in one: prepare_generation chose among those the module holds
+    const UserLikelihood::Fused& m = s->like.fused;
+    const int k = hot_is_adapt(flavour) ? 2 : (flavour_is_steady(flavour) ? 1 : 0);
+    const unsigned block = k == 2 ? m.block_adapt : m.block, cpw = block / (unsigned)s->shape.lpc, grid = (a.n_items + cpw - 1u) / cpw;
     // (launch_packed's two paths; the module's kernels take the argument block alone, no preloaded leading arguments)
-    if (d.dq) return update_packet(d, d.dq->kernel_by_name(s->like.fused.names[adapt ? 2 : (hot ? 1 : 0)]), grid, block, &ka, sizeof(ka));
-    update_on_stream(d, adapt ? s->like.fused.adapt : (hot ? s->like.fused.hot : s->like.fused.fn), grid, block, &ka, sizeof(ka), st);
+    if (d.dq) return update_packet(d, d.dq->kernel_by_name(m.names[k]), grid, block, &ka, sizeof(ka));
+    update_on_stream(d, k == 2 ? m.adapt : (k == 1 ? m.hot : m.fn), grid, block, &ka, sizeof(ka), st);
 }
 static int run_generations(const Group& g, int64_t n_gens) {
     bpm_sampler* s0 = g.h[0];
@@ -2373,8 +2361,7 @@ static int run_generations(const Group& g, int64_t n_gens) {
     const bool user_fused = s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->like.fused.fn != nullptr && g.R == 1;
     if (s0->cfg.target_id == BPM_TARGET_HOST_CALLBACK && s0->like.fn && g.R == 1 && !user_fused) return run_generations_user(s0, n_gens);
     if (user_fused && s0->world > 1 && !s0->comm) return fail("bpm_step: a host-callback sampler of a world needs an RCCL communicator (create it with a unique id)");
-    PhaseLaunch fn = user_fused ? launch_user_fused : pick_fused(s0);
-    if (!fn) return fail("bpm_step: host-callback target must be driven with bpm_propose / bpm_commit (or give it a device likelihood: bpm_set_device_likelihood)");
+    if (!user_fused && !pick_fused(s0)) return fail("bpm_step: host-callback target must be driven with bpm_propose / bpm_commit (or give it a device likelihood: bpm_set_device_likelihood)");
     const bool dream = s0->cfg.algo == BPM_ALGO_DREAM;
     int64_t done = 0;
     const bool push = s0->push_enabled && s0->push_connected;
@@ -2429,7 +2416,7 @@ static int run_generations(const Group& g, int64_t n_gens) {
                 CK(push_barrier(g));
                 push_entered = true;
             }
-            const int rc_gen = group_generation(g, n_gens - done, push ? 3 : (replay ? 2 : 0), fn);
+            const int rc_gen = group_generation(g, n_gens - done, push ? 3 : (replay ? 2 : 0));
             if (direct) {
                 for (int r = 0; r < (group_direct ? g.R : 1); ++r) {
                     bpm_sampler* s = g.h[r];
@@ -2458,7 +2445,7 @@ static int run_generations(const Group& g, int64_t n_gens) {
             for (uint32_t b = 0; b < s->xnsub; ++b)      // own counters armed (the capacity, hence the layout, may have changed)
                 HIPCK(hipMemsetAsync(s->PK + ((uint64_t)s->rank * s->xnsub + b) * s->xstride(), 0, sizeof(double), s->stream));
         }
-        for (int64_t i = 0; i < K; ++i) CK(group_generation(g, n_gens - done - i, 1, fn));
+        for (int64_t i = 0; i < K; ++i) CK(group_generation(g, n_gens - done - i, 1));
         bool overflow = false;
         uint32_t maxc = 0;
         for (int r = 0; r < g.R; ++r) {
@@ -2484,7 +2471,7 @@ static int run_generations(const Group& g, int64_t n_gens) {
                 s->k_gen = k.k_gen; s->t_abs = k.t_abs; s->hist_rows = k.hist_rows; s->rows_logical = k.rows_logical; s->w_rows = k.w_rows;
                 s->n_sparse_replays += 1;
             }
-            for (int64_t i = 0; i < K; ++i) CK(group_generation(g, n_gens - done - i, 0, fn));
+            for (int64_t i = 0; i < K; ++i) CK(group_generation(g, n_gens - done - i, 0));
         }
         // capacity for the next chunk from the largest sub-block count seen (identical on every rank: all see all
         // counters): a margin of ~3 sigma of a Poisson count on top of an observed maximum over >= 64 half generations
@@ -2904,14 +2891,13 @@ extern "C" int bpm_step_profiled(bpm_handle_t s, int64_t n_gens, double* kernel_
     CK(ensure_gen_sums(s, s->rows_logical + n_gens));
     std::vector<hipEvent_t> ev((size_t)n_gens * 4);
     for (auto& e : ev) HIPCK(hipEventCreate(&e));
-    PhaseLaunch fn = pick_fused(s);
     s->sparse_active = false;
     s->replay_active = false;
     for (int64_t g = 0; g < n_gens; ++g) {
         CK(prepare_generation(s, n_gens - g));
         for (int ph = 0; ph < 2; ++ph) {
             HIPCK(hipEventRecord(ev[(size_t)g * 4 + 2 * ph], s->stream));
-            if (s->cur_args[ph].n_items > 0) fn(s->cur_args[ph], s->stream);
+            if (s->cur_args[ph].n_items > 0) launch_update(s, ph);
             HIPCK(hipEventRecord(ev[(size_t)g * 4 + 2 * ph + 1], s->stream));
             CK(allgather_state(s));
         }
@@ -2961,12 +2947,7 @@ extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_
                                (size_t)rows * s->n_local, hipMemcpyHostToDevice, s->stream));
         // ln_like of the old rows is not stored in the reference's checkpoint: recompute (device targets) or NaN
         if (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK) {
-            const uint32_t n = (uint32_t)((size_t)rows * s->n_local);
-            switch (s->cfg.target_id) {
-                case BPM_TARGET_GAUSS_EQUICORR: g_eval_gauss[s->shape.idx](s->hist, n, s->ld, s->dim, s->tparams, s->llhist, s->stream); break;
-                case BPM_TARGET_MIXTURE_PAIRS: g_eval_mixture[s->shape.idx](s->hist, n, s->ld, s->dim, s->tparams, s->llhist, s->stream); break;
-                default: launch_eval<TARGET_BANANA, 1, 2>(s->hist, n, s->ld, s->dim, s->tparams, s->llhist, s->stream); break;
-            }
+            (void)launch_eval_target(s, s->hist, (uint32_t)((size_t)rows * s->n_local), s->llhist);
             HIPCK(hipGetLastError());
         } else {
             // host-callback target: the caller supplies the current ln-likes next (bpm_set_loglike fills the last row);
@@ -4473,12 +4454,7 @@ extern "C" int bpm_eval_loglike(bpm_handle_t s, const double* X, int32_t n, doub
     HIPCK(hipMemsetAsync(dX, 0, (size_t)n * s->ld * sizeof(double), s->stream));
     HIPCK(hipMemcpy2DAsync(dX, s->ld * sizeof(double), X, s->dim * sizeof(double), s->dim * sizeof(double), n,
                            hipMemcpyHostToDevice, s->stream));
-    switch (s->cfg.target_id) {
-        case BPM_TARGET_GAUSS_EQUICORR: g_eval_gauss[s->shape.idx](dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
-        case BPM_TARGET_MIXTURE_PAIRS: g_eval_mixture[s->shape.idx](dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
-        case BPM_TARGET_BANANA_2D: launch_eval<TARGET_BANANA, 1, 2>(dX, n, s->ld, s->dim, s->tparams, dO, s->stream); break;
-        default: return fail("bpm_eval_loglike: host-callback target has no device ln_like");
-    }
+    if (!launch_eval_target(s, dX, (uint32_t)n, dO)) return fail("bpm_eval_loglike: host-callback target has no device ln_like");
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(out, dO, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
@@ -4587,23 +4563,22 @@ extern "C" int bpm_debug_time_kernels(bpm_handle_t s, int32_t reps, float* updat
     CK(check_handle(s));
     CK(set_device(s));
     if (reps < 1 || !update_us || !replay_us) return fail("bpm_debug_time_kernels: bad argument");
-    PhaseLaunch fn = pick_fused(s);
-    if (!fn) return fail("bpm_debug_time_kernels: device targets only");
+    if (!pick_fused(s)) return fail("bpm_debug_time_kernels: device targets only");
     const PhaseArgs& a = s->cur_args[1];
     if (a.n_items == 0) return fail("bpm_debug_time_kernels: run at least one generation first");
     HIPCK(hipStreamSynchronize(s->stream));
     *update_us = 0.f; *replay_us = 0.f;
     for (int which = 0; which < 2; ++which) {
         if (which == 1 && (!s->accbits_all || s->world == 1 || a.accbits == nullptr)) break;     // no replay exchange on this handle
-        PhaseArgs r = a;
+        PhaseArgs r = a;      // (the update launch itself is relaunched as prepare_generation laid it out: cur_args[1] with the flavour chosen for it)
         if (which == 1) {
             r.replay = 1u; r.accbits = nullptr; r.accbits_all = s->accbits_all;
             trace_set(r, nullptr, nullptr, nullptr); r.pack = nullptr; r.hist_row = nullptr; r.llhist_row = nullptr;
             r.adapt_on = 0u;
         }
-        for (int i = 0; i < 3; ++i) { if (which == 0) fn(r, s->stream); else launch_replay_any(s, r); }
+        for (int i = 0; i < 3; ++i) { if (which == 0) launch_update(s, 1); else launch_replay_any(s, r); }
         HIPCK(hipEventRecord(s->ev0, s->stream));
-        for (int i = 0; i < reps; ++i) { if (which == 0) fn(r, s->stream); else launch_replay_any(s, r); }
+        for (int i = 0; i < reps; ++i) { if (which == 0) launch_update(s, 1); else launch_replay_any(s, r); }
         HIPCK(hipEventRecord(s->ev1, s->stream));
         HIPCK(hipEventSynchronize(s->ev1));
         HIPCK(hipGetLastError());
@@ -4611,6 +4586,15 @@ extern "C" int bpm_debug_time_kernels(bpm_handle_t s, int32_t reps, float* updat
         HIPCK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
         (which == 0 ? *update_us : *replay_us) = ms * 1e3f / (float)reps;
     }
+    return 0;
+}
+
+// Test hook: this handle's update launches so far by kernel flavour (kernels.h: Flavour)
+extern "C" int bpm_debug_flavour_counts(bpm_handle_t s, int64_t out[7]) {
+    CK(check_handle_keep_direct(s));
+    if (!out) return fail("bpm_debug_flavour_counts: null argument");
+    static_assert(N_FLAVOURS == 7, "bpm_debug_flavour_counts reports 7 counts");
+    for (int f = 0; f < N_FLAVOURS; ++f) out[f] = s->n_by_flavour[f];
     return 0;
 }
 

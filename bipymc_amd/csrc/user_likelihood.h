@@ -46,8 +46,8 @@ inline std::string compile_user_likelihood(const std::string& user_src, const st
 // caller's function as its target (user_target.h: Target<TARGET_USER>) -- one launch per half generation instead of three.  kernels.h, philox.h and
 // the device code of this path travel inside the library as string literals (embedded_src.h, written by the Makefile).  The kernel-argument block
 // must be the library's own: the program is compiled with the library's BPM_TEST_HOOKS setting and exports sizeof(PhaseArgs) for the caller to compare.
-// Two instantiations: the general one (HOT 0) and the steady-state one (`hot`: 1 with update records, 2 without -- what phase_args_hot(a, dream, with_plan,
-// false) fixes is a compile-time constant) -- name_expr[0 / 1]; name_expr[2]: eval_ll_kernel with the same target; name_expr[3]: DREAM's burn-in instantiation (hot + 2).
+// Two instantiations: the general one (HOT 0) and the steady-state one (`hot`: 1 with update records, 2 without -- what choose_flavour fixes for
+// that flavour is a compile-time constant) -- name_expr[0 / 1]; name_expr[2]: eval_ll_kernel with the same target; name_expr[3]: DREAM's burn-in instantiation (hot + 2).
 // `ns`: the inline namespace the program's device code lives in -- unique per module of the process: the library's queue finds kernels by name.
 // What is generated here is only what depends on run-time values: the #defines, the explicit instantiations and bpm_user_sizeof.
 using UserEvalLlKernel = void(const double*, uint32_t, uint32_t, uint32_t, const double*, double*);      // eval_ll_kernel (kernels.h) as the host launches it from a module

@@ -635,6 +635,13 @@ class HipEngine(object):
                                         _iptr(inv), C.byref(flip)))
         return order, inv, bool(flip.value)
 
+    def flavour_counts(self):
+        """-> {flavour: update-kernel launches of this handle so far}, flavours that never ran left out (bpm_debug_flavour_counts; kernels.h: Flavour)"""
+        self._need_hooks("bpm_debug_flavour_counts")
+        out = (C.c_int64 * 7)()
+        self._ck(self.lib.bpm_debug_flavour_counts(self._h, out))
+        return {f: int(n) for f, n in enumerate(out) if n}
+
 
 def selftest_philox(n=4096, seed=42, device=0):
     """the inline Philox against rocRAND's device engine (a test hook: runs on the test variant of the library)"""

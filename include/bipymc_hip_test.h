@@ -57,6 +57,9 @@ int bpm_debug_coherence_probe(int32_t device, int32_t coherent_alloc, int64_t* w
 int bpm_debug_outlier_select(bpm_handle_t h, const double* omega, double out[6]);
 /* the update and the replay kernel of the handle's last half generation re-launched `reps` times and timed (destructive; tools/emulate_ranks.py) */
 int bpm_debug_time_kernels(bpm_handle_t h, int32_t reps, float* update_us, float* replay_us);
+/* update-kernel launches of this handle so far by kernel flavour (bipymc_amd/csrc/kernels.h: Flavour): out[0] the general kernel, out[1] / out[2] single
+ * GPU in the steady state with / without plan records, out[3] / out[4] the same during DREAM's CR adaptation, out[5] a rank of a world, out[6] unused */
+int bpm_debug_flavour_counts(bpm_handle_t h, int64_t out[7]);
 /* the inline Philox4x32-10 against rocRAND's device engine: n blocks of (seed, subsequence i, block i) from both */
 int bpm_selftest_philox(int32_t device, int32_t n, uint64_t seed, uint32_t* out_mine, uint32_t* out_rocrand);
 /* per-generation host decisions (flip, shuffle order and its inverse) for generation t */

@@ -30,7 +30,7 @@ def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, lau
     eng.set_state(X0)
     ora.set_state(X0)
     eng.begin_run()
-    eng.step(gens)                         # NO trace: phase_args_hot() holds, the HOT instantiations run
+    eng.step(gens)                         # NO trace: the specialised (HOT) instantiations run
     eng.synchronize()
     ls = eng.launch_stats()
     if launches is None:
@@ -261,7 +261,7 @@ def _target_case(kind, N, d, rs):
 #   g_fused_mixture[v][shape] v = 0, 1, 2; 0..6     -> test_every_dispatch_table_entry_equals_the_oracle[mix-*]     (+ cfg5's share; DE-MC: v = 0 was statistical only)
 #   g_fused_banana[v]         v = 0, 1, 2           -> test_every_dispatch_table_entry_equals_the_oracle[banana-*]  (+ cfg3; DREAM: v = 1, 2 were untested)
 # Synchronous DE-MC (BPM_ALGO_DEMC_SYNC: what bipymc_amd.samplers.DeMc runs on) takes row 0 of the same tables with PhaseArgs::mode == 2 and x_next set
-# (prepare_generation: the general instantiation, never a HOT one -- phase_args_hot wants x_next == nullptr), one launch per generation on the HIP stream:
+# (prepare_generation: the general instantiation, never a HOT one -- the synchronous mode has no other flavour), one launch per generation on the HIP stream:
 #   g_fused_gauss[0][0..6], mode 2                  -> test_synchronous_demc_on_every_kernel_shape_equals_the_oracle[gauss-*]  (+ its edge rows: N = 4 / d = 1, odd d
 #                                                      at 257, 513, 2047, 3001)
 #   g_fused_mixture[0][0..6], mode 2                -> test_synchronous_demc_on_every_kernel_shape_equals_the_oracle[mix-*]
