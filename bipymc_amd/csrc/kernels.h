@@ -742,6 +742,37 @@ __device__ __forceinline__ uint32_t chain_to_pos(const PhaseArgs& a, uint32_t c)
     return a.inv_tab ? a.inv_tab[c] : perm_inv(c, a.pk);
 }
 
+// The planned front of one wavefront per chain with one coordinate pair per lane: what the wavefront asks for FIRST.  Data flow needs two round trips
+// ahead of the rows -- record -> rows -- and the front spends exactly those: the whole 64-byte record (one wide scalar load; its address comes from the
+// preloaded arguments) together with the argument block's first lines (the Layout, and the pointers whose data the front reads next), ONE wait, then the own
+// row and the 2 NP partner rows, every lane loading (load_row_all).  Everything else the update reads -- ln-like cache, accept counter, p_cr, the target's
+// parameters, the gamma table, the far lines of the argument block -- is issued BEHIND the row requests (phase_fused_kernel), so that those misses ride in the
+// shadow of the row fetch instead of standing in front of it (each was a `s_waitcnt lgkmcnt(0)` of its own behind a first-touch miss: three ahead of the rows).
+template <int DPL, int NPX>
+struct PlanFront {
+    uint32_t rec[PLAN_WORDS];
+    double x[DPL], ra[NPX][DPL], rb[NPX][DPL];
+    double ll_cur, pcr[3], gl[DPL];      // the chain's cached ln_like, p_cr, the lane's entries of the gamma table: requested just ahead of the rows
+    uint32_t acc_prev;
+};
+typedef uint32_t bpm_u32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ bpm_u32x16 plan_record(const uint32_t* recp) {      // (records are 64-byte aligned: plan_kernel)
+    return *reinterpret_cast<const bpm_u32x16*>(__builtin_assume_aligned(recp, 4 * PLAN_WORDS));
+}
+template <int DPL, int NP>
+__device__ __forceinline__ void plan_front(const Layout& L, const bpm_u32x16 rv, int q, PlanFront<DPL, (NP > 0 ? NP : 1)>& fr) {
+    static_assert(PLAN_WORDS == 16 && DPL == 2, "one 64-byte record, one 16-byte load per lane and row");
+#pragma unroll
+    for (int i = 0; i < PLAN_WORDS; ++i) fr.rec[i] = rv[i];
+    load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[0]), q, L.ld, fr.x);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[5 + 2 * p]), q, L.ld, fr.ra[p]);
+        load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[5 + 2 * p + 1]), q, L.ld, fr.rb[p]);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // nothing the scheduler finds further down is issued ahead of the row requests
+}
+
 // Build the proposal of chain c (dream.py:43-93 / demc.py:161-182).
 // ALGO compile-time; NP = compile-time number of pairs (0: runtime a.P, DREAM only).
 struct NoEarly { template <class W> __device__ __forceinline__ void operator()(W&) const {} };
@@ -750,10 +781,14 @@ struct PcrGiven { bool on = false; double p[MAX_CR]; };
 // EARLY: work on the own row (wk.x) that the caller wants done while the partner rows are still on their way -- the re-evaluation of the
 // current state's ln_like (lean_scalars): behind the proposal it sat on the critical path of the latency-bound launches (cfg5's share:
 // 10.05 instead of 9.3 us per generation), here it runs in the shadow of the partner fetches.
-template <int ALGO, int LPC, int DPL, int NP, int LOAD_LL = 1 /* 1 always, 0 never, 2 unless a.lean */, class EARLY = NoEarly>
+// FRONT (plan_front below, one wavefront per chain with one coordinate pair per lane): the caller read the update's record and requested the own row and
+// the 2 NP partner rows before anything else; the record arrives by value, the rows as loads in flight, and this function has no draw path but the record's.
+template <int ALGO, int LPC, int DPL, int NP, int LOAD_LL = 1 /* 1 always, 0 never, 2 unless a.lean */, class EARLY = NoEarly, bool FRONT = false>
 __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bool active, int q, int cw,
                                               uint32_t* s_part, Work<DPL>& wk, const uint32_t* rec = nullptr,
-                                              unsigned long long* bpm_stamp = nullptr, EARLY early = EARLY(), const PcrGiven pcr_ovr = PcrGiven()) {
+                                              unsigned long long* bpm_stamp = nullptr, EARLY early = EARLY(), const PcrGiven pcr_ovr = PcrGiven(),
+                                              const PlanFront<DPL, (NP > 0 ? NP : 1)>* fr = nullptr) {
+    static_assert(!FRONT || (LPC == WAVE && DPL == 2), "the planned front serves one wavefront per chain with one coordinate pair per lane");
     constexpr bool DREAM = ALGO == ALGO_DREAM;
     // FAST: partner ids straight into registers, every lane for itself, when a lane IS a chain (LPC == 1: no other
     // lane to share the work with, so the LDS hand-over loop would only re-evaluate the same Philox block once per
@@ -764,6 +799,11 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     const uint32_t dim = a.L.dim, ld = a.L.ld;
     const uint32_t P = NP > 0 ? (uint32_t)NP : a.P;
     // state-dependent loads first: they overlap with all the draw arithmetic below
+    if constexpr (FRONT) {
+        const bool in_row = 2u * (uint32_t)q < ld;         // (requested from every lane, like the partner rows: load_row's zeros by a select on the value)
+#pragma unroll
+        for (int s = 0; s < DPL; ++s) wk.x[s] = in_row ? fr->x[s] : 0.0;
+    } else
     load_row<LPC, DPL>(row_ptr(a.L, c), q, ld, wk.x);      // (a non-temporal load of this read-once row measured no faster)
     wk.ll_cur = 0.0;
     wk.acc_prev = 0u;
@@ -771,10 +811,12 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #if defined(BPM_TEST_HOOKS) && defined(BPM_FAKE_NO_LL)      // timing experiment only (wrong results): what the chain-indexed ln-like cache and accept counter cost
         if (LPC < WAVE) wk.ll_cur = wk.x[0] * 1e-300; else
 #endif
+        if constexpr (FRONT) wk.ll_cur = fr->ll_cur; else
         if (LOAD_LL == 1 || (LOAD_LL == 2 && !a.lean)) wk.ll_cur = a.ll[c - a.lo];   // (else: the caller re-evaluates it from wk.x -- lean_scalars)
         // the accept counter: one wavefront per chain reads it here (a scalar load, early) and stores + 1 on accept; with several chains per
         // wavefront the read is a scattered 4-byte load per update -- there an accepted update bumps it with a device-scope atomic add without
         // return instead (one writer per address and launch: nothing serialises): cfg3 12.7 -> 11.9 us per generation, cfg5 52.2 -> 48.2
+        if constexpr (FRONT) wk.acc_prev = fr->acc_prev; else
         if (LPC == WAVE) wk.acc_prev = a.acc_count[c - a.lo];
     }
     if (DREAM && a.adapt_on) {                 // dream.py:128: requested here, used after the proposal and after the accept test
@@ -785,7 +827,8 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     double pcr[MAX_CR];                        // p_cr (uniform pointer: one scalar load of the whole block)
     if (DREAM) {
 #pragma unroll
-        for (int m = 0; m < MAX_CR; ++m) pcr[m] = pcr_ovr.on ? pcr_ovr.p[m] : a.cr_state[m];      // (pcr_ovr: the workgroup folded the totals itself, cr_fold_part)
+        for (int m = 0; m < MAX_CR; ++m)      // (pcr_ovr: the workgroup folded the totals itself, cr_fold_part; the planned front read the three values its flavours have)
+            pcr[m] = pcr_ovr.on ? pcr_ovr.p[m] : (FRONT ? (m < 3 ? fr->pcr[m < 3 ? m : 0] : 0.0) : a.cr_state[m]);
     }
     // gamma table held across the wavefront's lanes: the lookup by d' is then a v_readlane, not a dependent load
     double gtab[DPL];
@@ -797,7 +840,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
             // load's destination register, which the compiler guards with s_waitcnt vmcnt(0): every wavefront then sat
             // out its own-row fetch before it could even request the partner rows.
             const uint32_t gi = (uint32_t)(q + u * WAVE);
-            const double gl = a.gamma_tab[gi <= dim ? gi : dim];
+            const double gl = FRONT ? fr->gl[u] : a.gamma_tab[gi <= dim ? gi : dim];
             gtab[u] = gi <= dim ? gl : 0.0;
         }
     }
@@ -818,7 +861,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     // pair-selection blocks, lane npairs + 2NP the chain's header block -- instead of three separate
     // evaluations (one of them a 110-instruction scalar one) per wavefront.
     const uint32_t npairs = (dim + 1u) >> 1;
-    const bool merged = RL && DPL == 2 && (npairs + 2u * (uint32_t)NP + 1u <= (uint32_t)WAVE);
+    const bool merged = !FRONT && RL && DPL == 2 && (npairs + 2u * (uint32_t)NP + 1u <= (uint32_t)WAVE);
     u32x4 wpair[DPL / 2];
     u32x4 h0;
     // QUAD (DREAM, 4 lanes per chain, three pairs, d <= 8): the chain's seven Philox blocks -- four coordinate pairs,
@@ -835,10 +878,18 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     // (one wavefront per chain only.  With 4 lanes per chain the records measured no gain, cfg5/8 13.8 vs 13.9 us/generation;
     // with one lane per chain a loss -- cfg3 14.6 vs 12.3 with 64-byte records per lane, 13.8 vs 12.6 from a
     // structure-of-arrays table whose loads coalesce: at 65536 chains plan_kernel itself costs 1.3 us per generation)
-    const bool planned = (LPC == WAVE) && rec != nullptr;
+    const bool planned = FRONT || ((LPC == WAVE) && rec != nullptr);
     // the coordinate-pair blocks follow the row requests when a wavefront is one chain with one pair per lane
     const bool dims_late = planned && RL && DPL == 2;
-    if (planned) {
+    if (FRONT) {
+        h0.x = fr->rec[1]; h0.y = fr->rec[2]; h0.z = fr->rec[3]; h0.w = fr->rec[4];
+#pragma unroll
+        for (int i = 0; i < 2 * NP; ++i) part.r[i] = fr->rec[5 + i];
+        if (!dims_late) {
+#pragma unroll
+            for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
+        }
+    } else if (planned) {
         h0.x = rec[1]; h0.y = rec[2]; h0.z = rec[3]; h0.w = rec[4];
         if (FAST || RL) {
 #pragma unroll
@@ -935,7 +986,13 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     // jitter and gamma arithmetic below
     constexpr int NPX = NP > 0 ? NP : 1;
     double ra[NPX][DPL], rb[NPX][DPL];
-    if (DREAM && NP > 0) {
+    if (FRONT && DREAM && NP > 0) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+#pragma unroll
+            for (int s = 0; s < DPL; ++s) { ra[p][s] = fr->ra[p][s]; rb[p][s] = fr->rb[p][s]; }
+        }
+    } else if (DREAM && NP > 0) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {             // all 2 NP row loads in flight together
             if (LPC == WAVE) {
@@ -947,7 +1004,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
             }
         }
     }
-    BPM_STAMP(7);
+    if (!FRONT) BPM_STAMP(7);      // (the planned front stamped its own row requests)
     if (dims_late) wpair[0] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)q);      // overlaps with the row fetches
     if (DREAM) early(wk);
 
@@ -1106,8 +1163,14 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         // proposal was built -- three memory round trips in a row where one does.  The empty asm makes every id an input at ONE point.
         const bool do_snk = snk_possible && u_sel < a.p_snooker;
         if (LPC == 1) asm volatile("" ::"v"(ca), "v"(cb), "v"(snk_id[0]), "v"(snk_id[1]), "v"(snk_id[2]));
+        if constexpr (FRONT && NP == 1) {
+            const bool in_row = 2u * (uint32_t)q < ld;
+#pragma unroll
+            for (int s = 0; s < DPL; ++s) { ra[s] = in_row ? fr->ra[0][s] : 0.0; rb[s] = in_row ? fr->rb[0][s] : 0.0; }
+        } else {
         load_row<LPC, DPL>(row_ptr(a.L, ca), q, ld, ra);
         load_row<LPC, DPL>(row_ptr(a.L, cb), q, ld, rb);
+        }
         double rz[DPL], r1[DPL], r2[DPL];
 #pragma unroll
         for (int s = 0; s < DPL; ++s) { rz[s] = 0.0; r1[s] = 0.0; r2[s] = 0.0; }
@@ -1345,6 +1408,10 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
 // s_load_dwordx8/x16 behind one wait.  Measured: 13.1 vs 15.2 us/generation for the 4-lanes-per-chain kernel
 // (cfg5/8), no change with one lane per chain, and a LOSS with one wavefront per chain (17.1 vs 15.8, cfg2: there
 // the lazy loads hide behind the row fetches) -- so only kernels with several chains per wavefront do it.
+// (That loss predates plan records: the partner ids were drawn in the kernel then, the draw needed most of the block anyway, and some forty fields of all
+// eight lines stood in the first wait with nothing to overlap them.  The planned front of one wavefront per chain -- plan_front -- pulls forward only
+// what the update reads on its way to the accept test, together with the record, and requests the rows right behind that one wait: 5.235 -> 5.173 us per
+// launch at cfg2.  Pulling forward the row addresses alone and reading the rest behind the rows lost: those scalar loads queue behind the row traffic.)
 template <int LPC>
 __device__ __forceinline__ void pin_args(const PhaseArgs& a) {
     if (LPC != WAVE) {
@@ -1424,41 +1491,15 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     // indexes the argument block dynamically: one `a.thr[n_cr - 1]` had put it into scratch, 30 us/generation at cfg5/8.)
     constexpr bool COPY = (HOT != 0);
     constexpr bool SHARD = (HOT == 5 || HOT == 6), ADAPT = (HOT == 3 || HOT == 4), NOPLAN = (HOT == 2 || HOT == 4 || HOT == 6);
-    PhaseArgs a_hot;
-    if (COPY) {
-        a_hot = a_in;
-        a_hot.mode = 0u; trace_set(a_hot, nullptr, nullptr, nullptr); a_hot.pack = nullptr;
-        a_hot.replay = 0u; a_hot.x_next = nullptr; a_hot.adapt_on = ADAPT ? 1u : 0u;
-#ifndef BPM_STAMPS
-        a_hot.stamps = nullptr;
-#else
-        if (SHARD) a_hot.stamps = nullptr;
-#endif
-        if (!ADAPT) a_hot.cr_fold_part = nullptr;
-        if (!SHARD) { a_hot.accbits = nullptr; a_hot.lo = 0; a_hot.L.world = 1; a_hot.acc_by_item = 0u; a_hot.n_peers = 0u; a_hot.peer_tab = nullptr; }
-        if (ALGO == ALGO_DREAM) a_hot.n_cr = 3;
-        if (NOPLAN) { a_hot.plan = nullptr; a_hot.rec_tab = nullptr; }
-    }
-    const PhaseArgs& a = COPY ? a_hot : a_in;
-    if (HOT) {
-        __builtin_assume(a_in.mode == 0u); __builtin_assume(a_in.pack == nullptr);
-#ifdef BPM_TEST_HOOKS
-        __builtin_assume(a_in.trace_i32 == nullptr);
-#endif
-        __builtin_assume(a_in.x_next == nullptr); __builtin_assume(a_in.adapt_on == (ADAPT ? 1u : 0u));
-#ifndef BPM_STAMPS
-        __builtin_assume(a_in.stamps == nullptr);
-#endif
-        if (!SHARD) { __builtin_assume(a_in.lo == 0); __builtin_assume(a_in.L.world == 1); }
-        __builtin_assume(a_in.epsilon > 0.0);
-        __builtin_assume(a_in.perm_tab != nullptr); __builtin_assume(a_in.inv_tab != nullptr);
-        if (ALGO == ALGO_DREAM) { __builtin_assume(a_in.u_epsilon > 0.0); __builtin_assume(a_in.n_cr == 3); }
-    }
+    // FRONT_CT: the PLAN flavours of one wavefront per chain with one coordinate pair per lane -- records are the only path there (choose_flavour), and the
+    // wavefront requests its rows before it reads anything else of the argument block (plan_front)
+    constexpr bool FRONT_CT = LPC == WAVE && DPL == 2 && (HOT == 1 || HOT == 3 || HOT == 5);
 #ifdef BPM_PRELOAD
     if (HOT) { __builtin_assume(pl_mode == 0u); __builtin_assume((pl_plan != nullptr) == !NOPLAN); }
 #else
-    const uint32_t* pl_plan = a.rec_tab;
-    const uint32_t pl_upd_off = a.rec_off, pl_n_items = a.n_items, pl_mode = a.mode;
+    // (what the private copy below holds in these fields, read here: the planned front needs them before the copy is made)
+    const uint32_t* pl_plan = (HOT && NOPLAN) ? nullptr : a_in.rec_tab;
+    const uint32_t pl_upd_off = a_in.rec_off, pl_n_items = a_in.n_items, pl_mode = HOT ? 0u : a_in.mode;
 #endif
     constexpr int BLK = block_for_hot(LPC, HOT, DPL);
     // CRP: this flavour sums its updates' CR statistics itself (level 1 of the CR reduction); with one wavefront per chain the 16 wavefronts of the
@@ -1474,6 +1515,127 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bpm_rt0)::"memory");
     BPM_STAMP(0);
 #endif
+    PlanFront<DPL, (NP > 0 ? NP : 1)> fr;
+    uint32_t f_c = 0u;
+    const uint32_t* f_rec = nullptr;
+    Layout f_L = {};
+    double *f_ll = nullptr, *f_wm = nullptr, *f_w2 = nullptr;
+    const double *f_crs = nullptr, *f_tp = nullptr, *f_gt = nullptr;
+    uint32_t* f_acc = nullptr;
+    unsigned long long* f_cnt = nullptr;
+    uint32_t f_lo = 0u;
+    typename Target<TARGET, LPC, DPL>::Consts tc_front;
+    if constexpr (FRONT_CT) {
+        // ONE scalar round trip: the record and every field of the argument block the update reads on its way to the accept test leave together, over a
+        // memory system that is still idle.  (A scalar load issued BEHIND the row requests queues behind 7 KB of row traffic per wavefront, sixteen
+        // wavefronts per CU: measured 1.3 us instead of 0.6, and every scalar wait waits for all of them.)  The fields are inputs of the empty statements
+        // the row stride and the row width pass through: live where the row addresses are made.  Not `volatile`, no memory clobber: a scalar load behind
+        // such a statement becomes a vector load.
+        if (w < pl_n_items) {
+            f_L = a_in.L;
+            if (SHARD) __builtin_assume(f_L.world > 1u); else f_L.world = 1;      // (choose_flavour: a rank of a world)
+            // (a rank of a world reads all of the Layout: its two runs of words as whole vectors, padding included, so that the wide loads the compiler
+            // makes of them have no dead register for another load in flight to be given)
+            typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+            typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+            u32x4_a4 lw4 = {0u, 0u, 0u, 0u};
+            u32x2_a4 lw2 = {0u, 0u};
+            if (SHARD) {
+                lw4 = *reinterpret_cast<const u32x4_a4*>(&a_in.L.n_local);
+                lw2 = *reinterpret_cast<const u32x2_a4*>(&a_in.L.magic);
+                f_L.n_local = lw4.x; f_L.ld = lw4.y; f_L.dim = lw4.z; f_L.world = lw4.w; f_L.magic = lw2.x;
+                __builtin_assume(f_L.world > 1u);
+            }
+            f_ll = a_in.ll; f_acc = a_in.acc_count; f_crs = a_in.cr_state; f_tp = a_in.tparams; f_gt = a_in.gamma_tab; f_cnt = a_in.counters;
+            if (ADAPT) { f_wm = a_in.w_mean; f_w2 = a_in.w_m2; }
+            if (SHARD) f_lo = a_in.lo;
+            const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pl_upd_off + w));
+            f_rec = pl_plan + (uint32_t)(pos * PLAN_WORDS);
+            bpm_u32x16 rv = plan_record(f_rec);
+            // (the whole record passes through the statement: all sixteen words stay live up to it, so no register of the wide load is handed to another load
+            // first, and every row address comes after it; the scheduling barrier keeps the small loads below from being issued, and waited for, ahead of it)
+#ifndef BPM_STAMPS      // (the stamp build: its loads behind the entry stamp are vector loads, no operands for these statements; it keeps the barrier)
+#define BPM_FRONT_ALL "s"(f_L.G), "s"(f_L.ld), "s"(f_L.dim), "s"(f_ll), "s"(f_acc), "s"(f_tp), "s"(f_cnt), "s"(a_in.seed), "s"(a_in.t), "s"(a_in.k), "s"(a_in.upd_off), \
+                      "s"(a_in.epsilon), "s"(a_in.wt), "s"(a_in.hist_by_pos), "s"(a_in.hist_row), "s"(a_in.llhist_row)
+#define BPM_FRONT_DREAM "s"(f_crs), "s"(f_gt), "s"(a_in.u_epsilon), "s"(a_in.thr[0]), "s"(a_in.thr[1]), "s"(a_in.thr[2]), "s"(a_in.thr[3])
+            if (ALGO == ALGO_DREAM && ADAPT) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM, "s"(f_wm), "s"(f_w2), "s"(a_in.cr_gate), "s"(a_in.hist_len));
+            else if (ALGO == ALGO_DREAM && SHARD) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM, "s"(f_lo), "s"(lw4), "s"(lw2));
+            else if (ALGO == ALGO_DREAM) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM);
+            else if (SHARD) asm("" : "+s"(rv) : BPM_FRONT_ALL, "s"(a_in.gamma_demc), "s"(a_in.p_snooker), "s"(a_in.M), "s"(a_in.pool_off), "s"(f_lo), "s"(lw4), "s"(lw2));
+            else asm("" : "+s"(rv) : BPM_FRONT_ALL, "s"(a_in.gamma_demc), "s"(a_in.p_snooker), "s"(a_in.M), "s"(a_in.pool_off));
+#undef BPM_FRONT_ALL
+#undef BPM_FRONT_DREAM
+#endif
+            __builtin_amdgcn_sched_barrier(0);
+            // the chain's own scalars, the target's parameters and the lane's entries of the gamma table just AHEAD of the rows: a few bytes each, first in
+            // the queue, in by the time the lanes' Philox blocks are done
+            f_c = rv[0];
+            fr.ll_cur = f_ll[f_c - f_lo];
+            fr.acc_prev = f_acc[f_c - f_lo];
+            if (ALGO == ALGO_DREAM) {
+#pragma unroll
+                for (int m = 0; m < 3; ++m) fr.pcr[m] = f_crs[m];
+#pragma unroll
+                for (int u = 0; u < DPL; ++u) {      // (index clamped to the table's last entry: make_proposal zeroes the lanes beyond dim by a select on the value)
+                    const uint32_t gi = (uint32_t)(q + u * WAVE);
+                    fr.gl[u] = f_gt[gi <= f_L.dim ? gi : f_L.dim];
+                }
+            }
+            tc_front = Target<TARGET, LPC, DPL>::load(q, f_L.dim, f_tp);
+            plan_front<DPL, NP>(f_L, rv, q, fr);
+            // (... and waited for HERE, behind the row requests, at one point: the chain id passes through the statement, the draws come after it.  Left to
+            // the compiler the target's scalars were loaded where ln_like is evaluated: behind the rows' traffic, and every later scalar wait waited for them.)
+#ifndef BPM_STAMPS      // (the stamp build waits at its stamps; its scalar loads behind a stamp are vector loads, no operands for this statement)
+            if constexpr (ALGO == ALGO_DREAM && TARGET == TARGET_GAUSS)
+                asm("" : "+s"(f_c) : "s"(fr.ll_cur), "s"(fr.acc_prev), "s"(fr.pcr[0]), "s"(fr.pcr[1]), "s"(fr.pcr[2]), "s"(tc_front.c0), "s"(tc_front.a), "s"(tc_front.b));
+            else if (ALGO == ALGO_DREAM) asm("" : "+s"(f_c) : "s"(fr.ll_cur), "s"(fr.acc_prev), "s"(fr.pcr[0]), "s"(fr.pcr[1]), "s"(fr.pcr[2]));
+            else if constexpr (TARGET == TARGET_GAUSS) asm("" : "+s"(f_c) : "s"(fr.ll_cur), "s"(fr.acc_prev), "s"(tc_front.c0), "s"(tc_front.a), "s"(tc_front.b));
+            else asm("" : "+s"(f_c) : "s"(fr.ll_cur), "s"(fr.acc_prev));
+#endif
+#ifdef BPM_STAMPS
+            BPM_STAMP(7);
+#endif
+        } else if (!CRP) {
+            return;
+        }
+    }
+    PhaseArgs a_hot;
+    if (COPY) {
+        if constexpr (FRONT_CT) {
+            a_hot = a_in;
+            a_hot.L = f_L; a_hot.ll = f_ll; a_hot.acc_count = f_acc; a_hot.cr_state = f_crs; a_hot.tparams = f_tp; a_hot.gamma_tab = f_gt; a_hot.counters = f_cnt;      // (in registers already)
+            if (ADAPT) { a_hot.w_mean = f_wm; a_hot.w_m2 = f_w2; }
+            if (SHARD) a_hot.lo = f_lo;
+        } else
+        a_hot = a_in;
+        a_hot.mode = 0u; trace_set(a_hot, nullptr, nullptr, nullptr); a_hot.pack = nullptr;
+        a_hot.replay = 0u; a_hot.x_next = nullptr; a_hot.adapt_on = ADAPT ? 1u : 0u;
+#ifndef BPM_STAMPS
+        a_hot.stamps = nullptr;
+#else
+        if (SHARD) a_hot.stamps = nullptr;
+#endif
+        if (!ADAPT) a_hot.cr_fold_part = nullptr;
+        if (!SHARD) { a_hot.accbits = nullptr; a_hot.lo = 0; a_hot.L.world = 1; a_hot.acc_by_item = 0u; a_hot.n_peers = 0u; a_hot.peer_tab = nullptr; }
+        if (ALGO == ALGO_DREAM) a_hot.n_cr = 3;
+        if (NOPLAN) { a_hot.plan = nullptr; a_hot.rec_tab = nullptr; }
+    }
+    const PhaseArgs& a = COPY ? a_hot : a_in;
+    static_assert(!FRONT_CT || COPY, "the planned front reads the argument block through the private copy");
+    if (HOT) {
+        __builtin_assume(a_in.mode == 0u); __builtin_assume(a_in.pack == nullptr);
+#ifdef BPM_TEST_HOOKS
+        __builtin_assume(a_in.trace_i32 == nullptr);
+#endif
+        __builtin_assume(a_in.x_next == nullptr); __builtin_assume(a_in.adapt_on == (ADAPT ? 1u : 0u));
+#ifndef BPM_STAMPS
+        __builtin_assume(a_in.stamps == nullptr);
+#endif
+        if (!SHARD) { __builtin_assume(a_in.lo == 0); __builtin_assume(a_in.L.world == 1); }
+        __builtin_assume(a_in.epsilon > 0.0);
+        __builtin_assume(a_in.perm_tab != nullptr); __builtin_assume(a_in.inv_tab != nullptr);
+        if (ALGO == ALGO_DREAM) { __builtin_assume(a_in.u_epsilon > 0.0); __builtin_assume(a_in.n_cr == 3); }
+    }
     pin_args<LPC>(a);
     uint32_t c;
     bool active;
@@ -1481,7 +1643,11 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     bool run = true;                     // (false: an idle wavefront of a CRP workgroup -- it only joins the barrier)
     double cr_d = 0.0;
     int cr_i = -1;
-    if (LPC == WAVE && pl_plan && !(CRP && w >= pl_n_items)) {
+    if constexpr (FRONT_CT) {
+        active = w < pl_n_items;
+        c = f_c;
+        rec = f_rec;
+    } else if (LPC == WAVE && pl_plan && !(CRP && w >= pl_n_items)) {
         // the update's record (by position in shuffle order) carries the chain id: wavefront-uniform scalar loads
         active = w < pl_n_items;
         if (!active) return;
@@ -1542,7 +1708,7 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     }
   if (run) {
     if (LPC == WAVE) c = __builtin_amdgcn_readfirstlane(c);   // wavefront-uniform: header draws and Feistel walks go to the scalar unit
-    const typename Target<TARGET, LPC, DPL>::Consts tc = Target<TARGET, LPC, DPL>::load(q, a.L.dim, a.tparams);
+    const typename Target<TARGET, LPC, DPL>::Consts tc = FRONT_CT ? tc_front : Target<TARGET, LPC, DPL>::load(q, a.L.dim, a.tparams);
     Work<DPL> wk;
     wk.item = w;
     wk.pos_own = a.upd_off + (active ? w : 0u);
@@ -1562,9 +1728,9 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
         auto early = [tc, q, dim_early, lean_early](Work<DPL>& k) { if (lean_early) k.ll_cur = Target<TARGET, LPC, DPL>::eval(k.x, q, dim_early, tc); };
         make_proposal<ALGO, LPC, DPL, NP, (LEAN_CT ? 0 : 2)>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, early, pcr_fold);
     } else if constexpr (CRP) {
-        make_proposal<ALGO, LPC, DPL, NP>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, NoEarly(), pcr_fold);
-    } else {      // (one wavefront per chain: exactly the call of rounds 1-3)
-        make_proposal<ALGO, LPC, DPL, NP>(a, c, active, q, cw, s_part, wk, rec, stamp_arg);
+        make_proposal<ALGO, LPC, DPL, NP, 1, NoEarly, FRONT_CT>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, NoEarly(), pcr_fold, &fr);
+    } else {      // (one wavefront per chain: the call of rounds 1-3, with the planned front's record and rows where the flavour has one)
+        make_proposal<ALGO, LPC, DPL, NP, 1, NoEarly, FRONT_CT>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, NoEarly(), PcrGiven(), &fr);
     }
     const double ll_prop = Target<TARGET, LPC, DPL>::eval(wk.p, q, a.L.dim, tc);
     BPM_STAMP(5);

@@ -68,7 +68,10 @@ def main():
     mhz = np.median(cyc[ns > 0] / ns[ns > 0]) * 1e3
     say("shader clock (median of s_memtime / 100 MHz counter over wavefront lifetimes): %.0f MHz" % mhz)
     say("per wavefront, shader cycles (s_memtime):")
-    seg = [("entry -> record in hand (slot 3)", 0, 3), ("record in hand -> rows requested (slot 1 <- 7)", 3, 1),
+    # (a build whose planned front requests the rows first stamps "rows requested" AHEAD of slot 3 -- the header words are read out of the record behind
+    # the row requests and the wait for everything else -- so there the second line is negative and the first one reads "entry -> all scalars in")
+    seg = [("entry -> rows requested (slot 1 <- 7)", 0, 1),
+           ("entry -> record in hand (slot 3)", 0, 3), ("record in hand -> rows requested (slot 1 <- 7)", 3, 1),
            ("rows requested -> proposal built: rows in (slot 4)", 1, 4), ("proposal built -> proposal ln-like done (slot 5)", 4, 5),
            ("ln-like done -> end of finish_update (slot 6)", 5, 6), ("rows requested -> end of finish_update", 1, 6),
            ("entry -> end of finish_update", 0, 6)]
