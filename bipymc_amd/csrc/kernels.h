@@ -269,17 +269,35 @@ __host__ __device__ __forceinline__ void trace_set(PhaseArgs&, int32_t*, double*
 // Sum over the LPC lanes of a chain subgroup, result in every lane of the subgroup.
 // Cross-lane moves are DPP (no LDS traffic, ~8 cycles each instead of a ds_bpermute round trip):
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror give the sum of each row of
-// 16 lanes; a full wavefront then combines its four row sums through v_readlane (scalar operands).
+// 16 lanes; a full wavefront then combines its four row sums with two more DPP steps (row_sums_f64).
 // Must be called with all 64 lanes active (it is: subgroups never diverge around a reduction).
+// Every DPP move here is a v_mov_b32_dpp WITHOUT an `old` operand (mov_dpp, bound_ctrl on): under these controls with full row and bank masks
+// every lane that is read afterwards has a valid source lane, so nothing of the destination's former value survives -- as update_dpp(0, ...) with
+// bound_ctrl off the compiler had to write that zero into the destination ahead of every step (one v_mov_b32 v, 0 per DPP move).
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) {
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true);
+}
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+    const int lo = dpp_i32<CTRL>(__double2loint(v));
+    const int hi = dpp_i32<CTRL>(__double2hiint(v));
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
                             __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+// The four row sums r0 .. r3 of a full wavefront (every lane of row k holds rk) -> (r0 + r1) + (r2 + r3) as a wavefront-uniform value.
+// row_bcast:15 hands lane 15 of every row to the row above it: rows 1 and 3 then hold r1 + r0 and r3 + r2 (rows 0 and 2 hold something nobody
+// reads: row 0 has no source and adds the 0 of bound_ctrl).  row_bcast:31 hands lane 31 to rows 2 and 3: row 3 holds (r3 + r2) + (r1 + r0), the
+// same two-level tree as four v_readlane pairs summed on the way -- f64 addition commutes, so the same bits -- for 4 DPP moves, 2 additions and
+// ONE v_readlane pair (lane 63) instead of 4 pairs, 4 moves of a scalar pair back into VGPRs and 3 additions.
+constexpr int DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
+__device__ __forceinline__ double row_sums_step1_f64(double v) { return v + dpp_f64<DPP_ROW_BCAST15>(v); }
+__device__ __forceinline__ double row_sums_step2_f64(double v) { return v + dpp_f64<DPP_ROW_BCAST31>(v); }
+__device__ __forceinline__ double row_sums_f64(double v) {
+    return readlane_f64(row_sums_step2_f64(row_sums_step1_f64(v)), WAVE - 1);
 }
 template <int LPC>
 __device__ __forceinline__ double gsum(double v) {
@@ -293,7 +311,7 @@ __device__ __forceinline__ double gsum(double v) {
         v += dpp_f64<0x140>(v);    // row_mirror
     }
     if (LPC == 32) v += __shfl_xor(v, 16);
-    if (LPC == 64) v = (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+    if (LPC == 64) v = row_sums_f64(v);
     return v;
 }
 // Two sums at once, step by step: the same tree and order for each as gsum (same bits); a DPP step has to wait for the addition before it,
@@ -315,25 +333,27 @@ __device__ __forceinline__ void gsum2(double& v, double& w) {
     }
     if (LPC == 32) { const double vs = __shfl_xor(v, 16), ws = __shfl_xor(w, 16); v += vs; w += ws; }
     if (LPC == 64) {
-        const double va = readlane_f64(v, 0) + readlane_f64(v, 16), wa = readlane_f64(w, 0) + readlane_f64(w, 16);
-        const double vb = readlane_f64(v, 32) + readlane_f64(v, 48), wb = readlane_f64(w, 32) + readlane_f64(w, 48);
-        v = va + vb; w = wa + wb;
+        v = row_sums_step1_f64(v); w = row_sums_step1_f64(w);
+        v = row_sums_step2_f64(v); w = row_sums_step2_f64(w);
+        v = readlane_f64(v, WAVE - 1); w = readlane_f64(w, WAVE - 1);
     }
 }
 template <int LPC>
 __device__ __forceinline__ int gsum_i(int v) {
     if (LPC >= 4) {
-        v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
+        v += dpp_i32<0xB1>(v);
+        v += dpp_i32<0x4E>(v);
     }
     if (LPC >= 16) {
-        v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);
-        v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);
+        v += dpp_i32<0x141>(v);
+        v += dpp_i32<0x140>(v);
     }
     if (LPC == 32) v += __shfl_xor(v, 16);
-    if (LPC == 64)
-        v = (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-            (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+    if (LPC == 64) {                            // (the row sums as in row_sums_f64: integer addition is exact, any order gives the same count)
+        v += dpp_i32<DPP_ROW_BCAST15>(v);
+        v += dpp_i32<DPP_ROW_BCAST31>(v);
+        v = __builtin_amdgcn_readlane(v, WAVE - 1);
+    }
     return v;
 }
 
@@ -694,7 +714,7 @@ __device__ __forceinline__ void box_muller_pair_f32(uint32_t w1, uint32_t w2, do
 // Lane K of every quad (4 consecutive lanes) to all four lanes of that quad: one DPP move, no LDS.
 template <int K>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, K * 0x55, 0xF, 0xF, false);
+    return (uint32_t)dpp_i32<K * 0x55>((int)v);
 }
 
 // Partner chains of chain c (pool positions -> global ids through the generation's bijection): in registers when
@@ -764,11 +784,28 @@ __device__ __forceinline__ void plan_front(const Layout& L, const bpm_u32x16 rv,
     static_assert(PLAN_WORDS == 16 && DPL == 2, "one 64-byte record, one 16-byte load per lane and row");
 #pragma unroll
     for (int i = 0; i < PLAN_WORDS; ++i) fr.rec[i] = rv[i];
-    load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[0]), q, L.ld, fr.x);
+    // Every row's base address is made on the scalar unit (the ids are scalars) and the 1 + 2 NP loads share ONE 32-bit lane offset
+    // (global_load_dwordx4 v, v_off, s[base]).  Left alone the compiler adds the lane offset to G once as a 64-bit vector pair and then every
+    // partner's row offset to THAT: a v_lshl_add_u64 and an address VGPR pair per partner row, ahead of the row requests.  The empty statements
+    // keep each base a scalar of its own; behind them the pointers are named global again (nothing else tells the compiler so: it would load `flat`).
+    typedef const __attribute__((address_space(1))) bpm_d2v* grow_t;
+    const double* base[1 + 2 * (NP > 0 ? NP : 1)];
+    base[0] = row_ptr(L, fr.rec[0]);
+#pragma unroll
+    for (int i = 0; i < 2 * NP; ++i) base[1 + i] = row_ptr(L, fr.rec[5 + i]);
+#ifndef BPM_STAMPS      // (the stamp build's record is a vector load: no scalar operands)
+#pragma unroll
+    for (int i = 0; i < 1 + 2 * NP; ++i) asm("" : "+s"(base[i]));
+#endif
+    const uint32_t last = (L.ld >> 1) - 1u, pi = (uint32_t)q < last ? (uint32_t)q : last;      // (load_row_all's clamp to the row's last pair)
+    bpm_d2v t = ((grow_t)base[0])[pi];
+    fr.x[0] = t.x; fr.x[1] = t.y;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[5 + 2 * p]), q, L.ld, fr.ra[p]);
-        load_row_all<WAVE, DPL>(row_ptr(L, fr.rec[5 + 2 * p + 1]), q, L.ld, fr.rb[p]);
+        t = ((grow_t)base[1 + 2 * p])[pi];
+        fr.ra[p][0] = t.x; fr.ra[p][1] = t.y;
+        t = ((grow_t)base[2 + 2 * p])[pi];
+        fr.rb[p][0] = t.x; fr.rb[p][1] = t.y;
     }
     __builtin_amdgcn_sched_barrier(0);      // nothing the scheduler finds further down is issued ahead of the row requests
 }
@@ -887,7 +924,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         for (int i = 0; i < 2 * NP; ++i) part.r[i] = fr->rec[5 + i];
         if (!dims_late) {
 #pragma unroll
-            for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
+            for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
         }
     } else if (planned) {
         h0.x = rec[1]; h0.y = rec[2]; h0.z = rec[3]; h0.w = rec[4];
@@ -897,13 +934,13 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         }
         if (!dims_late) {
 #pragma unroll
-            for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
+            for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
         }
     } else if (merged) {
         const uint32_t uq = (uint32_t)q, hdr_lane = npairs + 2u * (uint32_t)NP;
         const uint32_t pidx = uq - npairs;                       // partner index for lanes [npairs, hdr_lane)
         const uint32_t slot = uq < npairs ? SLOT_DIM0 + uq : (uq < hdr_lane ? SLOT_PAIR0 + (pidx >> 2) : SLOT_HDR0);
-        const u32x4 wb = chain_block(a.seed, c, a.t, slot);
+        const u32x4 wb = chain_block<true>(a.seed, c, a.t, slot);
         wpair[0] = wb;
         h0.x = (uint32_t)__builtin_amdgcn_readlane((int)wb.x, hdr_lane);
         h0.y = (uint32_t)__builtin_amdgcn_readlane((int)wb.y, hdr_lane);
@@ -922,9 +959,9 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #pragma unroll
         for (int i = 0; i < 2 * NP; ++i) part.r[i] = (uint32_t)__builtin_amdgcn_readlane((int)mine, npairs + i);
     } else if (QUAD) {
-        wpair[0] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)q);
+        wpair[0] = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)q);
         // second evaluation: lane 0 (and 3) the header block, lanes 1 and 2 the two pair-selection blocks
-        const u32x4 wb = chain_block(a.seed, c, a.t, q == 1 ? SLOT_PAIR0 : (q == 2 ? SLOT_PAIR0 + 1u : SLOT_HDR0));
+        const u32x4 wb = chain_block<true>(a.seed, c, a.t, q == 1 ? SLOT_PAIR0 : (q == 2 ? SLOT_PAIR0 + 1u : SLOT_HDR0));
         h0.x = quad_bcast<0>(wb.x); h0.y = quad_bcast<0>(wb.y); h0.z = quad_bcast<0>(wb.z); h0.w = quad_bcast<0>(wb.w);
         uint32_t i0 = 0, i1 = 0, i2 = 0, i3 = 0;
         if (q == 1 || q == 2) {                                    // lane 1: pairs 0 and 1, lane 2: pair 2 (partner_pos's layout)
@@ -940,9 +977,9 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         part.r[4] = quad_bcast<2>(i0); part.r[5] = quad_bcast<2>(i1);
     } else {
         // one header block: (select16|gamma16, forced dim [DREAM] / snooker gamma [DE-MC], accept hi, accept lo)
-        h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
+        h0 = chain_block<(LPC < WAVE)>(a.seed, c, a.t, SLOT_HDR0);      // (several chains per wavefront: the chain differs per lane)
 #pragma unroll
-        for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
+        for (int u = 0; u < DPL / 2; ++u) wpair[u] = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)(q + u * LPC));
         if (FAST) {
 #pragma unroll
             for (int i = 0; i < 2 * NP; ++i) part.r[i] = pos_to_chain(a, a.pool_off + partner_pos(a, c, (uint32_t)i, 2u * NP));
@@ -1005,7 +1042,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         }
     }
     if (!FRONT) BPM_STAMP(7);      // (the planned front stamped its own row requests)
-    if (dims_late) wpair[0] = chain_block(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)q);      // overlaps with the row fetches
+    if (dims_late) wpair[0] = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + (uint32_t)q);      // overlaps with the row fetches
     if (DREAM) early(wk);
 
     // ---- per-pair draws: one Philox block per coordinate pair
@@ -1935,8 +1972,8 @@ __global__ __launch_bounds__(block_for(LPC)) void phase_commit_kernel(const Phas
 constexpr int CR_L1_THREADS = 256;
 template <int G1, int J>
 __device__ __forceinline__ int cr_bcast_i(int v) {          // lane J of every group of G1 consecutive lanes, to all lanes of the group
-    if (G1 == 4) return __builtin_amdgcn_update_dpp(0, v, J * 0x55, 0xF, 0xF, false);              // quad_perm [J, J, J, J]
-    if (G1 == 16) return __builtin_amdgcn_update_dpp(0, v, 0x150 + J, 0xF, 0xF, false);            // row_newbcast:J
+    if (G1 == 4) return dpp_i32<J * 0x55>(v);              // quad_perm [J, J, J, J]
+    if (G1 == 16) return dpp_i32<0x150 + J>(v);            // row_newbcast:J
     return __builtin_amdgcn_readlane(v, J);
 }
 // lane k of the chunk sums CR value k (and k + 4 where a chunk has only four lanes): one compare and one conditional add per position and lane

@@ -117,7 +117,7 @@ __device__ __forceinline__ void wide_pair_proposal(const PhaseArgs& a, const Wid
     constexpr bool DREAM = ALGO == ALGO_DREAM;
     const uint32_t j0 = 2u * pi;
     const bool two = j0 + 1u < U.dim;
-    const u32x4 wj = chain_block(a.seed, c, a.t, SLOT_DIM0 + pi);
+    const u32x4 wj = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + pi);
     double en0 = 0.0, en1 = 0.0, eu0 = 0.0, eu1 = 0.0;
     mbits = 0u;
     if (valid) {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
                     const uint32_t j0 = 2u * pi;
                     bool b0 = false, b1 = false;
                     if (j0 < U.dim) {
-                        const u32x4 wj = chain_block(a.seed, c, a.t, SLOT_DIM0 + pi);
+                        const u32x4 wj = chain_block<true>(a.seed, c, a.t, SLOT_DIM0 + pi);
                         b0 = (wj.x >> 16) <= U.thr;
                         b1 = (j0 + 1u < U.dim) && (wj.x & 0xFFFFu) <= U.thr;
                     }

@@ -62,34 +62,60 @@ BPM_HD uint32_t mulhi32(uint32_t a, uint32_t b) {
 #endif
 }
 
+// a ^ b ^ c of per-lane words.  gfx950 has a three-input bitwise instruction (v_bitop3_b32, truth table 0x96 = odd parity) which the compiler does not
+// form from two xors by itself; on the device path for that target the builtin names it: one vector instruction per Philox word and round instead
+// of two dependent ones.  Every other target, and the host, xor twice.
+BPM_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 // Philox4x32-10 (Salmon et al., SC'11; Random123 constants).
-BPM_HD u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+// LANES: the caller's block differs from lane to lane (the slot, or the chain): rounds 2 .. 9 mix with xor3.  A block that is the same for the whole
+// wavefront (one wavefront per chain: header, pair and snooker blocks) is evaluated on the scalar unit, which has no three-input form -- there the
+// builtin would drag the whole evaluation onto the vector unit -- and so are the uniform parts of rounds 0 and 1 of a per-lane block (the words that
+// hold the chain id and the generation, and their products): those stay plain xors.  Same words either way.
+template <bool LANES>
+BPM_HD u32x4 philox4x32_10_t(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
     constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)M0 * (uint64_t)c0, p1 = (uint64_t)M1 * (uint64_t)c2;   // one 32x32->64 multiply each
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
         const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        const uint32_t n0 = (LANES && r >= 2) ? xor3(hi1, c1, k0) : (hi1 ^ c1 ^ k0), n2 = (LANES && r >= 2) ? xor3(hi0, c3, k1) : (hi0 ^ c3 ^ k1);
         c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
         k0 += W0; k1 += W1;
     }
     return u32x4{c0, c1, c2, c3};
 }
-
-// rocRAND addressing: key = seed words, counter.xy = block, counter.zw = subsequence.
-BPM_HD u32x4 philox_block(uint64_t seed, uint64_t subseq, uint64_t blk) {
-    return philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)subseq, (uint32_t)(subseq >> 32),
-                         (uint32_t)seed, (uint32_t)(seed >> 32));
+BPM_HD u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    return philox4x32_10_t<false>(c0, c1, c2, c3, k0, k1);
 }
 
+// rocRAND addressing: key = seed words, counter.xy = block, counter.zw = subsequence.
+template <bool LANES = false>
+BPM_HD u32x4 philox_block(uint64_t seed, uint64_t subseq, uint64_t blk) {
+    return philox4x32_10_t<LANES>((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)subseq, (uint32_t)(subseq >> 32),
+                                  (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// LANES: see philox4x32_10_t -- true where the slot or the chain differs between the lanes of a wavefront (device code only; the words are the same)
+template <bool LANES = false>
 BPM_HD u32x4 chain_block(uint64_t seed, uint64_t chain_id, uint64_t t, uint32_t slot) {
 #if defined(BPM_TEST_HOOKS) && defined(BPM_FAKE_DRAWS) && defined(__HIP_DEVICE_COMPILE__)     // ablation builds only (tools/): what do the draws cost?
     uint32_t x = (uint32_t)chain_id * 0x9e3779b9u + (uint32_t)t * 0x85ebca6bu + slot * 0xc2b2ae35u + (uint32_t)seed;
     x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
     return u32x4{x, x * 0x297a2d39u, x ^ 0x5bd1e995u, x + 0x7f4a7c15u};
 #else
-    return philox_block(seed, chain_id, (t << SLOT_BITS) | (uint64_t)slot);
+    return philox_block<LANES>(seed, chain_id, (t << SLOT_BITS) | (uint64_t)slot);
 #endif
 }
 
