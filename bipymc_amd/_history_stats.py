@@ -7,6 +7,9 @@ The contract they share.  The window is the super-chain rows >= n_burn, param_es
 g); it needs keep_history=True.  Each call is collective: every rank calls it with the same arguments, and every rank gets the same bits,
 because the ranks' parts travel through one allgather and are merged in rank order.
 
+With a thinned history (`thin=k` on the sampler, or after thin_history) the rows are the STORED rows -- every k-th generation: n_burn, `every`,
+lags, tau and ESS count stored rows / stored draws, and n_burn = n_chains * r leaves out the first r stored rows (r * k generations).
+
 A host class provides two hooks: _stats_engine(who) -> its engine (or the error of a sampler that has not run, in the name of the method
 `who`), and _stats_allgather(obj) -> [obj of every rank] in rank order.
 """
@@ -28,7 +31,7 @@ def empty_window(who, n_burn):
 class HistoryStatistics(object):
     def convergence_diagnostics(self, n_burn=0, max_lag=None):
         """Split-chain R-hat and effective sample size per coordinate; the window starts at the first whole generation after n_burn.
-        max_lag bounds the autocorrelation lags read (ess_capped says where it ended the sum).  -> diagnostics.ConvergenceDiagnostics"""
+        Over a thinned history n_burn, lags and tau count stored rows and ESS stored draws.  max_lag bounds the autocorrelation lags read (ess_capped says where it ended the sum).  -> diagnostics.ConvergenceDiagnostics"""
         from . import diagnostics as _diag
         eng = self._stats_engine("convergence_diagnostics")
         g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
@@ -36,7 +39,7 @@ class HistoryStatistics(object):
 
     def convergence_diagnostics_rank(self, n_burn=0, max_lag=None, prob=(0.05, 0.95)):
         """The rank-normalized split-R-hat, bulk-ESS and tail-ESS of Vehtari et al. (2021), as Stan and ArviZ report them, over
-        convergence_diagnostics' window: r_hat = max(bulk, tail) sees chains that differ in scale as well as in location and is defined for
+        convergence_diagnostics' window (n_burn, lags and ESS count stored rows / stored draws of a thinned history): r_hat = max(bulk, tail) sees chains that differ in scale as well as in location and is defined for
         heavy tails; ess_tail = min over the indicators x <= np.quantile(prob) says how well those quantiles are estimated.  Pooled ranks,
         normal scores and indicators are written into one scratch handle (four fills, each read by the classic pipeline), which costs the
         window's rows x (dim rounded up to even + 1) x 8 bytes plus the sort's scratch while the call runs.  Single rank only.

@@ -98,6 +98,10 @@ SIGNATURES = {
     "bpm_get_history": (C.c_int, [_H, C.c_int64, C.c_int64, _dp]),
     "bpm_get_loglike_history": (C.c_int, [_H, C.c_int64, C.c_int64, _dp]),
     "bpm_reserve_history": (C.c_int, [_H, C.c_int64]),
+    "bpm_set_history_thin": (C.c_int, [_H, C.c_int32]),
+    "bpm_thin_history": (C.c_int, [_H, C.c_int32]),
+    "bpm_set_history_thinned": (C.c_int, [_H, C.c_int64, _dp, _dp, C.c_int32, C.c_int64]),
+    "bpm_get_history_thin": (C.c_int, [_H, _P(C.c_int64)]),
     "bpm_get_stats": (C.c_int, [_H, _P(BpmStats)]),
     "bpm_set_adapt_state": (C.c_int, [_H, _dp, _dp, _dp, C.c_int64]),
     "bpm_eval_loglike": (C.c_int, [_H, _dp, C.c_int32, _dp]),
@@ -135,6 +139,7 @@ TEST_SIGNATURES = {
     "bpm_debug_outlier_select": (C.c_int, [_H, _dp, _dp]),
     "bpm_debug_time_kernels": (C.c_int, [_H, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     "bpm_debug_flavour_counts": (C.c_int, [_H, _P(C.c_int64)]),
+    "bpm_debug_get_welford": (C.c_int, [_H, _dp, _dp]),
 }
 
 _lib = None

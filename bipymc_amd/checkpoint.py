@@ -9,14 +9,18 @@ write / read exactly that layout, tried in this order:
   3. a NumPy `.npz` archive with the same keys (`chains/chain_id_<i>`) and shapes, when neither is available or the path ends in `.npz`.
 
 The adaptation state the reference forgets (p_cr, delta_m, n_cr_updates, generation counter, seed) goes to the side group
-`/bipymc_amd` (files without it -- the reference's own -- read fine).  `read()` decides by what is ON DISK: an HDF5 signature means
+`/bipymc_amd` (files without it -- the reference's own -- read fine).  A thinned history (DeMcMpi(thin=k)) keeps the reference's layout of the
+chains -- T is then the number of STORED rows -- and adds `thin`, `rows_logical` (1 + generations since initialisation) and `state` (the (N, dim)
+current state, which is not the last row when the last generation was not stored) to that group; a file without them reads as a row per
+generation with state = last row.  `read()` decides by what is ON DISK: an HDF5 signature means
 HDF5, whatever this interpreter could have written.
 """
 import os
 
 import numpy as np
 
-ADAPT_KEYS = ("t_abs", "seed", "p_cr", "delta_m", "n_cr_updates")
+ADAPT_KEYS = ("t_abs", "seed", "p_cr", "delta_m", "n_cr_updates", "thin", "rows_logical", "state")
+_INT_KEYS = ("t_abs", "seed", "thin", "rows_logical")
 
 
 def _have_h5py():
@@ -111,7 +115,7 @@ def read(path, n_chains, dim):
                     chains.append(f.read("/chains/chain_id_" + str(i)))
                 for k in ADAPT_KEYS:
                     if f.exists("/bipymc_amd/" + k):
-                        if k in ("t_abs", "seed"):
+                        if k in _INT_KEYS:
                             adapt[k] = int(f.read("/bipymc_amd/" + k, dtype=np.int64).reshape(-1)[0])
                         else:
                             adapt[k] = f.read("/bipymc_amd/" + k)

@@ -2250,6 +2250,31 @@ __global__ void hist_unpermute_kernel(const PermKey key, uint32_t N, uint32_t ld
     if (p == 0 && llsrc) lldst[c] = llsrc[k];      // (llsrc == nullptr: this row's ln-like was appended by chain)
 }
 
+// Every m-th row of a history buffer gathered into a NEW buffer (bpm_thin_history): dst row r = src row r m, rows of row_v elements V.
+// V = double2 (16-byte loads and stores) where a row is 16-byte aligned -- state rows always, ld is even; ln-like rows when n_local is even --
+// else double.  Grid: x = tiles of THIN_THREADS * THIN_UNR elements of a row, y = kept rows (a block walks rows y, y + gridDim.y, ...).  All
+// loads of a tile are issued before its stores.  The caller guarantees (rows_new - 1) m < the source's rows.
+constexpr int THIN_THREADS = 256, THIN_UNR = 4;
+template <class V>
+__global__ __launch_bounds__(THIN_THREADS) void hist_thin_kernel(const V* __restrict__ src, V* __restrict__ dst, uint64_t row_v, uint64_t rows_new, uint64_t m) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * (THIN_THREADS * THIN_UNR) + threadIdx.x;
+    for (uint64_t r = blockIdx.y; r < rows_new; r += gridDim.y) {
+        const V* srow = src + r * m * row_v;
+        V* drow = dst + r * row_v;
+        V v[THIN_UNR];
+#pragma unroll
+        for (int u = 0; u < THIN_UNR; ++u) {
+            const uint64_t i = i0 + (uint64_t)u * THIN_THREADS;
+            if (i < row_v) v[u] = srow[i];
+        }
+#pragma unroll
+        for (int u = 0; u < THIN_UNR; ++u) {
+            const uint64_t i = i0 + (uint64_t)u * THIN_THREADS;
+            if (i < row_v) drow[i] = v[u];
+        }
+    }
+}
+
 // Records of K consecutive generations in one launch, one thread per (generation, position in shuffle order):
 // everything of an update that depends only on (seed, generation, chain id) -- never on chain states -- so it can
 // be drawn ahead of time: the chain id at that position, its header block and its partner chains (dream.py:62-66;
@@ -2758,8 +2783,9 @@ __global__ __launch_bounds__(WAVE) void outlier_rebuild_kernel(Layout L, const d
 }
 
 // Welford moments of every local chain's history rows [0, rows) recomputed from the history
-// buffer (only needed when adaptation resumes after generations run without it).
-__global__ void welford_rebuild_kernel(const double* hist, uint64_t row_stride, uint64_t n_elem, uint32_t rows, uint32_t ld,
+// buffer (only needed when adaptation resumes after generations run without it).  m2_scale: 1.0, or -- the rows of a thinned history standing
+// for logical / stored times as many -- that ratio (sampler.hip: prepare_generation).
+__global__ void welford_rebuild_kernel(const double* hist, uint64_t row_stride, uint64_t n_elem, uint32_t rows, uint32_t ld, double m2_scale,
                                        double* w_mean, double* w_m2) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_elem) return;
@@ -2772,7 +2798,7 @@ __global__ void welford_rebuild_kernel(const double* hist, uint64_t row_stride, 
         m2 = m2 + d1 * (v - mean);
     }
     w_mean[we] = mean;
-    w_m2[we] = m2;
+    w_m2[we] = m2 * m2_scale;
 }
 
 // chain.py:25-27: state0 = theta_0 + N(0, diag(varepsilon)) for the local block of the exchange buffer

@@ -584,6 +584,9 @@ struct bpm_sampler {
     double* hist_tmp = nullptr;    // one row (n_local * ld) + its ln-likes (n_local): staging of normalize_history
     int64_t hist_rows = 0;     // rows stored (0 when keep_history == 0 and nothing stored)
     int64_t rows_logical = 0;  // len(chain.chain) of the reference: 1 + generations since (re)initialisation
+    // Thinned history (bpm_set_history_thin / bpm_thin_history): stored row r is logical row r * hist_stride, a generation is appended iff the logical
+    // row it produces is a multiple of the stride.  A property of the handle: (re)initialisation keeps it.  1: a row per generation (chain.py:51-54).
+    int64_t hist_stride = 1;
     // running population sums (cfg.running_moments): per history row g the 2 ld doubles [sum_i (x_ij - shift_j) | sum_i (x_ij - shift_j)^2]
     // over this rank's chains, shift = chain 0's state at the last (re)initialisation.  bpm_reduce_moments answers from them when
     // the history is not resident: param_est (demc.py:235-248) of 10^5 generations of config 2 without 660 GB of history.
@@ -892,6 +895,28 @@ static bool state_memory_is_coherent(bpm::DirectQueue* dq, int device) {
 }
 #endif
 
+// ---- thinned histories: the three questions everything below asks -------------------------------------------------------------------
+// stored rows of a history of `rows_logical` logical rows (row 0 = the initial state)
+static inline int64_t stored_rows_of(const bpm_sampler* s, int64_t rows_logical) {
+    return rows_logical < 1 ? 0 : (rows_logical - 1) / s->hist_stride + 1;
+}
+// is the history resident: one stored row for every logical row that is a multiple of the stride
+static inline bool history_resident(const bpm_sampler* s) {
+    return s->cfg.keep_history && s->hist_rows == stored_rows_of(s, s->rows_logical);
+}
+// is the last stored row the current state (it is not after a generation that was not appended)
+static inline bool last_row_is_state(const bpm_sampler* s) {
+    return s->hist_rows >= 1 && s->hist_rows == stored_rows_of(s, s->rows_logical) && (s->rows_logical - 1) % s->hist_stride == 0;
+}
+// does the generation that produces logical row rows_logical append
+static inline bool generation_appends(const bpm_sampler* s) {
+    return s->cfg.keep_history && (s->hist_stride == 1 || s->rows_logical % s->hist_stride == 0);      // (stride 1: no division in the generation loop)
+}
+// the stored rows after n_gens more generations: what a step call reserves
+static inline int64_t stored_rows_after(const bpm_sampler* s, int64_t n_gens) {
+    return s->hist_rows + (stored_rows_of(s, s->rows_logical + std::max<int64_t>(n_gens, 0)) - stored_rows_of(s, s->rows_logical));
+}
+
 // The history's growth rule, stated once: the rows ensure_history(s, rows) allocates (0: it fits) ...
 static int64_t history_growth(const bpm_sampler* s, int64_t rows) {
     if (!s->cfg.keep_history) rows = std::min<int64_t>(rows, 1);
@@ -908,9 +933,10 @@ static int history_growth_bytes(const bpm_sampler* s, int64_t rows, const std::s
     return 0;
 }
 
-static int ensure_history(bpm_sampler* s, int64_t rows) {
-    const int64_t cap = history_growth(s, rows);
+static int ensure_history(bpm_sampler* s, int64_t rows, bool exact = false) {      // (exact: room for `rows` and no more, where the growth rule's would not fit)
+    int64_t cap = history_growth(s, rows);
     if (cap == 0) return 0;
+    if (exact) cap = s->cfg.keep_history ? rows : std::min<int64_t>(rows, 1);
     const bool was_direct = s->dq_active;
     CK(leave_direct(s));              // (kernels in flight on the library's own queue still write the old buffers)
     const size_t row_d = (size_t)s->n_local * s->ld;
@@ -928,6 +954,23 @@ static int ensure_history(bpm_sampler* s, int64_t rows) {
     s->hist_tag.resize((size_t)cap, -1);
     s->dq_active = was_direct && g_disp.dq != nullptr;      // (inside a direct-mode generation: the stream is idle again, go on)
     return 0;
+}
+
+// A reservation somebody asked for (bpm_reserve_history, the head of a step call): the growth is checked against the free memory BEFORE anything
+// is allocated -- the regrow copy needs the old and the new buffer at once -- and the refusal names the ways out.  The handle stays as it was.
+static int reserve_history(bpm_sampler* s, int64_t rows, const char* who) {
+    if (history_growth(s, rows) == 0) return 0;
+    size_t mem_free = 0, mem_total = 0;
+    uint64_t need = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    if (history_growth_bytes(s, rows, who, "chain", mem_free, &need) == 0) return ensure_history(s, rows);
+    // the growth rule's half again on top does not fit: the rows asked for, exactly, before refusing (the message then states what they need)
+    const uint64_t exact = (uint64_t)rows * s->n_local * ((uint64_t)s->ld + 1u) * sizeof(double);
+    if (exact <= mem_free) return ensure_history(s, rows, true);
+    return fail(std::string(who) + ": the chain history of " + std::to_string((long long)rows) + " generations x " + std::to_string(s->n_local) + " chains x (" +
+                std::to_string(s->ld) + " + 1 ln-like) doubles needs " + std::to_string((unsigned long long)(exact >> 20)) + " MiB of device memory; " +
+                std::to_string(mem_free >> 20) + " MiB are free (the old rows stay allocated while they are copied); thin the history (thin=k at construction, "
+                "thin_history / bpm_thin_history on a handle that has one) or run with keep_history=False and running_moments=True");
 }
 
 // ln_like of n rows (ld doubles apart) by the sampler's shipped target, on its stream; false: a host-callback target has no kernel of its own
@@ -982,7 +1025,7 @@ static int normalize_history(bpm_sampler* s, int64_t r0, int64_t r1) {
 
 // ---- shared by the statistics of the history (bpm_reduce_moments ... bpm_trace_chains) -------------------------------------------------
 static int require_resident_history(const bpm_sampler* s, const char* who) {
-    if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+    if (!history_resident(s))
         return fail(std::string(who) + ": needs keep_history=True (a resident history of every generation)");
     return 0;
 }
@@ -1006,7 +1049,7 @@ void HistorySnapshot::take(const bpm_sampler* s) {
 }
 int HistorySnapshot::check(const bpm_sampler* s, const char* who, const char* first_call) const {
     if (!valid) return fail(std::string(who) + ": call " + first_call + " first");
-    if (epoch != s->hist_epoch || tabs != s->t_abs || rows != s->hist_rows || s->hist_rows != s->rows_logical)
+    if (epoch != s->hist_epoch || tabs != s->t_abs || rows != s->hist_rows || !history_resident(s))
         return fail(std::string(who) + ": the history changed since " + first_call + " (a step, set_history or set_state); call it again");
     return 0;
 }
@@ -1592,7 +1635,7 @@ extern "C" int bpm_set_loglike(bpm_handle_t s, const double* ll_local) {
     // the log-like history row of the current state: row 0 after (re)initialisation, the LAST row after a warm start
     // (bpm_set_history with a host-callback target could only leave NaN there; older rows stay NaN: the reference's
     // checkpoint does not store log-likes, chain.py:59-70)
-    if (s->hist_rows >= 1 && s->hist_rows == s->rows_logical)
+    if (last_row_is_state(s))
         HIPCK(hipMemcpyAsync(s->llhist + (size_t)(s->hist_rows - 1) * s->n_local, s->ll, s->n_local * sizeof(double),
                              hipMemcpyDeviceToDevice, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
@@ -1769,14 +1812,18 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
     // dependent dispatches (6 us at cfg2) for nothing, in the first n_cr_gen generations of every fresh run
     s->gen_cr_reduce = adapt_on && s->rows_logical > s->cfg.n_cr_gen;
     if (adapt_on && s->w_rows != s->rows_logical) {
-        if (!s->cfg.keep_history || s->hist_rows != s->rows_logical)
+        if (!history_resident(s))
             return fail("CR adaptation needs the chain history (keep_history=1) to rebuild its moments");
+        // A thinned history holds every hist_stride-th row: the moments of the stored rows, with m2 scaled by logical / stored rows, so that
+        // m2 / rows_logical -- what the in-kernel update, which counts with hist_len = rows_logical, goes on from -- is the variance of the
+        // stored rows ("Deviations").  A row per generation: x 1.0, the same bits as ever.
+        const double m2_scale = s->hist_rows == s->rows_logical ? 1.0 : (double)s->rows_logical / (double)s->hist_rows;
         const uint64_t n_elem = (uint64_t)s->n_local * s->ld;
         StreamSection sec(s);
         CK(sec.rc);
         CK(normalize_history(s, 0, s->hist_rows));
         hipLaunchKernelGGL(welford_rebuild_kernel, dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0, s->stream,
-                           s->hist, n_elem, n_elem, (uint32_t)s->hist_rows, s->ld, s->w_mean, s->w_m2);
+                           s->hist, n_elem, n_elem, (uint32_t)s->hist_rows, s->ld, m2_scale, s->w_mean, s->w_m2);
         HIPCK(hipGetLastError());
         CK(sec.end());
         s->w_rows = s->rows_logical;
@@ -1784,7 +1831,7 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
     CK(ensure_gen_sums(s, s->rows_logical + 1));
     double* hist_row = nullptr;
     double* llhist_row = nullptr;
-    if (s->cfg.keep_history) {
+    if (generation_appends(s)) {      // (a thinned history skips the generations between its rows: null pointers, the kernels append nothing)
         CK(ensure_history(s, s->hist_rows + 1));
         hist_row = s->hist + (uint64_t)s->hist_rows * s->n_local * s->ld;
         llhist_row = s->llhist + (uint64_t)s->hist_rows * s->n_local;
@@ -1984,7 +2031,7 @@ static int finish_generation(bpm_sampler* s) {
         s->w_rows += 1;
     }
     if (s->cfg.running_moments) CK(push_gen_sums(s, s->rows_logical));      // (the row this generation appended: index rows_logical)
-    if (s->cfg.keep_history) {
+    if (generation_appends(s)) {
         if (s->cur_args[0].hist_by_pos || s->cur_args[1].hist_by_pos)      // appended by position: generation t_abs, ln-like by chain?, shuffle switch
             s->hist_tag[(size_t)s->hist_rows] = (s->t_abs << 2) | ((s->cur_args[0].hist_by_pos | s->cur_args[1].hist_by_pos) == 2u ? 2 : 0) |
                                                 (s->opts.shuffle != 0 ? 1 : 0);
@@ -2495,7 +2542,7 @@ extern "C" int bpm_local_group_step(bpm_handle_t* handles, int32_t R, int64_t n_
         CK(check_handle(s));
         if (!s->local_group || (int)s->world != R || (int)s->rank != r) return fail("bpm_local_group_step: handles are not ranks 0..R-1 of one local group");
         if (!s->run_open) return fail("bpm_local_group_step: call bpm_begin_run on every rank first");
-        if (s->cfg.keep_history) CK(ensure_history(s, s->hist_rows + n_gens));
+        if (s->cfg.keep_history) CK(reserve_history(s, stored_rows_after(s, n_gens), "bpm_local_group_step"));
     CK(ensure_gen_sums(s, s->rows_logical + n_gens));
     }
     CK(set_device(handles[0]));
@@ -2515,7 +2562,7 @@ extern "C" int bpm_step(bpm_handle_t s, int64_t n_gens) {
         return fail("bpm_step: ranks of a local test group are driven by bpm_local_group_step (test variant)");
     if (!s->run_open) return fail("bpm_step: call bpm_begin_run first");
     if (n_gens < 0) return fail("bpm_step: n_gens < 0");
-    if (s->cfg.keep_history) CK(ensure_history(s, s->hist_rows + n_gens));
+    if (s->cfg.keep_history) CK(reserve_history(s, stored_rows_after(s, n_gens), "bpm_step"));
     CK(ensure_gen_sums(s, s->rows_logical + n_gens));
     bpm_sampler* one[1] = {s};
     Group g{one, 1, s->comm != nullptr};
@@ -2821,7 +2868,7 @@ extern "C" int bpm_step_timed(bpm_handle_t s, int64_t n_gens, float* elapsed_ms,
     CK(check_handle_keep_direct(s));
     CK(set_device(s));
     if (s->cfg.algo == BPM_ALGO_DEMC_SYNC) return fail("bpm_step_timed: not available for the synchronous DE-MC mode");
-    if (s->cfg.keep_history) CK(ensure_history(s, s->hist_rows + n_gens));
+    if (s->cfg.keep_history) CK(reserve_history(s, stored_rows_after(s, n_gens), "bpm_step_timed"));
     CK(ensure_gen_sums(s, s->rows_logical + n_gens));
     if (elapsed_ms) *elapsed_ms = 0.f;
     if (n_launches) *n_launches = 0;
@@ -2887,7 +2934,7 @@ extern "C" int bpm_step_profiled(bpm_handle_t s, int64_t n_gens, double* kernel_
     if (n_gens <= 0 || n_gens > 4096) return fail("bpm_step_profiled: 1 <= n_gens <= 4096");
     // (this entry point exchanges with the dense RCCL all-gather; a world without a communicator has no exchange here)
     if (s->world > 1 && !s->comm) return fail("bpm_step_profiled: not available for a rank of a world without an RCCL communicator (push exchange only): use bpm_step_timed");
-    if (s->cfg.keep_history) CK(ensure_history(s, s->hist_rows + n_gens));
+    if (s->cfg.keep_history) CK(reserve_history(s, stored_rows_after(s, n_gens), "bpm_step_profiled"));
     CK(ensure_gen_sums(s, s->rows_logical + n_gens));
     std::vector<hipEvent_t> ev((size_t)n_gens * 4);
     for (auto& e : ev) HIPCK(hipEventCreate(&e));
@@ -2925,6 +2972,7 @@ static void history_installed(bpm_sampler* s, int64_t rows) {
     for (int64_t r = 0; r < rows && r < (int64_t)s->hist_tag.size(); ++r) s->hist_tag[(size_t)r] = -1;
     s->hist_rows = rows;
     s->rows_logical = rows;
+    s->hist_stride = 1;      // (a row per generation: bpm_set_history_thinned says otherwise afterwards)
     s->w_rows = 0;      // moments are rebuilt from the rows when adaptation next needs them
     s->ll_stale = false;
     s->state_set = true;
@@ -2934,13 +2982,16 @@ static void history_installed(bpm_sampler* s, int64_t rows) {
 
 // Warm start (demc.py:46-51,217-233): install `rows` history rows of this rank's chains
 // (hist_local: rows x n_local x dim) and the full current state X (N x dim, = last row of every chain).
-extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_local, const double* X) {
+// x_is_last_row: the dense contract -- X is the last row, so a single row IS what bpm_set_state leaves; a thinned history's X is the CURRENT state,
+// which no stored row need be (bpm_set_history_thinned): every row is installed from hist_local then, the only one included
+static int install_history(bpm_sampler* s, const char* who, int64_t rows, const double* hist_local, const double* X, bool x_is_last_row) {
     CK(check_handle(s));
     CK(set_device(s));
-    if (rows < 1 || !hist_local || !X) return fail("bpm_set_history: bad argument");
-    if (!s->cfg.keep_history && rows > 1) return fail("bpm_set_history: sampler keeps no history");
+    if (rows < 1 || !hist_local || !X) return fail(std::string(who) + ": bad argument");
+    if (!s->cfg.keep_history && rows > 1) return fail(std::string(who) + ": sampler keeps no history");
     CK(bpm_set_state(s, X));      // (reset_history: a new hist_epoch, the one row)
-    if (rows > 1) {
+    s->hist_stride = 1;           // (a row per generation)
+    if (rows > 1 || !x_is_last_row) {
         CK(ensure_history(s, rows));
         HIPCK(hipMemsetAsync(s->hist, 0, (size_t)rows * s->n_local * s->ld * sizeof(double), s->stream));
         HIPCK(hipMemcpy2DAsync(s->hist, s->ld * sizeof(double), hist_local, s->dim * sizeof(double), s->dim * sizeof(double),
@@ -2965,6 +3016,9 @@ extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_
     }
     return 0;
 }
+extern "C" int bpm_set_history(bpm_handle_t s, int64_t rows, const double* hist_local, const double* X) {
+    return install_history(s, "bpm_set_history", rows, hist_local, X, true);
+}
 
 // param_est (demc.py:235-248) without moving the history: raw moments of this rank's part of the
 // super chain (row g*N + i = chain i at generation g) for rows >= n_burn:
@@ -2976,7 +3030,7 @@ extern "C" int bpm_reduce_moments(bpm_handle_t s, int64_t n_burn, double* sum, d
     CK(set_device(s));
     if (!sum || !sumsq || !shift || !count) return fail("bpm_reduce_moments: null argument");
     if (n_burn < 0) n_burn = 0;
-    if (s->cfg.running_moments && (!s->cfg.keep_history || s->hist_rows != s->rows_logical)) {
+    if (s->cfg.running_moments && !history_resident(s)) {
         // no resident history: answer from the per-generation population sums -- exact for a burn-in of whole generations
         if (n_burn % s->N != 0)
             return fail("bpm_reduce_moments: without a resident history n_burn must be a multiple of n_chains (whole generations)");
@@ -3704,7 +3758,7 @@ static int user_refresh_ll(bpm_sampler* s) {
     } else {
         CK(user_eval_launch(s, X, nullptr, s->n_local, s->ll));
     }
-    if (s->hist_rows >= 1 && s->hist_rows == s->rows_logical)
+    if (last_row_is_state(s))
         HIPCK(hipMemcpyAsync(s->llhist + (size_t)(s->hist_rows - 1) * s->n_local, s->ll, s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     return 0;
@@ -4295,7 +4349,7 @@ extern "C" int bpm_set_loglike_device(bpm_handle_t s, const double* ll_dev) {
     }
     HIPCK(hipDeviceSynchronize());
     HIPCK(hipMemcpyAsync(s->ll, ll_dev, s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    if (s->hist_rows >= 1 && s->hist_rows == s->rows_logical)
+    if (last_row_is_state(s))
         HIPCK(hipMemcpyAsync(s->llhist + (size_t)(s->hist_rows - 1) * s->n_local, s->ll, s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     return 0;
@@ -4304,8 +4358,122 @@ extern "C" int bpm_set_loglike_device(bpm_handle_t s, const double* ll_dev) {
 extern "C" int bpm_reserve_history(bpm_handle_t s, int64_t total_rows) {
     CK(check_handle(s));
     CK(set_device(s));
-    return ensure_history(s, total_rows);
+    return reserve_history(s, total_rows, "bpm_reserve_history");
 }
+
+// ---- thinned histories (chain.py:51-54 appends every generation; here every hist_stride-th) -------------------------------------------------
+// what a stride above 1 cannot go with, by reason
+static int check_history_stride(const bpm_sampler* s, const char* who, int64_t k) {
+    if (k < 1) return fail(std::string(who) + ": the stride must be at least 1 (1 = a row per generation)");
+    if (k > 1 && !s->cfg.keep_history) return fail(std::string(who) + ": this sampler keeps no history (keep_history=0): there is nothing to thin");
+    if (k > 2147483647LL) return fail(std::string(who) + ": the stride would exceed 2^31 - 1");
+    if (k > 1 && s->cfg.running_moments)
+        return fail(std::string(who) + ": running_moments counts every generation, a thinned history every k-th: the two n_burn units would disagree; use one or the other");
+    if (k > 1 && s->cfg.outlier_every > 0)
+        return fail(std::string(who) + ": the outlier check (outlier_every > 0) reads a history row per generation; it cannot run on a thinned history");
+    return 0;
+}
+
+extern "C" int bpm_set_history_thin(bpm_handle_t s, int32_t k) {
+    CK(check_handle(s));
+    CK(check_history_stride(s, "bpm_set_history_thin", k));
+    if (k == s->hist_stride) return 0;
+    if (s->rows_logical > 1 || s->hist_rows > 1)
+        return fail("bpm_set_history_thin: the history already holds generations at stride " + std::to_string((long long)s->hist_stride) +
+                    "; bpm_thin_history(h, m) thins what is stored (the new stride is a multiple of the old one)");
+    s->hist_stride = k;
+    return 0;
+}
+
+extern "C" int bpm_get_history_thin(bpm_handle_t s, int64_t out[4]) {
+    CK(check_handle(s));
+    if (!out) return fail("bpm_get_history_thin: null argument");
+    out[0] = s->hist_stride;
+    out[1] = s->rows_logical;
+    out[2] = s->hist_rows;
+    out[3] = s->hist_rows >= 1 ? (s->hist_rows - 1) * s->hist_stride : -1;
+    return 0;
+}
+
+// Keep stored rows 0, m, 2m, ... : gathered into buffers of exactly that many rows (hist_thin_kernel, on the HIP stream), which then take the old
+// ones' place in the registry as ensure_history's do; the old memory goes back.  Reads and writes new rows x n_local x (ld + 1) x 8 bytes once.
+extern "C" int bpm_thin_history(bpm_handle_t s, int32_t m) {
+    const char* who = "bpm_thin_history";
+    CK(check_handle(s));      // (leave_direct: kernels in flight on the library's own queue still write the old buffers)
+    CK(set_device(s));
+    if (m < 1) return fail(std::string(who) + ": m must be at least 1 (1 = keep every stored row)");
+    if (m == 1) return 0;
+    CK(check_history_stride(s, who, s->hist_stride * (int64_t)m));
+    if (!history_resident(s) || s->hist_rows < 1) return fail(std::string(who) + ": no resident history (initialise the chains first)");
+    if (s->proposed || s->phase != 0) return fail(std::string(who) + ": a generation is open (bpm_propose without its bpm_commit); finish it first");
+    const int64_t rows_new = (s->hist_rows - 1) / m + 1;
+    const size_t row_d = (size_t)s->n_local * s->ld;
+    DevTemp<double> nh, nl;
+    CK(nh.alloc((size_t)rows_new * row_d, who, "the thinned history's " + std::to_string((long long)rows_new) + " rows"));
+    CK(nl.alloc((size_t)rows_new * s->n_local));
+    const unsigned gy = (unsigned)std::min<int64_t>(rows_new, 65535);
+    const uint64_t tile = (uint64_t)THIN_THREADS * THIN_UNR;
+    {   // state rows: ld is even, every row starts on 16 bytes
+        const uint64_t row_v = row_d / 2u;
+        hipLaunchKernelGGL(hist_thin_kernel<double2>, dim3((unsigned)((row_v + tile - 1) / tile), gy), dim3(THIN_THREADS), 0, s->stream,
+                           reinterpret_cast<const double2*>(s->hist), reinterpret_cast<double2*>(nh.p), row_v, (uint64_t)rows_new, (uint64_t)m);
+    }
+    if (s->n_local % 2u == 0u) {
+        const uint64_t row_v = s->n_local / 2u;
+        hipLaunchKernelGGL(hist_thin_kernel<double2>, dim3((unsigned)((row_v + tile - 1) / tile), gy), dim3(THIN_THREADS), 0, s->stream,
+                           reinterpret_cast<const double2*>(s->llhist), reinterpret_cast<double2*>(nl.p), row_v, (uint64_t)rows_new, (uint64_t)m);
+    } else {      // an odd number of ln-likes per row: every other row starts 8 bytes off
+        const uint64_t row_v = s->n_local;
+        hipLaunchKernelGGL(hist_thin_kernel<double>, dim3((unsigned)((row_v + tile - 1) / tile), gy), dim3(THIN_THREADS), 0, s->stream,
+                           (const double*)s->llhist, nl.p, row_v, (uint64_t)rows_new, (uint64_t)m);
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(s->stream));
+    // (nothing of the sampler has changed up to here; nothing below can fail)
+    s->mem.replace(&s->hist, nh);
+    s->mem.replace(&s->llhist, nl);
+    s->hist_cap = rows_new;
+    for (int64_t r = 0; r < rows_new; ++r) s->hist_tag[(size_t)r] = s->hist_tag[(size_t)(r * m)];      // a row kept in position order moves with its tag
+    s->hist_tag.resize((size_t)rows_new, -1);
+    s->hist_rows = rows_new;
+    s->hist_stride *= m;
+    s->hist_epoch += 1;
+    return 0;
+}
+
+extern "C" int bpm_set_history_thinned(bpm_handle_t s, int64_t rows, const double* hist_local, const double* X, int32_t k, int64_t rows_logical) {
+    const char* who = "bpm_set_history_thinned";
+    CK(check_handle(s));
+    if (rows < 1 || !hist_local || !X) return fail(std::string(who) + ": bad argument");
+    CK(check_history_stride(s, who, k));
+    if (rows_logical < 1 || rows != (rows_logical - 1) / k + 1)
+        return fail(std::string(who) + ": " + std::to_string((long long)rows) + " stored rows do not agree with " + std::to_string((long long)rows_logical) +
+                    " logical rows at stride " + std::to_string(k) + " (rows must be (rows_logical - 1) / k + 1)");
+    // (X is the last stored row only when the last generation was stored: otherwise every row comes from hist_local, a single one too)
+    const int64_t stride_was = s->hist_stride;
+    if (install_history(s, who, rows, hist_local, X, (rows_logical - 1) % k == 0) != 0) {
+        s->hist_stride = stride_was;      // (an error in there leaves the handle as a failed bpm_set_history does -- re-initialised at X -- with its stride)
+        return 1;
+    }
+    s->hist_stride = k;
+    s->rows_logical = rows_logical;
+    s->w_rows = 0;      // (moments are rebuilt from the stored rows when adaptation next needs them)
+    return 0;
+}
+
+#ifdef BPM_TEST_HOOKS
+// Test variant only: the Welford records of this rank's chains, mean and m2 as n_local x ld each
+extern "C" int bpm_debug_get_welford(bpm_handle_t s, double* mean, double* m2) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!mean || !m2) return fail("bpm_debug_get_welford: null argument");
+    const size_t w = (size_t)s->ld * sizeof(double);
+    HIPCK(hipMemcpy2DAsync(mean, w, s->w_mean, 2 * w, w, s->n_local, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpy2DAsync(m2, w, s->w_m2, 2 * w, w, s->n_local, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+#endif   // BPM_TEST_HOOKS
 
 // Large device-to-host transfers into the caller's pageable buffer.  HIP's own pageable path stages through pinned
 // memory with ONE host thread copying out of it (~10 GB/s here, and the caller's fresh NumPy array page-faults on

@@ -40,6 +40,18 @@ def _hostname():
     return socket.gethostname()
 
 
+def check_thin(thin, what="thin"):
+    """the stride of a thinned history: an integer >= 1 (1 = a row per generation)"""
+    if isinstance(thin, bool) or not isinstance(thin, (int, np.integer)) or thin < 1:
+        raise ValueError("%s must be an integer >= 1 (got %r)" % (what, thin))
+    return int(thin)
+
+
+def stored_rows(rows_logical, thin):
+    """stored rows of a history of rows_logical logical rows (row 0 = the initial state) at stride thin: rows 0, thin, 2 thin, ..."""
+    return (int(rows_logical) - 1) // int(thin) + 1 if rows_logical >= 1 else 0
+
+
 def _default_engine_factory(**kw):
     from .engine import HipEngine
     return HipEngine(**kw)
@@ -59,6 +71,9 @@ class DeMcMpi(HistoryStatistics):
     def __init__(self, ln_like_fn, theta_0=None, varepsilon=1e-6, n_chains=8,
                  mpi_comm=None, ln_kwargs={}, **kwargs):
         assert n_chains >= 4                                   # samplers.py:249
+        # thin = k: the history keeps every k-th generation (rows 0, k, 2k, ... of the dense run's, everything else bit-identical); n_burn, lags
+        # and ESS of every statistic then count STORED rows.  The attribute follows thin_history().  (Absent from the reference, chain.py:51-54.)
+        self.thin = check_thin(kwargs.get("thin", 1))
         varepsilon = np.asarray(varepsilon, dtype=np.float64)
         self.n_chains = int(n_chains)
         self.comm = _comm.wrap(mpi_comm)
@@ -135,7 +150,9 @@ class DeMcMpi(HistoryStatistics):
             nccl_uid=uid, p_snooker=kwargs.get("p_snooker", 0.0), outlier_every=kwargs.get("outlier_every", 0),
             keep_history=kwargs.get("keep_history", True),
             # without a history param_est_moments answers from per-generation population sums (whole-generation burn-ins)
-            running_moments=kwargs.get("running_moments", not kwargs.get("keep_history", True)), **self._engine_kwargs(kwargs))
+            running_moments=kwargs.get("running_moments", not kwargs.get("keep_history", True)),
+            # (the stride reaches the factory only when it is not the default: an engine without thinning keeps working)
+            **dict(self._engine_kwargs(kwargs), **({"thin": self.thin} if self.thin > 1 else {})))
         self.n_local = self.n_chains // self.comm.size
         # ln_like_fn given as HIP source: a host-callback target whose likelihood is a kernel between the proposal and the commit kernel
         # (include/bipymc_hip.h: bpm_set_device_likelihood); an engine without the entry point (the CPU test engine) calls its python_fn
@@ -332,7 +349,7 @@ class DeMcMpi(HistoryStatistics):
         eng = self._engine
         self.comm.Barrier()            # ranks enter the run together (the push exchange bounds how long a rank waits for its peers)
         eng.begin_run(**self._run_opts(kwargs))
-        eng.reserve_history(eng.history_rows() + n_gens)
+        eng.reserve_history(stored_rows(self._rows_logical() + n_gens, self.thin))      # (the rows the run will STORE)
         done = 0
         chunk = int(self.checkpoint) if self.checkpoint and self.checkpoint > 0 else n_gens
         while done < n_gens:
@@ -417,9 +434,31 @@ class DeMcMpi(HistoryStatistics):
         """samplers.py:75-80."""
         return self.n_accepted / (self.n_accepted + self.n_rejected)
 
+    # ---- thinned histories ----------------------------------------------------------
+    def _rows_logical(self):
+        """1 + generations since the chains were (re)initialised"""
+        eng = self._engine
+        return eng.history_thin()["rows_logical"] if self.thin > 1 else eng.history_rows()
+
+    def thin_history(self, m):
+        """Keep every m-th stored row of the history (rows 0, m, 2m, ...) and record every thin * m-th generation from now on: the device memory
+        of the dropped rows is returned, `thin` becomes thin * m.  Call it on every rank.  Statistics opened before the call (quantile,
+        histogram, trace, diagnostics windows) have to be opened again."""
+        m = check_thin(m, "m")
+        if m > 1:
+            self._engine.thin_history(m)
+            self.thin *= m
+        self._hist_cache = None
+        self._hist_cache_rows = -1
+
+    def history_generations(self):
+        """the generation (since the chains were initialised) of every stored history row: np.arange(rows) * thin"""
+        return np.arange(self._engine.history_rows()) * self.thin
+
     # ---- results -----------------------------------------------------------------
     def param_est(self, n_burn, collection_rank=0):
-        """demc.py:235-248."""
+        """demc.py:235-248.  With a thinned history (thin > 1) the super chain holds the STORED rows -- every thin-th generation -- and n_burn
+        counts its rows: n_burn = n_chains * r leaves out the first r stored rows."""
         self.comm.Barrier()
         chain_slice = self.super_chain_mpi(collection_rank)
         if self.comm.rank == collection_rank:
@@ -431,7 +470,7 @@ class DeMcMpi(HistoryStatistics):
 
     def param_est_moments(self, n_burn):
         """mean and std (ddof=0) of the super-chain rows >= n_burn, as `param_est` computes them (demc.py:242-246),
-        reduced on the GPU(s) without moving the history to the host; identical on every rank."""
+        reduced on the GPU(s) without moving the history to the host; identical on every rank.  n_burn counts stored rows (thin > 1)."""
         cnt, s1, s2, sh = self._engine.reduce_moments(int(n_burn))
         parts = self.comm.allgather((cnt, s1, s2))
         n = float(sum(p[0] for p in parts))
@@ -508,9 +547,11 @@ class DeMcMpi(HistoryStatistics):
         if not h5_file:
             h5_file = self.h5_file
         full = self._super_chain(0)
+        # beside t_abs and seed: the stride, the logical length and the CURRENT state (with a stride above 1 that is no longer the last row)
+        adapt = dict(self._adapt_state(), thin=self.thin, rows_logical=self._rows_logical(), state=self._engine.get_state())
         if self.comm.rank == 0:
             T = full.shape[0] // self.n_chains
-            checkpoint.write(h5_file, full.reshape(T, self.n_chains, self.dim), self._adapt_state())
+            checkpoint.write(h5_file, full.reshape(T, self.n_chains, self.dim), adapt)
         self.comm.Barrier()
 
     def load_state(self, h5_file=""):
@@ -519,7 +560,19 @@ class DeMcMpi(HistoryStatistics):
             h5_file = self.h5_file
         hist, adapt = checkpoint.read(h5_file, self.n_chains, self.dim)   # (T, N, d)
         lo = self.comm.rank * self.n_local
-        self._engine.set_history(hist[:, lo:lo + self.n_local, :], hist[-1])
+        # a file without the thinning fields (the reference's, an older one): a row per generation, state = the last row
+        f_thin = int(np.asarray(adapt.get("thin", 1)).reshape(-1)[0])
+        rows_logical = int(np.asarray(adapt.get("rows_logical", (hist.shape[0] - 1) * f_thin + 1)).reshape(-1)[0])
+        X = np.asarray(adapt["state"], dtype=np.float64).reshape(self.n_chains, self.dim) if "state" in adapt else hist[-1]
+        if f_thin < 1 or self.thin % f_thin != 0:
+            raise ValueError("checkpoint %s holds every %d-th generation; a sampler with thin=%d cannot continue it (thin must be a multiple of %d)"
+                             % (h5_file, f_thin, self.thin, f_thin))
+        if f_thin == 1 and rows_logical == hist.shape[0]:
+            self._engine.set_history(hist[:, lo:lo + self.n_local, :], X)
+        else:
+            self._engine.set_history(hist[:, lo:lo + self.n_local, :], X, thin=f_thin, rows_logical=rows_logical)
+        if self.thin != f_thin:
+            self._engine.thin_history(self.thin // f_thin)
         self._after_state_reset()
         self._restore_adapt_state(adapt)
         self.comm.Barrier()

@@ -76,8 +76,8 @@ def _device_pointer(obj, n, what):
 class HipEngine(object):
     def __init__(self, algo, n_chains, dim, target_id, target_params, seed, device=0, rank=0, world_size=1,
                  nccl_uid=None, gamma_scale=1.0, del_pairs=3, burnin_gen=300, n_cr_gen=50, n_cr=3,
-                 p_snooker=0.0, outlier_every=0, keep_history=True, running_moments=False, lib=None):
-        """lib: the ctypes library to run on -- default the product library; tests that need the hooks of include/bipymc_hip_test.h pass
+                 p_snooker=0.0, outlier_every=0, keep_history=True, running_moments=False, lib=None, thin=1):
+        """thin: the history's stride (bpm_set_history_thin; 1 = a row per generation).  lib: the ctypes library to run on -- default the product library; tests that need the hooks of include/bipymc_hip_test.h pass
         `_lib.load_test()` (the same sources built with -DBPM_TEST_HOOKS)."""
         self._h = C.c_void_p()
         self.lib = lib if lib is not None else L.load()
@@ -111,6 +111,12 @@ class HipEngine(object):
         cfg.keep_history = 1 if keep_history else 0
         cfg.running_moments = 1 if running_moments else 0
         self._ck(self.lib.bpm_create(C.byref(cfg), C.byref(self._h)))
+        if int(thin) != 1:
+            try:
+                self.set_history_thin(thin)
+            except BaseException:
+                self.close()
+                raise
         self.algo, self.target_id = int(algo), int(target_id)
         self.n_cr = int(n_cr) if algo == L.ALGO_DREAM else 1
 
@@ -153,12 +159,44 @@ class HipEngine(object):
         self._ck(self.lib.bpm_get_state(self._h, _dptr(X)))
         return X
 
-    def set_history(self, hist_local, X):
+    def set_history(self, hist_local, X, thin=1, rows_logical=None):
+        """Warm start.  thin = 1: a row per generation, X the last row of every chain (bpm_set_history).  thin = k > 1 or a rows_logical: the rows
+        of a thinned history -- logical rows 0, k, 2k, ... of rows_logical (default: the last stored row is the last generation) -- and X the
+        CURRENT state, which is the last row only when (rows_logical - 1) % k == 0 (bpm_set_history_thinned)."""
         hist_local = np.ascontiguousarray(hist_local, dtype=np.float64)
         X = np.ascontiguousarray(X, dtype=np.float64)
         assert hist_local.ndim == 3 and hist_local.shape[1:] == (self.n_local, self.dim)
         assert X.shape == (self.n_chains, self.dim)
-        self._ck(self.lib.bpm_set_history(self._h, hist_local.shape[0], _dptr(hist_local), _dptr(X)))
+        if int(thin) == 1 and rows_logical is None:
+            self._ck(self.lib.bpm_set_history(self._h, hist_local.shape[0], _dptr(hist_local), _dptr(X)))
+            return
+        if rows_logical is None:
+            rows_logical = (hist_local.shape[0] - 1) * int(thin) + 1
+        self._ck(self.lib.bpm_set_history_thinned(self._h, hist_local.shape[0], _dptr(hist_local), _dptr(X), int(thin), int(rows_logical)))
+
+    # ---- thinned histories (include/bipymc_hip.h: bpm_set_history_thin) ---------------------------------
+    def set_history_thin(self, k):
+        """record every k-th generation from now on; only while the history holds its initial row"""
+        self._ck(self.lib.bpm_set_history_thin(self._h, int(k)))
+
+    def history_thin(self):
+        """-> dict(thin, rows_logical, rows, last_stored): the stride, 1 + generations since (re)initialisation, the stored rows and the logical
+        index of the last stored row (bpm_get_history_thin)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.bpm_get_history_thin(self._h, out))
+        return dict(thin=int(out[0]), rows_logical=int(out[1]), rows=int(out[2]), last_stored=int(out[3]))
+
+    def thin_history(self, m):
+        """keep stored rows 0, m, 2m, ...: the stride grows m-fold and the memory of the dropped rows is returned (bpm_thin_history)"""
+        self._ck(self.lib.bpm_thin_history(self._h, int(m)))
+
+    def debug_welford(self):
+        """-> (mean, m2), (n_local, dim) each: the Welford records of DREAM's CR statistic.  Test variant only."""
+        self._need_hooks("bpm_debug_get_welford")
+        ld = self.dim + (self.dim & 1)
+        mean = np.empty((self.n_local, ld)); m2 = np.empty((self.n_local, ld))
+        self._ck(self.lib.bpm_debug_get_welford(self._h, _dptr(mean), _dptr(m2)))
+        return mean[:, :self.dim].copy(), m2[:, :self.dim].copy()
 
     def set_loglike(self, ll_local):
         ll = np.ascontiguousarray(ll_local, dtype=np.float64)

@@ -20,6 +20,9 @@ from .utils import _target
 class DeMc(HistoryStatistics):
     def __init__(self, log_like_fn, n_chains=8, ln_kwargs={}, **proposal_kwargs):
         assert n_chains >= 4                                         # samplers.py:249
+        from .demc import check_thin
+        self.thin = check_thin(proposal_kwargs.get("thin", 1))       # (the history keeps every thin-th generation: DeMcMpi)
+        self._thin0 = self.thin
         self.n_chains = int(n_chains)
         self.log_like_fn = log_like_fn
         self._ln_kwargs = dict(ln_kwargs)
@@ -52,8 +55,9 @@ class DeMc(HistoryStatistics):
         if self._engine is not None:
             self._engine.close()
         eng = factory(algo=L.ALGO_DEMC_SYNC, n_chains=self.n_chains, dim=dim, target_id=tid, target_params=tparams,
-                      seed=seed, device=self._kw.get("device", 0))
+                      seed=seed, device=self._kw.get("device", 0), **({"thin": self._thin0} if self._thin0 > 1 else {}))
         self._engine = eng
+        self.thin = self._thin0
         self._device_target = tid != L.TARGET_HOST_CALLBACK
         # _init_chains (samplers.py:255-259): chain.py:27 jitter with variance varepsilon * inflate
         eng.init_chains(theta_0, np.asarray(varepsilon, dtype=np.float64) * kwargs.get("inflate", 1e1))
@@ -69,7 +73,8 @@ class DeMc(HistoryStatistics):
         eps_std = float(np.sqrt(np.max(np.asarray(varepsilon, dtype=np.float64)) * 1e-3))
         n_gens = max(0, -(-(int(n) - self.n_chains) // self.n_chains))          # while j < n - n_chains: j += n_chains
         eng.begin_run(epsilon=eps_std, gamma=gamma, shuffle=False, flip=0.0)
-        eng.reserve_history(1 + n_gens)
+        from .demc import stored_rows
+        eng.reserve_history(stored_rows(1 + n_gens, self.thin))
         if self._device_target or hip:
             eng.step(n_gens)
         else:
@@ -84,6 +89,20 @@ class DeMc(HistoryStatistics):
         self.n_rejected += int(st["local_n_rejected"]) - 1
         hist = eng.get_history()
         self.am_chains = [DetachedChain(i, hist[:, i, :]) for i in range(self.n_chains)]
+
+    def thin_history(self, m):
+        """keep every m-th stored row of the last run's history; `thin` becomes thin * m (DeMcMpi.thin_history)"""
+        from .demc import check_thin
+        m = check_thin(m, "m")
+        if m > 1:
+            self._stats_engine("thin_history").thin_history(m)
+            self.thin *= m
+            hist = self._engine.get_history()
+            self.am_chains = [DetachedChain(i, hist[:, i, :]) for i in range(self.n_chains)]
+
+    def history_generations(self):
+        """the generation of every stored history row: np.arange(rows) * thin"""
+        return np.arange(self._stats_engine("history_generations").history_rows()) * self.thin
 
     def _call(self, theta):
         v = self._frozen_ln_like_fn(np.array(theta, dtype=np.float64))
@@ -117,5 +136,6 @@ class DeMc(HistoryStatistics):
     _stats_allgather = staticmethod(single_process_allgather)
 
     def param_est(self, n_burn):
+        """samplers.py:311-315; with thin > 1 the rows are the stored ones and n_burn counts them"""
         chain_slice = self.super_chain[n_burn:, :]                      # samplers.py:311-315
         return np.mean(chain_slice, axis=0), np.std(chain_slice, axis=0), chain_slice

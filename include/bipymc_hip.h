@@ -276,7 +276,35 @@ int bpm_get_device_likelihood_info(bpm_handle_t h, int32_t* fused, char* why, in
 /* history of this rank's chains: out[(g - g_lo) * n_local * dim + i * dim + j], g in [g_lo, g_hi) */
 int bpm_get_history(bpm_handle_t h, int64_t g_lo, int64_t g_hi, double* out);
 int bpm_get_loglike_history(bpm_handle_t h, int64_t g_lo, int64_t g_hi, double* out);
+/* Room for total_rows STORED rows.  The growth is checked against the free device memory before anything is allocated (while the old rows are
+ * copied the old and the new buffer exist at once); the refusal states the size needed and names the ways out -- a thinned history (below), or
+ * keep_history = 0 with running_moments -- and leaves the handle usable.  Every step call reserves the rows it will store the same way. */
 int bpm_reserve_history(bpm_handle_t h, int64_t total_rows);
+/* THINNED HISTORIES (build-defined; the reference's McmcChain appends every generation, chain.py:51-54, and has no thinning).  A history has
+ * a stride k >= 1: stored row r is logical row r k, where logical row t is the state after generation t since the last (re)initialisation
+ * (row 0 = the initial state), and a generation is appended iff the logical row it produces is a multiple of k.  A thinned run's history is
+ * exactly [::k] of the dense run's from the same seed; state, ln-likes, accept counters, p_cr, delta_m and the CR adaptation of burn-in are
+ * bit-identical to the dense run's, and with stride 1 nothing changes at all.  Every statistic of the history (bpm_reduce_moments,
+ * bpm_diag_*, bpm_quantile_*, bpm_reduce_cov, bpm_hist_*, bpm_trace_*, bpm_derive) counts STORED rows: n_burn, g_lo / g_hi, every and lags.
+ * bpm_set_history_thin: what chain.py:51-54 appends, thinned to every k-th generation from now on.  Allowed while the history holds only its
+ *   initial row (after bpm_create / bpm_init_chains / bpm_set_state), or when k is the current stride; otherwise an error that points to
+ *   bpm_thin_history.  The stride belongs to the handle and survives bpm_init_chains / bpm_set_state (bpm_set_history installs a row per
+ *   generation: stride 1).  Refused, each with its reason: k < 1; keep_history = 0 with k > 1; running_moments = 1 with k > 1 (those sums count every
+ *   generation: the two n_burn units would disagree); outlier_every > 0 with k > 1 (the outlier check reads a row per generation).
+ * bpm_thin_history: thins what chain.py:51-54 has appended so far: keeps stored rows 0, m, 2m, ... and their ln-like rows; the new stride is
+ *   the old one times m, the new row count (rows - 1) / m + 1; m = 1 is a no-op.  Recording stays aligned by the append rule.  The kept rows
+ *   are gathered into new buffers of exactly that size, which replace the old ones; the old memory is returned, and an error on the way
+ *   leaves the sampler as it was.  Rows kept in position order stay so.  Open bpm_quantile_* / bpm_hist_* / bpm_trace_* / bpm_diag_* windows
+ *   answer "the history changed" afterwards.  The same refusals, and: a stride beyond 2^31 - 1, a half generation open (bpm_propose).
+ * bpm_set_history_thinned: warm start from a thinned checkpoint (chain.py:51-54's rows, every k-th): bpm_set_history, then stride k and the
+ *   logical length rows_logical; rows must be (rows_logical - 1) / k + 1.  X is the CURRENT state, which is the last row only when
+ *   (rows_logical - 1) % k == 0; otherwise every stored row, a single one included, is hist_local's.  An error behind the checks of the
+ *   arguments leaves the handle as a failed bpm_set_history does: re-initialised at X with one row, its stride kept.
+ * bpm_get_history_thin: out = {stride, logical rows, stored rows, logical index of the last stored row}. */
+int bpm_set_history_thin(bpm_handle_t h, int32_t k);
+int bpm_thin_history(bpm_handle_t h, int32_t m);
+int bpm_set_history_thinned(bpm_handle_t h, int64_t rows, const double* hist_local, const double* X, int32_t k, int64_t rows_logical);
+int bpm_get_history_thin(bpm_handle_t h, int64_t out[4]);
 /* param_est (demc.py:235-248) without moving the history: for this rank's rows of the interleaved
  * super chain (row g*N + i = chain i at generation g) with row index >= n_burn, returns count,
  * sum_j (x - shift_j), sum_j (x - shift_j)^2 and shift_j (length dim each; shift is identical on every
@@ -404,7 +432,8 @@ int bpm_derive(bpm_handle_t h, int64_t n_burn, int64_t* counts, double* sums, in
  * the call.  Costs hist_rows x n_local x ((n_out rounded up to even) + 1) x 8 bytes of device memory on dst.  Every check runs before any
  * launch.  Errors: a null handle, dst == src, different devices, no function installed, no resident history on src (keep_history = 0), a dst
  * without keep_history, with another target, dim != n_out or another n_chains, world_size != 1 on either (single rank only), a derived history
- * larger than the free device memory (the message names the requirement). */
+ * larger than the free device memory (the message names the requirement).  A THINNED source (bpm_set_history_thin) gives an ordinary
+ * stride-1 destination that holds the source's stored rows. */
 int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst);
 /* A RANKED HISTORY IS A HISTORY: the one transform of a history that is no function of one sample -- the pooled rank of every value within
  * its coordinate -- written into the history of `dst`, a second, ordinary handle as bpm_derive_history takes one (host-callback target,
@@ -430,7 +459,8 @@ int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst);
  * temporary is freed on return.  Errors: a null handle, dst == src, different devices, an unknown kind, a missing arg, a position outside
  * [0, S), no resident history on src (keep_history = 0), a range out of bounds, n < 4, a dst without keep_history, with another target, dim
  * or n_chains, world_size != 1 on either (single rank only), S >= 2^31, one column's scratch beyond the budget or scratch or history beyond
- * the free device memory (the message names the requirement). */
+ * the free device memory (the message names the requirement).  A THINNED source (bpm_set_history_thin): g_lo, g_hi count its stored rows and
+ * dst is an ordinary stride-1 history of them. */
 int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
                      const int64_t* pos, double* order_stats);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the

@@ -60,6 +60,9 @@ int bpm_debug_time_kernels(bpm_handle_t h, int32_t reps, float* update_us, float
 /* update-kernel launches of this handle so far by kernel flavour (bipymc_amd/csrc/kernels.h: Flavour): out[0] the general kernel, out[1] / out[2] single
  * GPU in the steady state with / without plan records, out[3] / out[4] the same during DREAM's CR adaptation, out[5] a rank of a world, out[6] unused */
 int bpm_debug_flavour_counts(bpm_handle_t h, int64_t out[7]);
+/* the Welford records of this rank's chains that DREAM's CR statistic is normalised with (dream.py:128): mean and m2, n_local x ld doubles
+ * each (ld = dim rounded up to even) */
+int bpm_debug_get_welford(bpm_handle_t h, double* mean, double* m2);
 /* the inline Philox4x32-10 against rocRAND's device engine: n blocks of (seed, subsequence i, block i) from both */
 int bpm_selftest_philox(int32_t device, int32_t n, uint64_t seed, uint32_t* out_mine, uint32_t* out_rocrand);
 /* per-generation host decisions (flip, shuffle order and its inverse) for generation t */
