@@ -17,6 +17,8 @@ def case_spec(case):
     from bipymc_amd.utils import banana_rv, d100_gauss, mixture_nd
     if case == "dream_gauss100":
         return d100_gauss.Gauss_100D()._bpm_target_spec(), L.ALGO_DREAM, 64, dict(burnin_gen=8, n_cr_gen=3), 20
+    if case == "dream_gauss100_overflow":  # dream_gauss100 from two rows of magnitude 1e160 (ln-like NaN; partners' proposals at that scale): tests/test_gpu_nonfinite.py
+        return d100_gauss.Gauss_100D()._bpm_target_spec(), L.ALGO_DREAM, 64, dict(burnin_gen=8, n_cr_gen=3), 20
     if case == "dream_gauss100_long":      # crosses two 64-generation table windows: the windows built INSIDE the generation loop
         return d100_gauss.Gauss_100D()._bpm_target_spec(), L.ALGO_DREAM, 64, dict(burnin_gen=8, n_cr_gen=3), 150
     if case == "dream_mix8_outlier":
@@ -34,7 +36,11 @@ def case_spec(case):
 
 
 def start_state(case, N, d):
-    return np.random.RandomState(3).normal(size=(N, d)) + 0.5
+    x0 = np.random.RandomState(3).normal(size=(N, d)) + 0.5
+    if case == "dream_gauss100_overflow":      # one overflow row in each rank's share at R = 2
+        x0[1] = 1e160 * np.where(np.arange(d) % 2 == 0, 1.0, -1.0)
+        x0[N // 2 + 5] = 1e160
+    return x0
 
 
 def main():

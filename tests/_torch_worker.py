@@ -68,6 +68,48 @@ def device_parity(algo, d, N, kw):
     print("device_parity ok")
 
 
+def device_nonfinite(name, variant):
+    """device_parity's loop on the bounded-support likelihood of tests/_nonfinite_cases.py (-inf outside a box; "bands": NaN and +inf inside it as well),
+    from a start with a quarter of the chains outside: the commit kernel's Metropolis step on ln-likes that are not finite, the values handed over as a
+    device tensor.  Per generation: the accept decisions (a chain moved iff the oracle accepted it), the counters, the NaN count, the ln-likes class by
+    class; at the end what device_parity asserts, at its tolerances."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _nonfinite_cases as NF
+    from bipymc_amd.engine import HipEngine
+    r = NF.oracle_box_run(name, variant)
+    assert r.margin >= NF.MARGIN, r.margin
+    torch_ll = NF.torch_ll_factory(torch, r.d, variant)
+    eng = HipEngine(algo=r.algo, n_chains=r.N, dim=r.d, target_id=R.TARGET_HOST, target_params=None, seed=r.seed, **r.kw)
+    eng.set_state(r.X0)
+    eng.set_loglike_device(torch_ll(eng.state_device()))
+    NF.assert_same_classes_and_close(eng.get_loglike(), r.ll0, 1e-12, 0, "start ln-likes")
+    eng.begin_run()
+    prev = r.X0
+    n_back = 0
+    for g in range(NF.GENS):
+        for ph in range(2):
+            rows = eng.propose_device()
+            eng.commit_device(torch_ll(rows))
+        now = eng.get_state()
+        changed = np.any(now != prev, axis=1)
+        prev = now
+        assert np.array_equal(changed, r.acc[g]), (g, np.nonzero(changed != r.acc[g])[0])
+        assert np.all(changed[r.from_minf[g]])                           # ll_cur = -inf, the proposal inside the box: the chain moved
+        n_back += int(np.count_nonzero(r.from_minf[g]))
+        st = eng.stats()
+        assert (st["local_n_accepted"], st["local_n_rejected"], st["n_nan_alpha"]) == (r.n_acc[g], r.n_rej[g], r.n_nan[g]), (g, st)
+        np.testing.assert_allclose(now, r.X[g + 1], rtol=1e-10, atol=1e-12)
+        NF.assert_same_classes_and_close(eng.get_loglike(), r.ll[g + 1], 1e-10, 1e-12, "ln-likes after generation %d" % g)
+    assert n_back >= 1 and st["n_nan_alpha"] > 0
+    np.testing.assert_allclose(eng.get_history(), r.history, rtol=1e-10, atol=1e-12)
+    NF.assert_same_classes_and_close(eng.get_loglike_history(), r.ll_history, 1e-10, 1e-12, "ln-like history")
+    if r.algo == R.ALGO_DREAM:
+        np.testing.assert_allclose(st["p_cr"], r.p_cr[-1], rtol=1e-8)
+        assert np.array_equal(st["n_cr_updates"], r.n_cr_updates)
+    eng.close()
+    print("device_nonfinite ok")
+
+
 def transports():
     """One likelihood, five ways to call it (samplers.py:36-43 calls ln_like_fn row by row): per row, vectorised over a half generation in one piece,
     vectorised with the read-back in five overlapped pieces, the pieces evaluated by a pool of three host threads, and as a torch function on the
@@ -117,5 +159,7 @@ def transports():
 if __name__ == "__main__":
     if sys.argv[1] == "device_parity":
         device_parity(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), json.loads(sys.argv[5]))
+    elif sys.argv[1] == "device_nonfinite":
+        device_nonfinite(sys.argv[2], sys.argv[3])
     elif sys.argv[1] == "transports":
         transports()

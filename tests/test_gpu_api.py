@@ -435,6 +435,27 @@ def test_nan_ratio_raises_like_numpy():
         s.run_mcmc(8 * 3)
 
 
+def test_nan_ratio_raises_on_the_device_paths_too():
+    """The same start -- every chain outside the support, so both ln-likes are -inf and alpha is NaN -- on the shipped banana target (the fused kernels,
+    lean form: a start at 1e160 overflows to -inf) and on a HipLikelihood of a box (tests/_nonfinite_cases.py; the run-time compiled update kernel)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import _nonfinite_cases as NF
+    from bipymc_amd import DeMcMpi, HipLikelihood
+    from bipymc_amd.utils import banana_rv
+    s = DeMcMpi(banana_rv.Banana_2D().ln_like, np.full(2, 1e160), n_chains=8, seed=1)
+    assert s.uses_device_target
+    with pytest.raises(ValueError):
+        s.run_mcmc(8 * 3)
+    d = 3
+    box = HipLikelihood(NF.hip_source("box", terms=False)[0], params=NF.box_params(d), python_fn=NF.BoxLikelihood(d, "box"))
+    s = DeMcMpi(box, 10.0 * NF.sigma_of(d), n_chains=8, seed=1)
+    assert not s.uses_device_target
+    with pytest.raises(ValueError):
+        s.run_mcmc(8 * 3)
+
+
 @pytest.mark.parametrize("ext", [".npz", ".h5"])
 def test_checkpoint_warm_start_gpu(tmp_path, ext):
     """demc.py:198-233 through the device engine: the NumPy twin of the layout, and the reference's own HDF5 layout (h5py, or the

@@ -8,19 +8,29 @@ Reference arithmetic restated by the oracle: bipymc/dream.py:32-140 (DREAM updat
 after G generations: rtol 1e-10 / atol 1e-12 (libm exp/log, reduction order and the float32 Box-Muller of the 1e-12-scale jitter;
 one generation agrees to 1e-12, tests/test_gpu_parity.py).
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import sampler_ref as R
 
 pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+from _nonfinite_cases import assert_same_classes_and_close  # noqa: E402
 
 RTOL, ATOL = 1e-10, 1e-12
 
 
-def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, launches=None):
+def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, launches=None, nonfinite=False):
     """launches: (update dispatches on the library's own queue, on the HIP stream) the run has to add; None = the shipped path of DE-MC and
-    DREAM, two update launches per generation, every one through the own queue"""
+    DREAM, two update launches per generation, every one through the own queue.
+    nonfinite: the run is MEANT to meet ln-likes that are not finite (tests/test_gpu_nonfinite.py): the NaN alphas are counted alike on both sides and
+    there are some, and NaN / +inf / -inf sit at the oracle's positions; the default keeps every other caller at "no NaN alpha at all"."""
     from bipymc_amd.engine import HipEngine
     eng = HipEngine(algo=algo, n_chains=N, dim=d, target_id=target_id, target_params=params, seed=seed, **okw)
     ora = R.OracleSampler(algo, N, d, target_id, params, seed, **okw)
@@ -28,7 +38,9 @@ def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, lau
     assert ls0["has_queue"], "no direct AQL queue on this box: " + str(ls0)
     assert ls0["fence"] == "acquire" and not ls0["coherent_state"], ls0
     eng.set_state(X0)
-    ora.set_state(X0)
+    quiet = dict(all="ignore") if nonfinite else {}         # (overflow and inf - inf are the point of such a run)
+    with np.errstate(**quiet):
+        ora.set_state(X0)
     eng.begin_run()
     eng.step(gens)                         # NO trace: the specialised (HOT) instantiations run
     eng.synchronize()
@@ -37,19 +49,24 @@ def _run_both(algo, N, d, target_id, params, seed, X0, gens, okw, hist_rows, lau
         assert ls["direct"] - ls0["direct"] == 2 * gens and ls["stream"] == ls0["stream"], (ls0, ls)   # every update kernel through the own queue
     else:
         assert (ls["direct"] - ls0["direct"], ls["stream"] - ls0["stream"]) == tuple(launches), (ls0, ls)
-    ora.run(gens)
+    with np.errstate(**quiet):
+        ora.run(gens)
     st = eng.stats()
     # ---- integers: exact
     assert st["local_n_accepted"] == ora.local_n_accepted, (st["local_n_accepted"], ora.local_n_accepted)
     assert st["local_n_rejected"] == ora.local_n_rejected
-    assert st["n_nan_alpha"] == ora.n_nan == 0
-    # ---- floats
+    if nonfinite:
+        assert st["n_nan_alpha"] == ora.n_nan > 0, (st["n_nan_alpha"], ora.n_nan)
+    else:
+        assert st["n_nan_alpha"] == ora.n_nan == 0
+    # ---- floats (nonfinite: first NaN, +inf and -inf each at the oracle's positions, then the values as everywhere)
+    _assert_close = assert_same_classes_and_close if nonfinite else (lambda got, want, rtol, atol: np.testing.assert_allclose(got, want, rtol=rtol, atol=atol))
     X = eng.get_state()
-    np.testing.assert_allclose(X, ora.X, rtol=RTOL, atol=ATOL)
-    np.testing.assert_allclose(eng.get_loglike(), ora.ll, rtol=RTOL, atol=1e-9)
+    _assert_close(X, ora.X, RTOL, ATOL)
+    _assert_close(eng.get_loglike(), ora.ll, RTOL, 1e-9)
     for g in hist_rows:                    # two history rows, straight out of the device history
-        np.testing.assert_allclose(eng.get_history(g, g + 1)[0], ora.history[g], rtol=RTOL, atol=ATOL)
-        np.testing.assert_allclose(eng.get_loglike_history(g, g + 1)[0], ora.ll_history[g], rtol=RTOL, atol=1e-9)
+        _assert_close(eng.get_history(g, g + 1)[0], ora.history[g], RTOL, ATOL)
+        _assert_close(eng.get_loglike_history(g, g + 1)[0], ora.ll_history[g], RTOL, 1e-9)
     if algo == R.ALGO_DREAM:
         np.testing.assert_allclose(st["p_cr"], ora.cr.p_cr, rtol=1e-9)
         np.testing.assert_allclose(st["delta_m"], ora.cr.delta_m, rtol=1e-6)        # divides by per-chain history variances: see test_gpu_parity
