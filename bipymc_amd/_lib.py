@@ -135,6 +135,8 @@ TEST_SIGNATURES = {
     "bpm_debug_queue_pad": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int64)]),
     "bpm_debug_coherence_probe": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int64)]),
     "bpm_selftest_philox": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, _u32p, _u32p]),
+    "bpm_selftest_accept": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "bpm_selftest_accept_error": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp]),
     "bpm_debug_perm": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_double, _ip, _ip, _ip]),
     "bpm_debug_outlier_select": (C.c_int, [_H, _dp, _dp]),
     "bpm_debug_time_kernels": (C.c_int, [_H, C.c_int32, _P(C.c_float), _P(C.c_float)]),
@@ -164,7 +166,7 @@ def load():
 
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
-_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/device_memory.h", "csrc/user_likelihood.h", "csrc/derived.h",
+_ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/accept_test.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/accept_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/device_memory.h", "csrc/user_likelihood.h", "csrc/derived.h",
             "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_target.h", "csrc/derive_rows.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 

@@ -25,6 +25,10 @@
 #endif
 
 #include "philox.h"
+#include "accept_test.h"
+#ifndef BPM_ACCEPT_FILTER_DIVERGENT      // (timing builds: finish_update)
+#define BPM_ACCEPT_FILTER_DIVERGENT 0
+#endif
 
 // Diagnostic build only (-DBPM_STAMPS): s_memtime stamps along one wavefront's critical path, written to
 // PhaseArgs::stamps (8 x u64 per work item).  Never compiled into the product library.
@@ -503,12 +507,18 @@ struct Target<TARGET_GAUSS, LPC, DPL> {
         }
         return k;
     }
+    // EVEN_ZERO (DREAM's planned front, phase_fused_kernel): the caller's v[s] is exactly +0 in every lane whose EVEN coordinate lies beyond dim -- the
+    // own row's lanes beyond the row are zeroed by a select on the loaded value (make_proposal: in_row; ld is dim rounded up to even, so "beyond the
+    // row" and "2 pi >= dim" are one condition) and a proposal equals the own row wherever its mask bit is clear, which it is beyond dim.  With
+    // is[s] = 0 there (load) the lane adds +0 to sums that are +0: the guard on even s cannot change a bit.  The guard on odd s stays: for an odd dim
+    // the lane of the last pair holds the row's pad column, whose content every writer of a state row would have to keep finite.
+    template <bool EVEN_ZERO = false>
     static __device__ __forceinline__ double eval(const double* v, int q, uint32_t dim, const Consts& k) {
         double s1 = 0.0, s2 = 0.0;
 #pragma unroll
         for (int s = 0; s < DPL; ++s) {
             const uint32_t j = 2u * (uint32_t)(q + (s >> 1) * LPC) + (s & 1);
-            if (j < dim) {
+            if ((EVEN_ZERO && (s & 1) == 0) || j < dim) {
                 const double z = v[s] * k.is[s];
                 s1 += z;
                 s2 += z * z;
@@ -878,7 +888,9 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
             // out its own-row fetch before it could even request the partner rows.
             const uint32_t gi = (uint32_t)(q + u * WAVE);
             const double gl = FRONT ? fr->gl[u] : a.gamma_tab[gi <= dim ? gi : dim];
-            gtab[u] = gi <= dim ? gl : 0.0;
+            // (the planned front keeps the loaded value: the lookup below reads lane d' of the table, 1 <= d' <= dim -- a zero count is forced to 1 -- so
+            // the lanes beyond dim are never read)
+            gtab[u] = (FRONT || gi <= dim) ? gl : 0.0;
         }
     }
     // ... and with several chains per wavefront (at most 32 coordinates): lane l holds entry l, the lookup by d' is a lane read through the LDS crossbar
@@ -1078,16 +1090,19 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
         if (j0 < dim) {
             const u32x4 wj = wpair[u];
             const bool two = j0 + 1 < dim;
+            // (DREAM's planned front draws the pad column's jitter unguarded: the proposal reads a jump only under its mask bit, and bit 2u + 1 is set
+            // only under `two`)
+            const bool two_eps = two || (FRONT && DREAM);
             if (a.epsilon > 0.0) {                                   // util.py:5-16
                 double n0, n1;
                 box_muller_pair_f32(wj.z, wj.w, n0, n1);
                 eps_n[2 * u] = a.epsilon * n0;
-                if (two) eps_n[2 * u + 1] = a.epsilon * n1;
+                if (two_eps) eps_n[2 * u + 1] = a.epsilon * n1;
             }
             if (DREAM) {
                 if (a.u_epsilon > 0.0) {                             // util.py:18-28
                     eps_u[2 * u] = -a.u_epsilon + (2.0 * a.u_epsilon) * (((double)(wj.y >> 16) + 0.5) * 1.52587890625e-05);
-                    if (two) eps_u[2 * u + 1] = -a.u_epsilon + (2.0 * a.u_epsilon) * (((double)(wj.y & 0xFFFFu) + 0.5) * 1.52587890625e-05);
+                    if (two_eps) eps_u[2 * u + 1] = -a.u_epsilon + (2.0 * a.u_epsilon) * (((double)(wj.y & 0xFFFFu) + 0.5) * 1.52587890625e-05);
                 }
                 if ((wj.x >> 16) <= thr) { maskbits |= 1u << (2 * u); ++cnt; }              // dream.py:52-53
                 if (two && (wj.x & 0xFFFFu) <= thr) { maskbits |= 1u << (2 * u + 1); ++cnt; }
@@ -1290,11 +1305,14 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     const uint32_t ld = a.L.ld;
     const uint32_t li = c - a.lo;
     const double ll_cur = wk.ll_cur;
-    double alpha = exp((ll_prop + wk.log_corr) - ll_cur);
-    const bool is_nan = alpha != alpha;
-    alpha = fmin(1.0, alpha);
-    alpha = fmax(0.0, alpha);                            // np.clip(np.min((1, .)), 0, 1); NaN stays NaN in NumPy
-    const bool accepted = !is_nan && (wk.u_acc < alpha);
+    const double d_acc = (ll_prop + wk.log_corr) - ll_cur;
+    bool is_nan;
+    // u < clip(min(1, exp(d)), 0, 1), decided without the exp() where a float32 2^t can (accept_test.h) -- with one wavefront per chain, where d is
+    // wavefront-uniform and the exact path sits behind a scalar branch.  Several chains per wavefront keep the plain formula: there the branch is a
+    // divergent one, taken when any lane asks, and with it cfg5's share measured 1.4 % SLOWER than without (9.36 against 9.22 us per generation, outside
+    // both spreads; cfg5 whole unchanged, cfg3 0.7 % faster: profiles/accept_filter.txt).  -DBPM_ACCEPT_FILTER_DIVERGENT=1 builds the filter into them too.
+    constexpr bool FILTER = LPC == WAVE || BPM_ACCEPT_FILTER_DIVERGENT != 0;
+    const bool accepted = FILTER ? accept_test(d_acc, wk.u_acc, &is_nan) : accept_exact(d_acc, wk.u_acc, &is_nan);
     const bool lean = LEAN == 2 || (LEAN == 1 && a.lean != 0u);
     if (lean) {      // one counter bump per wavefront (all lanes are still here): acc_count[n_local + shard]
         const unsigned long long m = __ballot(active && accepted && q == 0);
@@ -1427,7 +1445,8 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     if (trace_i32_of(a) && q == 0) {
         trace_i32_of(a)[(uint64_t)li * TRACE_I32 + 3] = accepted ? 1 : 0;
         double* tf = trace_f64_of(a) + (uint64_t)li * TRACE_F64;
-        tf[0] = alpha; tf[1] = ll_prop; tf[2] = wk.delta; tf[3] = wk.gamma;
+        bool nan_alpha;
+        tf[0] = accept_alpha(d_acc, &nan_alpha); tf[1] = ll_prop; tf[2] = wk.delta; tf[3] = wk.gamma;      // (the trace records the exact value)
     }
     // push exchange: a wavefront ends only when its stores into the peers' replicas have been acknowledged at system scope (gfx942 / gfx950 count
     // stores in vmcnt: the #error at the top of this file).  The packet of this kernel may carry no release fence (agent-scope mode), and the flag
@@ -1769,7 +1788,9 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     } else {      // (one wavefront per chain: the call of rounds 1-3, with the planned front's record and rows where the flavour has one)
         make_proposal<ALGO, LPC, DPL, NP, 1, NoEarly, FRONT_CT>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, NoEarly(), PcrGiven(), &fr);
     }
-    const double ll_prop = Target<TARGET, LPC, DPL>::eval(wk.p, q, a.L.dim, tc);
+    double ll_prop;
+    if constexpr (FRONT_CT && TARGET == TARGET_GAUSS && ALGO == ALGO_DREAM) ll_prop = Target<TARGET_GAUSS, LPC, DPL>::template eval<true>(wk.p, q, a.L.dim, tc);
+    else ll_prop = Target<TARGET, LPC, DPL>::eval(wk.p, q, a.L.dim, tc);
     BPM_STAMP(5);
     finish_update<ALGO, LPC, DPL, (LEAN_CT ? 2 : (LEAN ? 1 : 0)), CRP>(a, c, active, q, wk, ll_prop);
     if (CRP && active && a.adapt_on && a.cr_gate) { cr_d = wk.delta; cr_i = wk.cr_idx; }      // what finish_update wrote into the chain's slots

@@ -356,11 +356,9 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
     }
     // ---- Metropolis (samplers.py:328-336): everything here is wavefront-uniform
     const double ll_prop = T.finish(a.tparams, U.dim);
-    double alpha = exp((ll_prop + log_corr) - ll_cur);
-    const bool is_nan = alpha != alpha;
-    alpha = fmin(1.0, alpha);
-    alpha = fmax(0.0, alpha);
-    const bool accepted = __builtin_amdgcn_readfirstlane((!is_nan && (u01_53(h0.z, h0.w) < alpha)) ? 1 : 0) != 0;
+    const double d_acc = (ll_prop + log_corr) - ll_cur;
+    bool is_nan;
+    const bool accepted = __builtin_amdgcn_readfirstlane(accept_test(d_acc, u01_53(h0.z, h0.w), &is_nan) ? 1 : 0) != 0;      // (accept_test.h)
     const double new_ll = accepted ? ll_prop : ll_cur;
     if (lane == 0) {
         if (accepted) {
@@ -392,7 +390,8 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
         if (trace_i32_of(a)) {
             trace_i32_of(a)[(uint64_t)li * TRACE_I32 + 3] = accepted ? 1 : 0;
             double* tf = trace_f64_of(a) + (uint64_t)li * TRACE_F64;
-            tf[0] = alpha; tf[1] = ll_prop; tf[2] = delta; tf[3] = U.gamma;
+            bool nan_alpha;
+            tf[0] = accept_alpha(d_acc, &nan_alpha); tf[1] = ll_prop; tf[2] = delta; tf[3] = U.gamma;
         }
     }
     // ---- pass C
@@ -464,11 +463,9 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_commit_kernel(const
     const double ll_cur = a.ll[li], ll_prop = a.aux_buf[a.L.n_local + w], log_corr = a.aux_buf[w];
     const uint32_t acc_prev = a.acc_count[li];
     const u32x4 h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
-    double alpha = exp((ll_prop + log_corr) - ll_cur);
-    const bool is_nan = alpha != alpha;
-    alpha = fmin(1.0, alpha);
-    alpha = fmax(0.0, alpha);
-    const bool accepted = __builtin_amdgcn_readfirstlane((!is_nan && (u01_53(h0.z, h0.w) < alpha)) ? 1 : 0) != 0;
+    const double d_acc = (ll_prop + log_corr) - ll_cur;
+    bool is_nan;
+    const bool accepted = __builtin_amdgcn_readfirstlane(accept_test(d_acc, u01_53(h0.z, h0.w), &is_nan) ? 1 : 0) != 0;      // (accept_test.h)
     const double new_ll = accepted ? ll_prop : ll_cur;
     if (lane == 0) {
         if (accepted) { a.acc_count[li] = acc_prev + 1u; a.ll[li] = new_ll; }
@@ -477,7 +474,8 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_commit_kernel(const
         if (trace_i32_of(a)) {
             trace_i32_of(a)[(uint64_t)li * TRACE_I32 + 3] = accepted ? 1 : 0;
             double* tf = trace_f64_of(a) + (uint64_t)li * TRACE_F64;
-            tf[0] = alpha; tf[1] = ll_prop; tf[2] = DREAM ? *delta_ptr(a.L, c) : 0.0; tf[3] = 0.0;
+            bool nan_alpha;
+            tf[0] = accept_alpha(d_acc, &nan_alpha); tf[1] = ll_prop; tf[2] = DREAM ? *delta_ptr(a.L, c) : 0.0; tf[3] = 0.0;
         }
     }
     const bool welford = DREAM && a.adapt_on;

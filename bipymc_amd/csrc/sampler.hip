@@ -49,6 +49,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #ifdef BPM_TEST_HOOKS
 #include "rocrand_check.h"
+#include "accept_check.h"
 #endif
 #include "aql_queue.h"
 #include "user_likelihood.h"
@@ -4688,6 +4689,51 @@ extern "C" int bpm_selftest_philox(int32_t device, int32_t n, uint64_t seed, uin
         std::memcpy(out_mine + 4 * (size_t)i, h.data() + 8 * (size_t)i, 16);
         std::memcpy(out_rocrand + 4 * (size_t)i, h.data() + 8 * (size_t)i + 4, 16);
     }
+    return 0;
+}
+
+// The accept test of the update kernels (accept_test.h) on n caller-supplied (d, u) pairs, evaluated on the device: its decision and NaN flag beside the
+// plain formula's with the device library's exp(), and whether the float32 filter asked for the exact path.  One byte per case and array.
+extern "C" int bpm_selftest_accept(int32_t device, int32_t n, const double* d, const double* u, uint8_t* accepted_filter, uint8_t* accepted_exact,
+                                   uint8_t* nan_filter, uint8_t* nan_exact, uint8_t* took_exact) {
+    if (n <= 0 || !d || !u || !accepted_filter || !accepted_exact || !nan_filter || !nan_exact || !took_exact) return fail("bpm_selftest_accept: bad argument");
+    HIPCK(hipSetDevice(device));
+    DevTemp<double> dd, du;
+    DevTemp<uint8_t> dout;
+    CK(dd.alloc((size_t)n)); CK(du.alloc((size_t)n)); CK(dout.alloc((size_t)n * 5));
+    HIPCK(hipMemcpy(dd.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(du.p, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(accept_check_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, (int)n, dd.p, du.p, dout.p);
+    HIPCK(hipGetLastError());
+    HIPCK(hipDeviceSynchronize());
+    std::vector<uint8_t> h((size_t)n * 5);
+    HIPCK(hipMemcpy(h.data(), dout.p, h.size(), hipMemcpyDeviceToHost));
+    uint8_t* const outs[5] = {accepted_filter, accepted_exact, nan_filter, nan_exact, took_exact};
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 5; ++k) outs[k][i] = h[5 * (size_t)i + k];
+    return 0;
+}
+
+// The measured error of the accept test's float32 route: out[0] = max over EVERY float t in [-58, -2^-20] of |(double)exp2_f32(t) / exp2_f64(t) - 1| (one
+// launch), out[1] = max over the n given d of |route(d) / exp(d) - 1| with the device library's exp.
+extern "C" int bpm_selftest_accept_error(int32_t device, int32_t n, const double* d, double out[2]) {
+    if (n <= 0 || !d || !out) return fail("bpm_selftest_accept_error: bad argument");
+    HIPCK(hipSetDevice(device));
+    DevTemp<double> dd;
+    DevTemp<unsigned long long> slots;
+    CK(dd.alloc((size_t)n)); CK(slots.alloc(2));
+    HIPCK(hipMemcpy(dd.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCK(hipMemset(slots.p, 0, 2 * sizeof(unsigned long long)));
+    const float t_small = 0x1p-20f, t_big = 58.0f;
+    uint32_t b_lo, b_hi;
+    std::memcpy(&b_lo, &t_small, 4); std::memcpy(&b_hi, &t_big, 4);
+    hipLaunchKernelGGL(accept_exp2_sweep_kernel, dim3(4096), dim3(256), 0, 0, b_lo, b_hi, slots.p);
+    hipLaunchKernelGGL(accept_route_kernel, dim3(1024), dim3(256), 0, 0, (int)n, dd.p, slots.p + 1);
+    HIPCK(hipGetLastError());
+    HIPCK(hipDeviceSynchronize());
+    unsigned long long h[2];
+    HIPCK(hipMemcpy(h, slots.p, sizeof(h), hipMemcpyDeviceToHost));
+    std::memcpy(out, h, sizeof(h));
     return 0;
 }
 

@@ -65,6 +65,13 @@ int bpm_debug_flavour_counts(bpm_handle_t h, int64_t out[7]);
 int bpm_debug_get_welford(bpm_handle_t h, double* mean, double* m2);
 /* the inline Philox4x32-10 against rocRAND's device engine: n blocks of (seed, subsequence i, block i) from both */
 int bpm_selftest_philox(int32_t device, int32_t n, uint64_t seed, uint32_t* out_mine, uint32_t* out_rocrand);
+/* the update kernels' accept test (bipymc_amd/csrc/accept_test.h) on n pairs (d, u), on the device: its decision and NaN flag, the plain formula's
+ * (exp, clamp, compare, with the device library's exp), and whether its float32 filter asked for the exact path -- one byte per case and array */
+int bpm_selftest_accept(int32_t device, int32_t n, const double* d, const double* u, uint8_t* accepted_filter, uint8_t* accepted_exact,
+                        uint8_t* nan_filter, uint8_t* nan_exact, uint8_t* took_exact);
+/* the measured relative error of that filter's float32 route: out[0] over every float t in [-58, -2^-20] against the library's f64 exp2, out[1] over
+ * the n given d (d -> t -> float -> 2^t) against the library's exp(d) */
+int bpm_selftest_accept_error(int32_t device, int32_t n, const double* d, double out[2]);
 /* per-generation host decisions (flip, shuffle order and its inverse) for generation t */
 int bpm_debug_perm(bpm_handle_t h, int64_t t, int32_t shuffle, double flip_prob, int32_t* out_order, int32_t* out_inverse, int32_t* out_flip);
 
