@@ -165,36 +165,73 @@ struct PushCtrl {
     unsigned long long pad[5];
     unsigned long long probe[MAX_SEG];
 };
+// The argument block of the update kernels.  Its first 248 bytes are the HOT BLOCK: what the planned front of a one-wavefront-per-chain update kernel
+// (phase_fused_kernel, FRONT_CT) gathers in its first scalar round trip, together with the update record.  Every line of the kernarg segment is a first
+// touch there, and scalar loads return out of order: the one wait lasts as long as the slowest line, so the block is packed into as few 64-byte lines
+// as its bytes need.  The block follows the 24 bytes of leading scalar arguments (sampler.hip: FusedKernarg) in a 64-byte-aligned kernarg slot, so
+// the lines end at offsets 40, 104, 168 and 232 of this struct:
+//   [  0, 104)  what every planned flavour reads                                       (with the leading arguments: lines 0 and 1)
+//   [104, 168)  what DREAM adds, the burn-in flavour's additions in its middle         (line 2: thr[0..3] ends it, thr[4..7] no flavour with a front reads)
+//   [168, 232)  what a rank of a world adds (the rest of the Layout, lo), then DE-MC's (line 3)
+//   [232, 248)  the geometry of the burn-in flavour's CR sums, which its workgroups read on every path (the start of line 4)
+// The steady-state DREAM kernel thus reads lines 0-2, DE-MC's 0, 1 and 3, a DREAM rank of a world all four, the burn-in flavour 0-2 and 4 -- the fewest lines their bytes fit
+// (profiles/arg_lines.txt has the table by flavour; tests/test_update_kernel_arg_lines.py holds the kernels to it, sampler.hip pins the offsets).
+// The Layout's members lie apart for it -- G, ld and dim lead the block, the rest is the rank's run: L() puts them together, set_L() takes them apart.
+// The fields are the same in every build variant: what only the test variant or the stamp build has stands at the tail.
 struct PhaseArgs {
-    Layout L;
+    // ---- [0, 104): every planned flavour
+    double* L_G;           // Layout::G, ld, dim (L() below)
+    uint32_t L_ld, L_dim;
     double* ll;            // [n_local] cached ln_like of the local chains (samplers.py:330 re-evaluates it)
+    uint32_t* acc_count;   // [n_local] accepted updates of each local chain in this run (one writer per chain)
+    const double* tparams; // target parameter block
+    unsigned long long* counters;  // [2] = NaN Metropolis ratios (rare; the only atomic)
     double* hist_row;      // [n_local * ld] history row being appended (chain.py:51-54) or nullptr
     double* llhist_row;    // [n_local] or nullptr
+    uint64_t seed;
+    uint64_t t;            // absolute generation
+    uint32_t k;            // generation within this run_mcmc call (demc.py:78)
+    uint32_t upd_off;      // position ranges in shuffle order: upd_off, n_upd, pool_off, M
+    double epsilon;
+    uint32_t wt;                // 1: the dispatch packet of this launch carries NO release fence -- what a later kernel reads (accepted state
+                                // rows, ln-like cache, accept counters) leaves through agent-scope (write-through) stores (store_row_wt)
+    uint32_t hist_by_pos;       // 1: the history row and its ln-like are appended at the update's POSITION in this generation's shuffle order
+                                // (work items of a wavefront write consecutive rows) instead of at the chain's index; the host remembers the
+                                // generation, and rows are put back into chain order when anything reads them (sampler.hip: normalize_history)
+                                // 2: the row by position, its ln-like by chain (while DREAM's outlier check is due every few generations: it sums
+                                // the ln-like history of every chain, see outlier_omega_kernel)
+    // ---- [104, 168): DREAM
+    const double* cr_state;  // p_cr[MAX_CR] | delta_m[MAX_CR] | n_cr_updates[MAX_CR]
+    const double* gamma_tab;    // [dim + 1] DREAM gamma_base by d' (dream.py:61), host-evaluated
+    double u_epsilon;
     double* w_mean;        // Welford moments of each chain's own history (dream.py:128), ONE record per chain: [mean (ld) | m2 (ld)], chain li at w_mean + li * 2 ld;
     double* w_m2;          // w_m2 = w_mean + ld (same stride).  (Two arrays until round 4: two scattered reads and writes per burn-in update where one does.)
-    const double* tparams; // target parameter block
-    const double* cr_state;  // p_cr[MAX_CR] | delta_m[MAX_CR] | n_cr_updates[MAX_CR]
-    unsigned long long* counters;  // [2] = NaN Metropolis ratios (rare; the only atomic)
-    uint32_t* acc_count;   // [n_local] accepted updates of each local chain in this run (one writer per chain)
+    uint32_t cr_gate;      // dream.py:123 history length > n_cr_gen
+    uint32_t hist_len;     // rows of every chain's history before this generation
+    uint32_t thr[MAX_CR];       // mask thresholds floor(CR_m * 2^16) (dream.py:53,113)
+    // ---- [184, 232): a rank of a world, DE-MC
+    uint64_t L_blk;        // Layout::blk, n_local, world, magic (L() below)
+    uint32_t L_n_local, L_world, L_magic;
+    uint32_t lo;
+    double gamma_demc, p_snooker;
+    uint32_t M, pool_off;
+    // ---- [232, 248): the burn-in flavour's level-1 CR sums (line 4, for that flavour alone)
+    uint32_t cr_fold_nb;   // partial sums per array (= their stride): the generation's level-1 sums, or what cr_mid_kernel passes left of them; <= CR_FINAL_MAX
+    uint32_t cr_chunk0, cr_n1;   // first chunk of this half generation, chunks per generation (the stride of the m-major partial arrays)
+    uint32_t adapt_on;     // dream.py:92  burnin_gen > k
+    // ---- the rest: no planned front reads it ahead of its rows
+    uint32_t N, n_upd;
     double* prop_buf;      // host-callback path: [n_local * ld] proposals by work item
     double* aux_buf;       // host-callback path: [log_corr (n_local) | ll_prop (n_local)] by work item (two dense arrays: the ln-likes arrive as ONE dense copy,
                            // host -> device or device -> device; the snooker correction never leaves the device)
     int32_t* ids_buf;      // host-callback path: [n_local] global id by work item (-1 = inactive)
-#ifdef BPM_TEST_HOOKS      // the per-chain decision trace of the parity tests: test variant only (include/bipymc_hip_test.h: bpm_set_trace); the PRODUCT's
-    int32_t* trace_i32;    // argument block has no such fields and its kernels no traced branch (trace_i32_of & co. below are compile-time null there)
-    double* trace_f64;     // [n_local * TRACE_F64]   ([n_local * TRACE_I32] above)
-    uint8_t* trace_mask;   // [n_local * dim]
-#endif
     PermKey pk;
     const uint32_t* perm_tab;   // [N] shuffle order of this generation, position -> chain id (nullptr: evaluate the bijection)
     const uint32_t* inv_tab;    // [N] its inverse, chain id -> position
-    const double* gamma_tab;    // [dim + 1] DREAM gamma_base by d' (dream.py:61), host-evaluated
     const uint32_t* plan;       // [N * PLAN_WORDS] by position in shuffle order: chain id, header block, partner ids of
                                 // this generation, precomputed by plan_kernel (nullptr: drawn in the update kernel)
     const uint32_t* rec_tab;    // what the update kernel reads its records from: `plan` (item w -> record rec_off + w, rec_off =
     uint32_t rec_off;           // upd_off), or this rank's own run of the owner-sorted records of the half generation (rec_off = 0)
-    uint32_t thr[MAX_CR];       // mask thresholds floor(CR_m * 2^16) (dream.py:53,113)
-    unsigned long long* stamps;  // diagnostic build only
     double* pack;               // sparse exchange (world > 1): this rank's block [count u32 | pad | ids[cap] | rows[cap][ld]] or nullptr
     uint32_t pack_cap, pack_nsub, pack_stride;   // per sub-block: capacity (rows), count of sub-blocks, doubles per sub-block          // rows the block can take (even)
     double* x_next;             // mode 2 (synchronous DE-MC): new states go here, the state matrix stays frozen
@@ -217,22 +254,8 @@ struct PhaseArgs {
     // slots -- is stored at the same offset in each of them with system-scope stores; n_peers == 0: no push
     const unsigned long long* peer_tab;
     uint32_t n_peers;
-    uint32_t hist_by_pos;       // 1: the history row and its ln-like are appended at the update's POSITION in this generation's shuffle order
-                                // (work items of a wavefront write consecutive rows) instead of at the chain's index; the host remembers the
-                                // generation, and rows are put back into chain order when anything reads them (sampler.hip: normalize_history)
-                                // 2: the row by position, its ln-like by chain (while DREAM's outlier check is due every few generations: it sums
-                                // the ln-like history of every chain, see outlier_omega_kernel)
-#ifndef BPM_LEAN_LAST
     uint32_t lean;              // 1 (several chains per wavefront, device target, many chains): ln_like of the current state is re-evaluated from the own
                                 // row instead of read from `ll`, `ll` is not written, accepted updates are counted per wavefront (kernels.h: lean_scalars)
-#endif
-    uint32_t wt;                // 1: the dispatch packet of this launch carries NO release fence -- what a later kernel reads (accepted state
-                                // rows, ln-like cache, accept counters) leaves through agent-scope (write-through) stores (store_row_wt)
-    uint64_t seed;
-    uint64_t t;            // absolute generation
-    uint32_t k;            // generation within this run_mcmc call (demc.py:78)
-    uint32_t N, lo;
-    uint32_t upd_off, n_upd, pool_off, M;   // position ranges in shuffle order
     uint32_t mode;         // 0: work item = position (world == 1); 1: work item = local chain filtered by its group;
                            // 2: synchronous DE-MC (samplers.py:261-308): every local chain, pool = all OTHER chains
     uint32_t n_items;
@@ -245,15 +268,21 @@ struct PhaseArgs {
     const double* cr_fold_part;
     const double* cr_fold_tot;
     double* cr_fold_out;
-    uint32_t cr_fold_nb;   // partial sums per array (= their stride): the generation's level-1 sums, or what cr_mid_kernel passes left of them; <= CR_FINAL_MAX
-    uint32_t cr_chunk0, cr_n1;   // first chunk of this half generation, chunks per generation (the stride of the m-major partial arrays)
-    uint32_t adapt_on;     // dream.py:92  burnin_gen > k
-    uint32_t cr_gate;      // dream.py:123 history length > n_cr_gen
-    uint32_t hist_len;     // rows of every chain's history before this generation
-    double gamma_scale, gamma_demc, epsilon, u_epsilon, p_snooker;
-#ifdef BPM_LEAN_LAST
-    uint32_t lean, pad_lean;
+    double gamma_scale;
+    unsigned long long* stamps;  // diagnostic build only
+#ifdef BPM_TEST_HOOKS      // the per-chain decision trace of the parity tests: test variant only (include/bipymc_hip_test.h: bpm_set_trace); the PRODUCT's
+    int32_t* trace_i32;    // argument block has no such fields and its kernels no traced branch (trace_i32_of & co. below are compile-time null there)
+    double* trace_f64;     // [n_local * TRACE_F64]   ([n_local * TRACE_I32] above)
+    uint8_t* trace_mask;   // [n_local * dim]
 #endif
+    __host__ __device__ __forceinline__ Layout L() const {
+        Layout l;
+        l.G = L_G; l.blk = L_blk; l.n_local = L_n_local; l.ld = L_ld; l.dim = L_dim; l.world = L_world; l.magic = L_magic;
+        return l;
+    }
+    __host__ __device__ __forceinline__ void set_L(const Layout& l) {
+        L_G = l.G; L_blk = l.blk; L_n_local = l.n_local; L_ld = l.ld; L_dim = l.dim; L_world = l.world; L_magic = l.magic;
+    }
 };
 
 // The trace pointers of an argument block: fields of the test variant only (-DBPM_TEST_HOOKS); in the product library these are compile-time null
@@ -843,7 +872,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
     // RL path below: 25.9 vs 19.8 us/generation at cfg2.)
     constexpr bool FAST = (NP > 0) && (LPC == 1);
     constexpr bool SNK_DIRECT = (LPC == 1);
-    const uint32_t dim = a.L.dim, ld = a.L.ld;
+    const uint32_t dim = a.L().dim, ld = a.L().ld;
     const uint32_t P = NP > 0 ? (uint32_t)NP : a.P;
     // state-dependent loads first: they overlap with all the draw arithmetic below
     if constexpr (FRONT) {
@@ -851,7 +880,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #pragma unroll
         for (int s = 0; s < DPL; ++s) wk.x[s] = in_row ? fr->x[s] : 0.0;
     } else
-    load_row<LPC, DPL>(row_ptr(a.L, c), q, ld, wk.x);      // (a non-temporal load of this read-once row measured no faster)
+    load_row<LPC, DPL>(row_ptr(a.L(), c), q, ld, wk.x);      // (a non-temporal load of this read-once row measured no faster)
     wk.ll_cur = 0.0;
     wk.acc_prev = 0u;
     if (!a.replay) {
@@ -1045,11 +1074,11 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #pragma unroll
         for (int p = 0; p < NP; ++p) {             // all 2 NP row loads in flight together
             if (LPC == WAVE) {
-                load_row_all<LPC, DPL>(row_ptr(a.L, part.get(2 * p)), q, ld, ra[p]);
-                load_row_all<LPC, DPL>(row_ptr(a.L, part.get(2 * p + 1)), q, ld, rb[p]);
+                load_row_all<LPC, DPL>(row_ptr(a.L(), part.get(2 * p)), q, ld, ra[p]);
+                load_row_all<LPC, DPL>(row_ptr(a.L(), part.get(2 * p + 1)), q, ld, rb[p]);
             } else {
-                load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p)), q, ld, ra[p]);
-                load_row<LPC, DPL>(row_ptr(a.L, part.get(2 * p + 1)), q, ld, rb[p]);
+                load_row<LPC, DPL>(row_ptr(a.L(), part.get(2 * p)), q, ld, ra[p]);
+                load_row<LPC, DPL>(row_ptr(a.L(), part.get(2 * p + 1)), q, ld, rb[p]);
             }
         }
     }
@@ -1170,8 +1199,8 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #pragma unroll 1
             for (uint32_t p = 0; p < P; ++p) {
                 double ra[DPL], rb[DPL];
-                load_row<LPC, DPL>(row_ptr(a.L, part.lds[2 * p]), q, ld, ra);
-                load_row<LPC, DPL>(row_ptr(a.L, part.lds[2 * p + 1]), q, ld, rb);
+                load_row<LPC, DPL>(row_ptr(a.L(), part.lds[2 * p]), q, ld, ra);
+                load_row<LPC, DPL>(row_ptr(a.L(), part.lds[2 * p + 1]), q, ld, rb);
 #pragma unroll
                 for (int s = 0; s < DPL; ++s) sum[s] = (p == 0) ? (ra[s] - rb[s]) : (sum[s] + (ra[s] - rb[s]));
             }
@@ -1220,16 +1249,16 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 #pragma unroll
             for (int s = 0; s < DPL; ++s) { ra[s] = in_row ? fr->ra[0][s] : 0.0; rb[s] = in_row ? fr->rb[0][s] : 0.0; }
         } else {
-        load_row<LPC, DPL>(row_ptr(a.L, ca), q, ld, ra);
-        load_row<LPC, DPL>(row_ptr(a.L, cb), q, ld, rb);
+        load_row<LPC, DPL>(row_ptr(a.L(), ca), q, ld, ra);
+        load_row<LPC, DPL>(row_ptr(a.L(), cb), q, ld, rb);
         }
         double rz[DPL], r1[DPL], r2[DPL];
 #pragma unroll
         for (int s = 0; s < DPL; ++s) { rz[s] = 0.0; r1[s] = 0.0; r2[s] = 0.0; }
         if (do_snk) {
-            load_row<LPC, DPL>(row_ptr(a.L, SNK_DIRECT ? snk_id[0] : part.lds[2]), q, ld, rz);
-            load_row<LPC, DPL>(row_ptr(a.L, SNK_DIRECT ? snk_id[1] : part.lds[3]), q, ld, r1);
-            load_row<LPC, DPL>(row_ptr(a.L, SNK_DIRECT ? snk_id[2] : part.lds[4]), q, ld, r2);
+            load_row<LPC, DPL>(row_ptr(a.L(), SNK_DIRECT ? snk_id[0] : part.lds[2]), q, ld, rz);
+            load_row<LPC, DPL>(row_ptr(a.L(), SNK_DIRECT ? snk_id[1] : part.lds[3]), q, ld, r1);
+            load_row<LPC, DPL>(row_ptr(a.L(), SNK_DIRECT ? snk_id[2] : part.lds[4]), q, ld, r2);
         }
         early(wk);
 #pragma unroll
@@ -1302,7 +1331,7 @@ __device__ __forceinline__ void make_proposal(const PhaseArgs& a, uint32_t c, bo
 template <int ALGO, int LPC, int DPL, int LEAN = 0 /* 0 never, 1 when a.lean, 2 always */, bool CRP_W = false>
 __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bool active, int q,
                                               const Work<DPL>& wk, double ll_prop) {
-    const uint32_t ld = a.L.ld;
+    const uint32_t ld = a.L().ld;
     const uint32_t li = c - a.lo;
     const double ll_cur = wk.ll_cur;
     const double d_acc = (ll_prop + wk.log_corr) - ll_cur;
@@ -1317,7 +1346,7 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     if (lean) {      // one counter bump per wavefront (all lanes are still here): acc_count[n_local + shard]
         const unsigned long long m = __ballot(active && accepted && q == 0);
         if ((threadIdx.x & (WAVE - 1)) == 0 && m != 0ull)
-            __hip_atomic_fetch_add(&a.acc_count[a.L.n_local + ((blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x / WAVE)) & (ACC_SHARDS - 1))],
+            __hip_atomic_fetch_add(&a.acc_count[a.L().n_local + ((blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x / WAVE)) & (ACC_SHARDS - 1))],
                                    (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (!active) return;
@@ -1350,16 +1379,16 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     } else if (accepted) {
         // (lean: the ln-like cache is not written -- nothing on this path reads it, the host refreshes it on demand)
         if (a.wt == 2u) {
-            store_row_wt16<LPC, DPL>(row_ptr(a.L, c), q, ld, nv);
+            store_row_wt16<LPC, DPL>(row_ptr(a.L(), c), q, ld, nv);
 #if defined(BPM_TEST_HOOKS) && defined(BPM_FAKE_NO_LL)
             if (LPC < WAVE) {} else
 #endif
             if (q == 0 && !lean) __hip_atomic_store(&a.ll[li], new_ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (a.wt) {
-            store_row_wt<LPC, DPL>(row_ptr(a.L, c), q, ld, nv);
+            store_row_wt<LPC, DPL>(row_ptr(a.L(), c), q, ld, nv);
             if (q == 0 && !lean) __hip_atomic_store(&a.ll[li], new_ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            store_row<LPC, DPL>(row_ptr(a.L, c), q, ld, nv);
+            store_row<LPC, DPL>(row_ptr(a.L(), c), q, ld, nv);
             if (q == 0 && !lean) a.ll[li] = new_ll;
         }
     }
@@ -1381,11 +1410,11 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
     }
     if (a.n_peers) {
         // push exchange: the owner writes what changed into every other rank's replica (same offsets: the replicas have one layout)
-        const uint32_t row_off = (uint32_t)(row_ptr(a.L, c) - a.L.G);
+        const uint32_t row_off = (uint32_t)(row_ptr(a.L(), c) - a.L().G);
         // CR statistics of EVERY update travel during burn-in (dream.py:92) -- once the gate of dream.py:123 is open: before that nobody reduces
         // them (sampler.hip: gen_cr_reduce), and the first generation behind the gate rewrites every chain's slots in every replica
         const bool slots = ALGO == ALGO_DREAM && a.adapt_on && a.cr_gate && q == 0;
-        const uint32_t d_off = (uint32_t)(delta_ptr(a.L, c) - a.L.G), c_off = (uint32_t)(cridx_ptr(a.L, c) - a.L.G);
+        const uint32_t d_off = (uint32_t)(delta_ptr(a.L(), c) - a.L().G), c_off = (uint32_t)(cridx_ptr(a.L(), c) - a.L().G);
         const bool gated = a.adapt_on && a.cr_gate;
 #pragma unroll 1
         for (uint32_t p = 0; p < a.n_peers; ++p) {
@@ -1434,11 +1463,11 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
         if (q == 0 && a.adapt_on && !(CRP_W && a.cr_part1 != nullptr)) {      // (structural: a flavour that cannot write level 1 ALWAYS writes the slots)
             const bool gated = a.adapt_on && a.cr_gate;
             if (a.wt) {
-                __hip_atomic_store(delta_ptr(a.L, c), gated ? wk.delta : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(cridx_ptr(a.L, c), gated ? (double)wk.cr_idx : -1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(delta_ptr(a.L(), c), gated ? wk.delta : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(cridx_ptr(a.L(), c), gated ? (double)wk.cr_idx : -1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                *delta_ptr(a.L, c) = gated ? wk.delta : 0.0;
-                *cridx_ptr(a.L, c) = gated ? (double)wk.cr_idx : -1.0;
+                *delta_ptr(a.L(), c) = gated ? wk.delta : 0.0;
+                *cridx_ptr(a.L(), c) = gated ? (double)wk.cr_idx : -1.0;
             }
         }
     }
@@ -1471,12 +1500,12 @@ __device__ __forceinline__ void finish_update(const PhaseArgs& a, uint32_t c, bo
 template <int LPC>
 __device__ __forceinline__ void pin_args(const PhaseArgs& a) {
     if (LPC != WAVE) {
-        asm volatile("" ::"s"(a.L.G), "s"(a.L.ld), "s"(a.L.dim), "s"(a.ll), "s"(a.hist_row), "s"(a.llhist_row), "s"(a.tparams),
+        asm volatile("" ::"s"(a.L().G), "s"(a.L().ld), "s"(a.L().dim), "s"(a.ll), "s"(a.hist_row), "s"(a.llhist_row), "s"(a.tparams),
                      "s"(a.cr_state), "s"(a.acc_count), "s"(a.perm_tab), "s"(a.inv_tab), "s"(a.gamma_tab), "s"(a.plan), "s"(a.pack),
                      "s"(a.thr[0]), "s"(a.thr[1]), "s"(a.thr[2]), "s"(a.seed), "s"(a.t), "s"(a.k), "s"(a.N),
                      "s"(a.lo), "s"(a.upd_off), "s"(a.n_upd), "s"(a.pool_off), "s"(a.M), "s"(a.mode), "s"(a.n_items), "s"(a.n_cr));
-        asm volatile("" ::"s"(a.adapt_on), "s"(a.cr_gate), "s"(a.hist_len), "s"(a.epsilon), "s"(a.u_epsilon), "s"(a.L.n_local),
-                     "s"(a.L.world), "s"(a.L.magic), "s"(a.counters), "s"(a.pack_cap), "s"(a.pack_nsub), "s"(a.pack_stride));
+        asm volatile("" ::"s"(a.adapt_on), "s"(a.cr_gate), "s"(a.hist_len), "s"(a.epsilon), "s"(a.u_epsilon), "s"(a.L().n_local),
+                     "s"(a.L().world), "s"(a.L().magic), "s"(a.counters), "s"(a.pack_cap), "s"(a.pack_nsub), "s"(a.pack_stride));
     }
 }
 
@@ -1522,12 +1551,60 @@ __host__ inline Flavour choose_flavour(const PhaseArgs& a, bool dream, bool can_
     if (!(a.mode == 0 && (a.rec_tab != nullptr) == plan && trace_i32_of(a) == nullptr && a.pack == nullptr && a.x_next == nullptr && a.epsilon > 0.0 &&
           a.perm_tab != nullptr && a.inv_tab != nullptr && a.replay == 0 && (!dream || (a.u_epsilon > 0.0 && a.n_cr == 3))))
         return FLAVOUR_GENERAL;
-    const bool single = a.n_peers == 0 && a.L.world == 1 && a.lo == 0 && stamps_allow_hot(a) && a.accbits == nullptr;
+    const bool single = a.n_peers == 0 && a.L().world == 1 && a.lo == 0 && stamps_allow_hot(a) && a.accbits == nullptr;
     if (single && a.adapt_on == 0) return plan ? FLAVOUR_STEADY_PLAN : FLAVOUR_STEADY;
-    if (plan && a.adapt_on == 0 && a.L.world > 1 && a.stamps == nullptr && (a.accbits != nullptr || a.n_peers > 0)) return FLAVOUR_SHARD_PLAN;
+    if (plan && a.adapt_on == 0 && a.L().world > 1 && a.stamps == nullptr && (a.accbits != nullptr || a.n_peers > 0)) return FLAVOUR_SHARD_PLAN;
     if (single && a.adapt_on != 0 && dream) return plan ? FLAVOUR_ADAPT_PLAN : FLAVOUR_ADAPT;
     return FLAVOUR_GENERAL;
 }
+// The hot block of an argument block (PhaseArgs) as the planned front reads it: whole vectors over its runs -- the widest scalar loads that cover them,
+// one or two per kernarg line instead of one per field or pair of fields -- and the fields taken from the vectors' words afterwards.  A pointer made of
+// two words is given its address space by hand (global: what the compiler infers for a pointer it loads from the kernarg segment as a pointer).
+typedef uint32_t bpm_hot16 __attribute__((ext_vector_type(16), aligned(8)));
+typedef uint32_t bpm_hot8 __attribute__((ext_vector_type(8), aligned(8)));
+typedef uint32_t bpm_hot4 __attribute__((ext_vector_type(4), aligned(8)));
+typedef uint32_t bpm_hot2 __attribute__((ext_vector_type(2), aligned(8)));
+constexpr int HOT_BLOCK_BYTES = 248;
+template <class V, int OFF>
+__device__ __forceinline__ V hot_read(const PhaseArgs& a) {
+    static_assert(OFF % 8 == 0 && OFF + (int)sizeof(V) <= HOT_BLOCK_BYTES, "a run of the hot block");
+    return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(&a) + OFF);
+}
+struct HotWords {
+    uint32_t w[HOT_BLOCK_BYTES / 4];      // the block's words, zero where the flavour loads nothing (constant indices only: registers)
+#define BPM_HOT_SET(V, N) template <int OFF> __device__ __forceinline__ void set(V v) { _Pragma("unroll") for (int i = 0; i < N; ++i) w[OFF / 4 + i] = v[i]; }
+    BPM_HOT_SET(bpm_hot16, 16) BPM_HOT_SET(bpm_hot8, 8) BPM_HOT_SET(bpm_hot4, 4) BPM_HOT_SET(bpm_hot2, 2)
+#undef BPM_HOT_SET
+    template <class T>
+    __device__ __forceinline__ T* ptr(int off) const {
+        typedef __attribute__((address_space(1))) T GT;
+        return (T*)(GT*)(((unsigned long long)w[off / 4 + 1] << 32) | w[off / 4]);
+    }
+    __device__ __forceinline__ uint64_t u64(int off) const { return ((uint64_t)w[off / 4 + 1] << 32) | w[off / 4]; }
+    __device__ __forceinline__ double f64(int off) const { return __hiloint2double((int)w[off / 4 + 1], (int)w[off / 4]); }
+    __device__ __forceinline__ uint32_t u32(int off) const { return w[off / 4]; }
+#define BPM_HOT_OFF(f) ((int)__builtin_offsetof(PhaseArgs, f))
+    // the fields of a flavour's runs into an argument block (every field the flavour's vectors cover and a kernel reads: none is left to a load of its own)
+    template <bool DREAM, bool ADAPT, bool SHARD>
+    __device__ __forceinline__ void put(PhaseArgs& a) const {
+        a.L_G = ptr<double>(BPM_HOT_OFF(L_G)); a.L_ld = u32(BPM_HOT_OFF(L_ld)); a.L_dim = u32(BPM_HOT_OFF(L_dim));
+        a.ll = ptr<double>(BPM_HOT_OFF(ll)); a.acc_count = ptr<uint32_t>(BPM_HOT_OFF(acc_count)); a.tparams = ptr<const double>(BPM_HOT_OFF(tparams));
+        a.counters = ptr<unsigned long long>(BPM_HOT_OFF(counters)); a.hist_row = ptr<double>(BPM_HOT_OFF(hist_row)); a.llhist_row = ptr<double>(BPM_HOT_OFF(llhist_row));
+        a.seed = u64(BPM_HOT_OFF(seed)); a.t = u64(BPM_HOT_OFF(t)); a.k = u32(BPM_HOT_OFF(k)); a.upd_off = u32(BPM_HOT_OFF(upd_off));
+        a.epsilon = f64(BPM_HOT_OFF(epsilon)); a.wt = u32(BPM_HOT_OFF(wt)); a.hist_by_pos = u32(BPM_HOT_OFF(hist_by_pos));
+        if (DREAM) {
+            a.cr_state = ptr<const double>(BPM_HOT_OFF(cr_state)); a.gamma_tab = ptr<const double>(BPM_HOT_OFF(gamma_tab)); a.u_epsilon = f64(BPM_HOT_OFF(u_epsilon));
+#pragma unroll
+            for (int m = 0; m < 4; ++m) a.thr[m] = w[BPM_HOT_OFF(thr) / 4 + m];
+        } else {
+            a.gamma_demc = f64(BPM_HOT_OFF(gamma_demc)); a.p_snooker = f64(BPM_HOT_OFF(p_snooker)); a.M = u32(BPM_HOT_OFF(M)); a.pool_off = u32(BPM_HOT_OFF(pool_off));
+        }
+        if (ADAPT) {
+            a.w_mean = ptr<double>(BPM_HOT_OFF(w_mean)); a.w_m2 = ptr<double>(BPM_HOT_OFF(w_m2)); a.cr_gate = u32(BPM_HOT_OFF(cr_gate)); a.hist_len = u32(BPM_HOT_OFF(hist_len));
+        }
+        if (SHARD) { a.L_n_local = u32(BPM_HOT_OFF(L_n_local)); a.L_world = u32(BPM_HOT_OFF(L_world)); a.L_magic = u32(BPM_HOT_OFF(L_magic)); a.lo = u32(BPM_HOT_OFF(lo)); }
+    }
+};
 constexpr bool flavour_is_steady(int f) { return f == FLAVOUR_STEADY_PLAN || f == FLAVOUR_STEADY; }
 template <int ALGO, int TARGET, int LPC, int DPL, int NP, int HOT = 0>
 __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kernel(
@@ -1574,53 +1651,63 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     PlanFront<DPL, (NP > 0 ? NP : 1)> fr;
     uint32_t f_c = 0u;
     const uint32_t* f_rec = nullptr;
+    HotWords hw = {};
+    bpm_hot4 v_cg = {};      // (the burn-in flavour: the geometry of its CR sums)
     Layout f_L = {};
-    double *f_ll = nullptr, *f_wm = nullptr, *f_w2 = nullptr;
+    double* f_ll = nullptr;
     const double *f_crs = nullptr, *f_tp = nullptr, *f_gt = nullptr;
     uint32_t* f_acc = nullptr;
-    unsigned long long* f_cnt = nullptr;
     uint32_t f_lo = 0u;
     typename Target<TARGET, LPC, DPL>::Consts tc_front;
     if constexpr (FRONT_CT) {
         // ONE scalar round trip: the record and every field of the argument block the update reads on its way to the accept test leave together, over a
         // memory system that is still idle.  (A scalar load issued BEHIND the row requests queues behind 7 KB of row traffic per wavefront, sixteen
-        // wavefronts per CU: measured 1.3 us instead of 0.6, and every scalar wait waits for all of them.)  The fields are inputs of the empty statements
-        // the row stride and the row width pass through: live where the row addresses are made.  Not `volatile`, no memory clobber: a scalar load behind
-        // such a statement becomes a vector load.
-        if (w < pl_n_items) {
-            f_L = a_in.L;
-            if (SHARD) __builtin_assume(f_L.world > 1u); else f_L.world = 1;      // (choose_flavour: a rank of a world)
-            // (a rank of a world reads all of the Layout: its two runs of words as whole vectors, padding included, so that the wide loads the compiler
-            // makes of them have no dead register for another load in flight to be given)
-            typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-            typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-            u32x4_a4 lw4 = {0u, 0u, 0u, 0u};
-            u32x2_a4 lw2 = {0u, 0u};
-            if (SHARD) {
-                lw4 = *reinterpret_cast<const u32x4_a4*>(&a_in.L.n_local);
-                lw2 = *reinterpret_cast<const u32x2_a4*>(&a_in.L.magic);
-                f_L.n_local = lw4.x; f_L.ld = lw4.y; f_L.dim = lw4.z; f_L.world = lw4.w; f_L.magic = lw2.x;
-                __builtin_assume(f_L.world > 1u);
+        // wavefronts per CU: measured 1.3 us instead of 0.6, and every scalar wait waits for all of them.)  The block's runs are inputs of the empty statement
+        // the record passes through: live where the row addresses are made.  Not `volatile`, no memory clobber: a scalar load behind such a statement becomes
+        // a vector load.  Three wide loads over three kernarg lines in the steady-state DREAM kernel, where thirteen loads touched eight lines of a block laid
+        // out by history: +5.0 % chain-updates/s at 1000 generations, +4.2 % over 20 (profiles/arg_lines.txt).
+        // (the block's runs as whole vectors: [0, 64) for every flavour, then what the flavour adds -- PhaseArgs has the map.  Ahead of the branch: a wavefront
+        // without an update leaves at once or, in a burn-in workgroup, goes on to the barrier with the same uniform values -- loaded under the branch they
+        // would meet zeros behind it, forty words in vector registers)
+        const bpm_hot16 v0 = hot_read<bpm_hot16, 0>(a_in);
+        bpm_hot16 v1 = {}, vds = {};
+        bpm_hot8 vc1 = {}, vad = {}, vde = {};
+        bpm_hot4 vth = {}, vsh = {};
+        bpm_hot2 vc2 = {}, vt2 = {};
+        hw.set<0>(v0);
+        if (ALGO == ALGO_DREAM) {
+            v1 = hot_read<bpm_hot16, 64>(a_in); hw.set<64>(v1);
+            if (ADAPT) {
+                vad = hot_read<bpm_hot8, 128>(a_in); vt2 = hot_read<bpm_hot2, 160>(a_in); v_cg = hot_read<bpm_hot4, BPM_HOT_OFF(cr_fold_nb)>(a_in);
+                hw.set<128>(vad); hw.set<160>(vt2);
             }
-            f_ll = a_in.ll; f_acc = a_in.acc_count; f_crs = a_in.cr_state; f_tp = a_in.tparams; f_gt = a_in.gamma_tab; f_cnt = a_in.counters;
-            if (ADAPT) { f_wm = a_in.w_mean; f_w2 = a_in.w_m2; }
-            if (SHARD) f_lo = a_in.lo;
-            const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pl_upd_off + w));
+            else { vth = hot_read<bpm_hot4, 152>(a_in); hw.set<152>(vth); }
+            if (SHARD) { vsh = hot_read<bpm_hot4, 192>(a_in); hw.set<192>(vsh); }
+        } else {
+            vc1 = hot_read<bpm_hot8, 64>(a_in); vc2 = hot_read<bpm_hot2, 96>(a_in); hw.set<64>(vc1); hw.set<96>(vc2);
+            if (SHARD) { vds = hot_read<bpm_hot16, 168>(a_in); hw.set<168>(vds); }
+            else { vde = hot_read<bpm_hot8, 200>(a_in); hw.set<200>(vde); }
+        }
+        // (the work item is the wavefront's: said so, the branch is a scalar one and what is set under it stays in scalar registers behind it)
+        const uint32_t w_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
+        if (w_u < pl_n_items) {
+            PhaseArgs fa = {};
+            hw.template put<ALGO == ALGO_DREAM, ADAPT, SHARD>(fa);
+            f_L = fa.L();
+            if (SHARD) __builtin_assume(f_L.world > 1u); else f_L.world = 1;      // (choose_flavour: a rank of a world)
+            f_lo = fa.lo;
+            f_ll = fa.ll; f_acc = fa.acc_count; f_crs = fa.cr_state; f_tp = fa.tparams; f_gt = fa.gamma_tab;
+            const uint32_t pos = pl_upd_off + w_u;
             f_rec = pl_plan + (uint32_t)(pos * PLAN_WORDS);
             bpm_u32x16 rv = plan_record(f_rec);
             // (the whole record passes through the statement: all sixteen words stay live up to it, so no register of the wide load is handed to another load
             // first, and every row address comes after it; the scheduling barrier keeps the small loads below from being issued, and waited for, ahead of it)
 #ifndef BPM_STAMPS      // (the stamp build: its loads behind the entry stamp are vector loads, no operands for these statements; it keeps the barrier)
-#define BPM_FRONT_ALL "s"(f_L.G), "s"(f_L.ld), "s"(f_L.dim), "s"(f_ll), "s"(f_acc), "s"(f_tp), "s"(f_cnt), "s"(a_in.seed), "s"(a_in.t), "s"(a_in.k), "s"(a_in.upd_off), \
-                      "s"(a_in.epsilon), "s"(a_in.wt), "s"(a_in.hist_by_pos), "s"(a_in.hist_row), "s"(a_in.llhist_row)
-#define BPM_FRONT_DREAM "s"(f_crs), "s"(f_gt), "s"(a_in.u_epsilon), "s"(a_in.thr[0]), "s"(a_in.thr[1]), "s"(a_in.thr[2]), "s"(a_in.thr[3])
-            if (ALGO == ALGO_DREAM && ADAPT) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM, "s"(f_wm), "s"(f_w2), "s"(a_in.cr_gate), "s"(a_in.hist_len));
-            else if (ALGO == ALGO_DREAM && SHARD) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM, "s"(f_lo), "s"(lw4), "s"(lw2));
-            else if (ALGO == ALGO_DREAM) asm("" : "+s"(rv) : BPM_FRONT_ALL, BPM_FRONT_DREAM);
-            else if (SHARD) asm("" : "+s"(rv) : BPM_FRONT_ALL, "s"(a_in.gamma_demc), "s"(a_in.p_snooker), "s"(a_in.M), "s"(a_in.pool_off), "s"(f_lo), "s"(lw4), "s"(lw2));
-            else asm("" : "+s"(rv) : BPM_FRONT_ALL, "s"(a_in.gamma_demc), "s"(a_in.p_snooker), "s"(a_in.M), "s"(a_in.pool_off));
-#undef BPM_FRONT_ALL
-#undef BPM_FRONT_DREAM
+            if (ALGO == ALGO_DREAM && ADAPT) asm("" : "+s"(rv) : "s"(v0), "s"(v1), "s"(vad), "s"(vt2), "s"(v_cg));
+            else if (ALGO == ALGO_DREAM && SHARD) asm("" : "+s"(rv) : "s"(v0), "s"(v1), "s"(vth), "s"(vsh));
+            else if (ALGO == ALGO_DREAM) asm("" : "+s"(rv) : "s"(v0), "s"(v1), "s"(vth));
+            else if (SHARD) asm("" : "+s"(rv) : "s"(v0), "s"(vc1), "s"(vc2), "s"(vds));
+            else asm("" : "+s"(rv) : "s"(v0), "s"(vc1), "s"(vc2), "s"(vde));
 #endif
             __builtin_amdgcn_sched_barrier(0);
             // the chain's own scalars, the target's parameters and the lane's entries of the gamma table just AHEAD of the rows: a few bytes each, first in
@@ -1659,9 +1746,11 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     if (COPY) {
         if constexpr (FRONT_CT) {
             a_hot = a_in;
-            a_hot.L = f_L; a_hot.ll = f_ll; a_hot.acc_count = f_acc; a_hot.cr_state = f_crs; a_hot.tparams = f_tp; a_hot.gamma_tab = f_gt; a_hot.counters = f_cnt;      // (in registers already)
-            if (ADAPT) { a_hot.w_mean = f_wm; a_hot.w_m2 = f_w2; }
-            if (SHARD) a_hot.lo = f_lo;
+            hw.template put<ALGO == ALGO_DREAM, ADAPT, SHARD>(a_hot);      // (in registers already)
+            if (ADAPT) { a_hot.cr_fold_nb = v_cg.x; a_hot.cr_chunk0 = v_cg.y; a_hot.cr_n1 = v_cg.z; }
+            // (what choose_flavour fixes of fields that now come out of the vectors: said of the copy, the assumptions on a_in below no longer reach them)
+            __builtin_assume(a_hot.epsilon > 0.0);
+            if (ALGO == ALGO_DREAM) __builtin_assume(a_hot.u_epsilon > 0.0);
         } else
         a_hot = a_in;
         a_hot.mode = 0u; trace_set(a_hot, nullptr, nullptr, nullptr); a_hot.pack = nullptr;
@@ -1672,7 +1761,7 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
         if (SHARD) a_hot.stamps = nullptr;
 #endif
         if (!ADAPT) a_hot.cr_fold_part = nullptr;
-        if (!SHARD) { a_hot.accbits = nullptr; a_hot.lo = 0; a_hot.L.world = 1; a_hot.acc_by_item = 0u; a_hot.n_peers = 0u; a_hot.peer_tab = nullptr; }
+        if (!SHARD) { a_hot.accbits = nullptr; a_hot.lo = 0; a_hot.L_world = 1; a_hot.acc_by_item = 0u; a_hot.n_peers = 0u; a_hot.peer_tab = nullptr; }
         if (ALGO == ALGO_DREAM) a_hot.n_cr = 3;
         if (NOPLAN) { a_hot.plan = nullptr; a_hot.rec_tab = nullptr; }
     }
@@ -1687,7 +1776,7 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
 #ifndef BPM_STAMPS
         __builtin_assume(a_in.stamps == nullptr);
 #endif
-        if (!SHARD) { __builtin_assume(a_in.lo == 0); __builtin_assume(a_in.L.world == 1); }
+        if (!SHARD) { __builtin_assume(a_in.lo == 0); __builtin_assume(a_in.L_world == 1); }
         __builtin_assume(a_in.epsilon > 0.0);
         __builtin_assume(a_in.perm_tab != nullptr); __builtin_assume(a_in.inv_tab != nullptr);
         if (ALGO == ALGO_DREAM) { __builtin_assume(a_in.u_epsilon > 0.0); __builtin_assume(a_in.n_cr == 3); }
@@ -1764,14 +1853,14 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
     }
   if (run) {
     if (LPC == WAVE) c = __builtin_amdgcn_readfirstlane(c);   // wavefront-uniform: header draws and Feistel walks go to the scalar unit
-    const typename Target<TARGET, LPC, DPL>::Consts tc = FRONT_CT ? tc_front : Target<TARGET, LPC, DPL>::load(q, a.L.dim, a.tparams);
+    const typename Target<TARGET, LPC, DPL>::Consts tc = FRONT_CT ? tc_front : Target<TARGET, LPC, DPL>::load(q, a.L().dim, a.tparams);
     Work<DPL> wk;
     wk.item = w;
     wk.pos_own = a.upd_off + (active ? w : 0u);
     if (LPC == WAVE) wk.pos_own = (uint32_t)__builtin_amdgcn_readfirstlane((int)wk.pos_own);      // uniform: the history row's address stays on the scalar unit
     constexpr bool LEAN = lean_scalars<TARGET, LPC>();
     // (LEAN: ln_like of the current state from the own row == the cached value, bit for bit -- see lean_scalars)
-    const uint32_t dim_early = a.L.dim;      // (captured by value, a few registers: a by-reference capture put one instantiation's constants on the stack)
+    const uint32_t dim_early = a.L().dim;      // (captured by value, a few registers: a by-reference capture put one instantiation's constants on the stack)
     constexpr bool LEAN_CT = LEAN && lean_always<TARGET>();
 #ifdef BPM_STAMPS
     bpm_stamp[1] = 0; BPM_STAMP(1);
@@ -1789,8 +1878,8 @@ __global__ __launch_bounds__(block_for_hot(LPC, HOT, DPL)) void phase_fused_kern
         make_proposal<ALGO, LPC, DPL, NP, 1, NoEarly, FRONT_CT>(a, c, active, q, cw, s_part, wk, rec, stamp_arg, NoEarly(), PcrGiven(), &fr);
     }
     double ll_prop;
-    if constexpr (FRONT_CT && TARGET == TARGET_GAUSS && ALGO == ALGO_DREAM) ll_prop = Target<TARGET_GAUSS, LPC, DPL>::template eval<true>(wk.p, q, a.L.dim, tc);
-    else ll_prop = Target<TARGET, LPC, DPL>::eval(wk.p, q, a.L.dim, tc);
+    if constexpr (FRONT_CT && TARGET == TARGET_GAUSS && ALGO == ALGO_DREAM) ll_prop = Target<TARGET_GAUSS, LPC, DPL>::template eval<true>(wk.p, q, a.L().dim, tc);
+    else ll_prop = Target<TARGET, LPC, DPL>::eval(wk.p, q, a.L().dim, tc);
     BPM_STAMP(5);
     finish_update<ALGO, LPC, DPL, (LEAN_CT ? 2 : (LEAN ? 1 : 0)), CRP>(a, c, active, q, wk, ll_prop);
     if (CRP && active && a.adapt_on && a.cr_gate) { cr_d = wk.delta; cr_i = wk.cr_idx; }      // what finish_update wrote into the chain's slots
@@ -1875,12 +1964,12 @@ __global__ __launch_bounds__(block_for(LPC)) void phase_replay_kernel(const Phas
     } else {
         c = pos_to_chain(a, pos);
     }
-    active = active && (c - a.lo) >= a.L.n_local && a.accbits_all[c] != 0;      // remote, and accepted by its owner
+    active = active && (c - a.lo) >= a.L().n_local && a.accbits_all[c] != 0;      // remote, and accepted by its owner
     if (LPC == WAVE && !active) return;
     if (LPC == WAVE) c = __builtin_amdgcn_readfirstlane(c);
     Work<DPL> wk;
     make_proposal<ALGO, LPC, DPL, NP>(a, c, active, q, cw, s_part, wk, rec);
-    if (active) store_row<LPC, DPL>(row_ptr(a.L, c), q, a.L.ld, wk.p);
+    if (active) store_row<LPC, DPL>(row_ptr(a.L(), c), q, a.L().ld, wk.p);
 }
 
 // Replay with owner-sorted records (one wavefront per chain): one work item per update of the OTHER ranks (the host knows every
@@ -1910,13 +1999,13 @@ __global__ __launch_bounds__(REPLAY_WG) void phase_replay_sorted_kernel(const Ph
     if (r == a_in.seg_me || k >= hi - lo) return;                  // own segment: rows are in place
     const uint32_t e = lo + k;
     const uint32_t* rec = a.rec_sorted + (uint32_t)(e * PLAN_WORDS);
-    const uint32_t acc = a.accbits_all[(uint64_t)r * a.L.n_local + k];     // rank r's k-th update of this half generation
+    const uint32_t acc = a.accbits_all[(uint64_t)r * a.L().n_local + k];     // rank r's k-th update of this half generation
     uint32_t c = rec[0];
     if (acc == 0u) return;
     c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
     Work<DPL> wk;
     make_proposal<ALGO, LPC, DPL, NP>(a, c, true, lane, wv, s_part, wk, rec);
-    store_row<LPC, DPL>(row_ptr(a.L, c), lane, a.L.ld, wk.p);
+    store_row<LPC, DPL>(row_ptr(a.L(), c), lane, a.L().ld, wk.p);
 }
 
 // Host-callback ln_like_fn: proposals out ...  (NP: the pair count as a compile-time constant -- partner ids in registers, one Philox evaluation per lane
@@ -1935,14 +2024,14 @@ __global__ __launch_bounds__(block_for(LPC)) void phase_propose_kernel(const Pha
     Work<DPL> wk;
     make_proposal<ALGO, LPC, DPL, NP>(a, c, active, q, cw, s_part, wk);
     if (!active) return;
-    store_row<LPC, DPL>(a.prop_buf + (uint64_t)w * a.L.ld, q, a.L.ld, wk.p);
+    store_row<LPC, DPL>(a.prop_buf + (uint64_t)w * a.L().ld, q, a.L().ld, wk.p);
     if (q == 0) {
         a.aux_buf[w] = wk.log_corr;
         // CR statistic travels through the exchange slots directly
         if (ALGO == ALGO_DREAM) {
             const bool gated = a.adapt_on && a.cr_gate;
-            *delta_ptr(a.L, c) = gated ? wk.delta : 0.0;
-            *cridx_ptr(a.L, c) = gated ? (double)wk.cr_idx : -1.0;
+            *delta_ptr(a.L(), c) = gated ? wk.delta : 0.0;
+            *cridx_ptr(a.L(), c) = gated ? (double)wk.cr_idx : -1.0;
         }
     }
 }
@@ -1959,23 +2048,23 @@ __global__ __launch_bounds__(block_for(LPC)) void phase_commit_kernel(const Phas
     if (LPC == WAVE && !active) return;
     const uint32_t c = active ? (uint32_t)id : a.lo;
     Work<DPL> wk;
-    load_row<LPC, DPL>(row_ptr(a.L, c), q, a.L.ld, wk.x);
-    load_row<LPC, DPL>(a.prop_buf + (uint64_t)(active ? w : 0u) * a.L.ld, q, a.L.ld, wk.p);
+    load_row<LPC, DPL>(row_ptr(a.L(), c), q, a.L().ld, wk.x);
+    load_row<LPC, DPL>(a.prop_buf + (uint64_t)(active ? w : 0u) * a.L().ld, q, a.L().ld, wk.p);
     wk.log_corr = active ? a.aux_buf[w] : 0.0;
     wk.ll_cur = a.ll[c - a.lo];
     wk.acc_prev = a.acc_count[c - a.lo];
     if (ALGO == ALGO_DREAM && a.adapt_on) {
-        load_row<LPC, DPL>(a.w_mean + (uint32_t)((c - a.lo) * 2u * a.L.ld), q, a.L.ld, wk.w_mean);
-        load_row<LPC, DPL>(a.w_m2 + (uint32_t)((c - a.lo) * 2u * a.L.ld), q, a.L.ld, wk.w_m2);
+        load_row<LPC, DPL>(a.w_mean + (uint32_t)((c - a.lo) * 2u * a.L().ld), q, a.L().ld, wk.w_mean);
+        load_row<LPC, DPL>(a.w_m2 + (uint32_t)((c - a.lo) * 2u * a.L().ld), q, a.L().ld, wk.w_m2);
     }
-    const double ll_prop = active ? a.aux_buf[a.L.n_local + w] : 0.0;
+    const double ll_prop = active ? a.aux_buf[a.L().n_local + w] : 0.0;
     const u32x4 h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
     wk.u_acc = u01_53(h0.z, h0.w);
     wk.delta = 0.0; wk.gamma = 0.0; wk.cr_idx = -1; wk.d_prime = 0; wk.jump = 0; wk.snk = 0; wk.maskbits = 0; wk.item = w; wk.pos_own = 0u;
     // finish_update rewrites the CR slots: carry the values written by the propose kernel
     if (ALGO == ALGO_DREAM && active) {
-        wk.delta = *delta_ptr(a.L, c);
-        wk.cr_idx = (int)*cridx_ptr(a.L, c);
+        wk.delta = *delta_ptr(a.L(), c);
+        wk.cr_idx = (int)*cridx_ptr(a.L(), c);
     }
     PhaseArgs b = a;
     if (ALGO == ALGO_DREAM) b.cr_gate = (wk.cr_idx >= 0) ? 1u : 0u;

@@ -142,8 +142,8 @@ __device__ __forceinline__ void wide_pair_proposal(const PhaseArgs& a, const Wid
             double2 ra[NP > 0 ? NP : 1], rb[NP > 0 ? NP : 1];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {                              // all 2 NP row loads in flight together
-                ra[p] = wide_load2(row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2 * p)), pi, valid);
-                rb[p] = wide_load2(row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2 * p + 1)), pi, valid);
+                ra[p] = wide_load2(row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 2 * p)), pi, valid);
+                rb[p] = wide_load2(row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 2 * p + 1)), pi, valid);
             }
             s0 = ra[0].x - rb[0].x; s1 = ra[0].y - rb[0].y;
 #pragma unroll
@@ -151,8 +151,8 @@ __device__ __forceinline__ void wide_pair_proposal(const PhaseArgs& a, const Wid
         } else {
 #pragma unroll 1
             for (uint32_t p = 0; p < U.P; ++p) {
-                const double2 ra = wide_load2(row_ptr(a.L, (uint32_t)__shfl((int)mine, (int)(2u * p))), pi, valid);
-                const double2 rb = wide_load2(row_ptr(a.L, (uint32_t)__shfl((int)mine, (int)(2u * p + 1u))), pi, valid);
+                const double2 ra = wide_load2(row_ptr(a.L(), (uint32_t)__shfl((int)mine, (int)(2u * p))), pi, valid);
+                const double2 rb = wide_load2(row_ptr(a.L(), (uint32_t)__shfl((int)mine, (int)(2u * p + 1u))), pi, valid);
                 s0 = (p == 0) ? (ra.x - rb.x) : (s0 + (ra.x - rb.x));
                 s1 = (p == 0) ? (ra.y - rb.y) : (s1 + (ra.y - rb.y));
             }
@@ -162,14 +162,14 @@ __device__ __forceinline__ void wide_pair_proposal(const PhaseArgs& a, const Wid
         p0 = (mbits & 1u) ? (jump0 + x.x) : x.x;
         p1 = (mbits & 2u) ? (jump1 + x.y) : x.y;
     } else if (!U.snk) {                                                  // demc.py:161-182
-        const double2 ra = wide_load2(row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 0)), pi, valid);
-        const double2 rb = wide_load2(row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 1)), pi, valid);
+        const double2 ra = wide_load2(row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 0)), pi, valid);
+        const double2 rb = wide_load2(row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 1)), pi, valid);
         double q0 = U.gamma * (ra.x - rb.x), q1 = U.gamma * (ra.y - rb.y);
         q0 = q0 + x.x; q1 = q1 + x.y;
         q0 = q0 + en0; q1 = q1 + en1;
         p0 = q0; p1 = q1;
     } else {                                                              // snooker (ter Braak & Vrugt 2008): along x - z
-        const double2 rz = wide_load2(row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2)), pi, valid);
+        const double2 rz = wide_load2(row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 2)), pi, valid);
         double q0 = x.x + U.gs * (x.x - rz.x), q1 = x.y + U.gs * (x.y - rz.y);
         q0 = q0 + en0; q1 = q1 + en1;
         p0 = (j0 < U.dim) ? q0 : x.x;
@@ -207,11 +207,11 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
     if (!FUSED && lane == 0) a.ids_buf[w] = (int32_t)c;
     const uint32_t li = c - a.lo;
     WideUni U;
-    U.dim = a.L.dim; U.ld = a.L.ld; U.P = NP > 0 ? (uint32_t)NP : a.P;
+    U.dim = a.L().dim; U.ld = a.L().ld; U.P = NP > 0 ? (uint32_t)NP : a.P;
     U.thr = 65536u; U.forced = U.dim; U.epsilon = a.epsilon; U.u_epsilon = a.u_epsilon; U.snk = 0; U.gs = 0.0;
     const uint32_t npairs = (U.dim + 1u) >> 1;
     const uint32_t n_chunks = (npairs + WIDE_CHUNK_PAIRS - 1u) / WIDE_CHUNK_PAIRS;
-    const double* xrow = row_ptr(a.L, c);
+    const double* xrow = row_ptr(a.L(), c);
     // ---- header block, partner chains (one lane per partner: dream.py:62-66 / demc.py:169; snooker: three more)
     const u32x4 h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
     const bool snk_possible = !DREAM && a.p_snooker > 0.0 && a.M >= 3;
@@ -271,9 +271,9 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
     // ---- snooker: pass S
     double sn_n2 = 0.0;
     if (snk_possible && u_sel < a.p_snooker) {
-        const double* zrow = row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2));
-        const double* r1row = row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 3));
-        const double* r2row = row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 4));
+        const double* zrow = row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 2));
+        const double* r1row = row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 3));
+        const double* r2row = row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 4));
         double n2 = 0.0, dot = 0.0;
 #pragma unroll 1
         for (uint32_t k = 0; k < n_chunks; ++k) {
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
     const double* m2row = a.w_m2 + (uint32_t)(li * 2u * U.ld);
     double* hrow = (FUSED && a.hist_row) ? a.hist_row + (uint32_t)(li * U.ld) : nullptr;
     double* prow = FUSED ? nullptr : a.prop_buf + (uint64_t)w * U.ld;
-    const double* zrow_b = U.snk ? row_ptr(a.L, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2)) : xrow;
+    const double* zrow_b = U.snk ? row_ptr(a.L(), (uint32_t)__builtin_amdgcn_readlane((int)mine, 2)) : xrow;
 #pragma unroll 1
     for (uint32_t k = 0; k < n_chunks; ++k) {
 #pragma unroll
@@ -348,8 +348,8 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
         if (lane == 0) {
             a.aux_buf[w] = log_corr;
             if (DREAM) {
-                *delta_ptr(a.L, c) = cr_stat ? delta : 0.0;
-                *cridx_ptr(a.L, c) = cr_stat ? (double)cr_idx : -1.0;
+                *delta_ptr(a.L(), c) = cr_stat ? delta : 0.0;
+                *cridx_ptr(a.L(), c) = cr_stat ? (double)cr_idx : -1.0;
             }
         }
         return;
@@ -371,14 +371,14 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
         if (a.llhist_row) a.llhist_row[li] = new_ll;
         if (DREAM && a.adapt_on) {      // (the CR slots are read by the reduction of an adapting generation only: kernels.h finish_update)
             if (a.wt) {
-                __hip_atomic_store(delta_ptr(a.L, c), cr_stat ? delta : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(cridx_ptr(a.L, c), cr_stat ? (double)cr_idx : -1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(delta_ptr(a.L(), c), cr_stat ? delta : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(cridx_ptr(a.L(), c), cr_stat ? (double)cr_idx : -1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                *delta_ptr(a.L, c) = cr_stat ? delta : 0.0;
-                *cridx_ptr(a.L, c) = cr_stat ? (double)cr_idx : -1.0;
+                *delta_ptr(a.L(), c) = cr_stat ? delta : 0.0;
+                *cridx_ptr(a.L(), c) = cr_stat ? (double)cr_idx : -1.0;
             }
             if (a.n_peers && a.adapt_on && a.cr_gate) {              // push exchange: the slots of every update travel during CR adaptation
-                const uint32_t d_off = (uint32_t)(delta_ptr(a.L, c) - a.L.G), c_off = (uint32_t)(cridx_ptr(a.L, c) - a.L.G);
+                const uint32_t d_off = (uint32_t)(delta_ptr(a.L(), c) - a.L().G), c_off = (uint32_t)(cridx_ptr(a.L(), c) - a.L().G);
 #pragma unroll 1
                 for (uint32_t p = 0; p < a.n_peers; ++p) {
                     double* pg = reinterpret_cast<double*>(a.peer_tab[p]);
@@ -397,11 +397,11 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_kernel(
     // ---- pass C
     const bool welford = DREAM && a.adapt_on;
     if (accepted || welford || a.x_next) {
-        double* srow = row_ptr(a.L, c);
+        double* srow = row_ptr(a.L(), c);
         double* nrow = a.x_next ? a.x_next + (uint32_t)(li * U.ld) : nullptr;
         double* wm = a.w_mean + (uint32_t)(li * 2u * U.ld);
         double* w2 = a.w_m2 + (uint32_t)(li * 2u * U.ld);
-        const uint32_t row_off = (uint32_t)(srow - a.L.G);
+        const uint32_t row_off = (uint32_t)(srow - a.L().G);
         const double cntp = (double)(a.hist_len + 1);
 #pragma unroll 1
         for (uint32_t k = 0; k < n_chunks; ++k) {
@@ -458,9 +458,9 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_commit_kernel(const
     const int32_t id = a.ids_buf[w];
     if (id < 0) return;
     const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(id), li = c - a.lo;
-    const uint32_t dim = a.L.dim, ld = a.L.ld, npairs = (dim + 1u) >> 1;
+    const uint32_t dim = a.L().dim, ld = a.L().ld, npairs = (dim + 1u) >> 1;
     const uint32_t n_chunks = (npairs + WIDE_CHUNK_PAIRS - 1u) / WIDE_CHUNK_PAIRS;
-    const double ll_cur = a.ll[li], ll_prop = a.aux_buf[a.L.n_local + w], log_corr = a.aux_buf[w];
+    const double ll_cur = a.ll[li], ll_prop = a.aux_buf[a.L().n_local + w], log_corr = a.aux_buf[w];
     const uint32_t acc_prev = a.acc_count[li];
     const u32x4 h0 = chain_block(a.seed, c, a.t, SLOT_HDR0);
     const double d_acc = (ll_prop + log_corr) - ll_cur;
@@ -475,11 +475,11 @@ __global__ __launch_bounds__(BPM_BLOCK_WAVE) void phase_wide_commit_kernel(const
             trace_i32_of(a)[(uint64_t)li * TRACE_I32 + 3] = accepted ? 1 : 0;
             double* tf = trace_f64_of(a) + (uint64_t)li * TRACE_F64;
             bool nan_alpha;
-            tf[0] = accept_alpha(d_acc, &nan_alpha); tf[1] = ll_prop; tf[2] = DREAM ? *delta_ptr(a.L, c) : 0.0; tf[3] = 0.0;
+            tf[0] = accept_alpha(d_acc, &nan_alpha); tf[1] = ll_prop; tf[2] = DREAM ? *delta_ptr(a.L(), c) : 0.0; tf[3] = 0.0;
         }
     }
     const bool welford = DREAM && a.adapt_on;
-    double* srow = row_ptr(a.L, c);
+    double* srow = row_ptr(a.L(), c);
     const double* prow = a.prop_buf + (uint64_t)w * ld;
     double* hrow = a.hist_row ? a.hist_row + (uint32_t)(li * ld) : nullptr;
     double* nrow = a.x_next ? a.x_next + (uint32_t)(li * ld) : nullptr;

@@ -316,6 +316,19 @@ struct FusedKernarg {
     PhaseArgs a;
 };
 static_assert(offsetof(FusedKernarg, a) == 24 && sizeof(FusedKernarg) == 24 + sizeof(PhaseArgs), "kernarg layout of phase_fused_kernel");
+// The hot block of the argument block (kernels.h: PhaseArgs), pinned: kernarg slots are 64-byte aligned (aql_queue.h: SLOT_BYTES), so behind the 24 bytes
+// of leading arguments the block's lines end at 40, 104, 168 and 232 -- the same offsets in every build variant.
+#define BPM_HOT_AT(field, off) static_assert(offsetof(PhaseArgs, field) == (off), "hot block of PhaseArgs: " #field)
+BPM_HOT_AT(L_G, 0); BPM_HOT_AT(L_ld, 8); BPM_HOT_AT(L_dim, 12); BPM_HOT_AT(ll, 16); BPM_HOT_AT(acc_count, 24); BPM_HOT_AT(tparams, 32); BPM_HOT_AT(counters, 40);
+BPM_HOT_AT(hist_row, 48); BPM_HOT_AT(llhist_row, 56); BPM_HOT_AT(seed, 64); BPM_HOT_AT(t, 72); BPM_HOT_AT(k, 80); BPM_HOT_AT(upd_off, 84); BPM_HOT_AT(epsilon, 88);
+BPM_HOT_AT(wt, 96); BPM_HOT_AT(hist_by_pos, 100);                                                                                  // every planned flavour: lines 0, 1
+BPM_HOT_AT(cr_state, 104); BPM_HOT_AT(gamma_tab, 112); BPM_HOT_AT(u_epsilon, 120); BPM_HOT_AT(w_mean, 128); BPM_HOT_AT(w_m2, 136); BPM_HOT_AT(cr_gate, 144);
+BPM_HOT_AT(hist_len, 148); BPM_HOT_AT(thr, 152);                                                                                   // DREAM, its burn-in: line 2
+BPM_HOT_AT(L_blk, 184); BPM_HOT_AT(L_n_local, 192); BPM_HOT_AT(L_world, 196); BPM_HOT_AT(L_magic, 200); BPM_HOT_AT(lo, 204);
+BPM_HOT_AT(gamma_demc, 208); BPM_HOT_AT(p_snooker, 216); BPM_HOT_AT(M, 224); BPM_HOT_AT(pool_off, 228);                            // a rank of a world, DE-MC: line 3
+#undef BPM_HOT_AT
+static_assert((offsetof(FusedKernarg, a) + offsetof(PhaseArgs, thr) + 4 * sizeof(uint32_t)) % 64 == 0 && (offsetof(FusedKernarg, a) + offsetof(PhaseArgs, pool_off) + sizeof(uint32_t)) % 64 == 0 &&
+              bpm::DirectQueue::SLOT_BYTES % 64 == 0, "the hot block's lines 2 and 3 end on lines of the kernarg segment");
 // One update-kernel dispatch from a ready argument block (a FusedKernarg, or the bare PhaseArgs a run-time module's kernels take) and the counters
 // it moves: as a packet on the library's own queue (k: null = the kernel was not found), the one consumer of a packet's riders -- its fences and
 // its timing signal, what it used cleared ...
@@ -1841,7 +1854,7 @@ static int prepare_generation(bpm_sampler* s, int64_t n_ahead) {
     for (int ph = 0; ph < 2; ++ph) {
         PhaseArgs& a = s->cur_args[ph];
         std::memset(&a, 0, sizeof(a));
-        a.L = s->L;
+        a.set_L(s->L);
         a.ll = s->ll;
         a.hist_row = hist_row;
         a.llhist_row = llhist_row;
