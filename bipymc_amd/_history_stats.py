@@ -68,6 +68,36 @@ class HistoryStatistics(object):
         g0, g1 = _diag.window(n_burn, self.n_chains, eng.history_rows())
         return _dv.DerivedHistory(_rk.ranked_engine(eng, g0, g1, scale=scale, folded=folded, who=who), self.n_chains, self._stats_allgather)
 
+    def param_est_hdi(self, n_burn=0, prob=0.94):
+        """The highest-density interval of every coordinate over param_est(n_burn)[2]: the shortest interval that holds the share `prob` of
+        the draws -- with the S values sorted and m = min(floor(prob * S), S - 1), the first i of the smallest s[i + m] - s[i] gives
+        (s[i], s[i + m]) (summary.py has the definition with its NaN and inf rules).  prob: one probability or up to 8.  One sort of every
+        column on the device and one scan per probability.  Single rank only.  -> summary.PosteriorHDI(lo, hi, prob, n_nan, n)"""
+        from . import rank_diagnostics as _rk
+        from . import summary as _sm
+        who = "param_est_hdi"
+        _rk.check_single_rank(who, getattr(getattr(self, "comm", None), "size", 1))
+        _sm.check_hdi_prob(who, prob)
+        return _sm.compute_hdi(self._stats_engine(who), n_burn, prob, self.n_chains, who=who)
+
+    def posterior_summary(self, n_burn=0, hdi_prob=0.94, prob=(0.05, 0.95), max_lag=None):
+        """The table a Bayesian report prints, per coordinate: mean, sd, the highest-density interval of hdi_prob, median and
+        np.quantile(prob), the Monte Carlo standard errors of mean and sd, ess_mean, ess_sd, ess_bulk, ess_tail, the rank-normalized and the
+        classic R-hat -- all over the split rows of convergence_diagnostics' window, the same draws in every column (n_burn, lags and ESS
+        count stored rows / stored draws of a thinned history).  str() of the result is the table.  Costs what convergence_diagnostics_rank
+        costs plus one sort of the raw columns and a fifth fill of its one scratch handle.  Single rank only.
+        -> summary.PosteriorSummary"""
+        from . import diagnostics as _diag
+        from . import rank_diagnostics as _rk
+        from . import summary as _sm
+        who = "posterior_summary"
+        _rk.check_single_rank(who, getattr(getattr(self, "comm", None), "size", 1))
+        _rk.check_prob(who, prob)
+        _sm.check_hdi_prob(who, hdi_prob)
+        eng = self._stats_engine(who)
+        g0, g1 = _diag.window(check_n_burn(who, n_burn), self.n_chains, eng.history_rows())
+        return _sm.compute(eng, self._stats_allgather, g0, g1, hdi_prob=hdi_prob, prob=prob, max_lag=max_lag, who=who)
+
     def param_est_quantiles(self, n_burn=0, q=(0.05, 0.5, 0.95)):
         """np.quantile(param_est(n_burn)[2], q, axis=0), exactly (an MSD radix select).  -> (len(q), dim), or (dim,) for a scalar q"""
         from . import quantiles as _qs

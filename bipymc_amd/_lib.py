@@ -120,6 +120,7 @@ SIGNATURES = {
     "bpm_derive": (C.c_int, [_H, C.c_int64, _P(C.c_int64), _dp, _P(C.c_int64), _P(C.c_int64), _dp, C.c_int64]),
     "bpm_derive_history": (C.c_int, [_H, _H]),
     "bpm_rank_history": (C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _P(C.c_int64), _dp]),
+    "bpm_hdi": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _P(C.c_int64), _dp, _dp, _P(C.c_int64), _dp, _P(C.c_int64)]),
 }
 
 # include/bipymc_hip_test.h: exported by the test variant only

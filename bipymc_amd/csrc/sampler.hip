@@ -1046,14 +1046,20 @@ static int require_resident_history(const bpm_sampler* s, const char* who) {
 
 // param_est's selection (demc.py:235-248): this rank's rows [lo, hi), lo <= hi, of the super chain (row g*N + i = chain i at generation g)
 // at or after n_burn (negative: 0).  A partial first generation is counted by chain index, so that row is brought into chain order first.
-static int super_chain_window(bpm_sampler* s, int64_t n_burn, uint64_t* lo, uint64_t* hi) {
+// (the bounds alone, nothing launched: *partial_row = the history row of a partial first generation, -1 if there is none)
+static void super_chain_bounds(const bpm_sampler* s, int64_t n_burn, uint64_t* lo, uint64_t* hi, int64_t* partial_row) {
     if (n_burn < 0) n_burn = 0;
     const int64_t g0 = n_burn / s->N;
     int64_t first = n_burn % s->N - (int64_t)s->lo;      // first local chain of generation g0 that counts
     first = std::max<int64_t>(0, std::min<int64_t>(first, s->n_local));
-    if (first != 0 && g0 < s->hist_rows) CK(normalize_history(s, g0, g0 + 1));
+    *partial_row = first != 0 && g0 < s->hist_rows ? g0 : -1;
     *hi = (uint64_t)s->hist_rows * s->n_local;
     *lo = std::min(*hi, (uint64_t)std::min<int64_t>(g0, s->hist_rows) * s->n_local + (g0 < s->hist_rows ? (uint64_t)first : 0));
+}
+static int super_chain_window(bpm_sampler* s, int64_t n_burn, uint64_t* lo, uint64_t* hi) {
+    int64_t partial_row = -1;
+    super_chain_bounds(s, n_burn, lo, hi, &partial_row);
+    if (partial_row >= 0) CK(normalize_history(s, partial_row, partial_row + 1));
     return 0;
 }
 
@@ -4111,21 +4117,124 @@ static hipError_t rank_sort(void* tmp, size_t* tmp_bytes, unsigned long long* in
     return rocprim::segmented_radix_sort_keys(tmp, *tmp_bytes, in, out, bc * S, bc, seg, seg + 1, 0u, 64u, st);
 }
 
+// ---- the one batch loop of whatever reads sorted columns: bpm_rank_history's sorted kinds (the consumer scores) and bpm_hdi (it scans) ---
+// rank_window_checks: S and the order statistics' positions; rank_batches_plan: the batch the scratch budget holds and every allocation;
+// rank_batches_run: per batch of columns the keys, the sort, the picks, then consume(k0, b, kw, n_tiles, nby, sorted) -- the batch's first
+// column and width, rk_keys_kernel's launch shape over it, and its sorted keys [b][S].  Nothing is launched before run.
+struct RankBatches {
+    uint32_t S = 0, dim = 0, bc = 0;
+    int32_t n_pos = 0;
+    size_t tmp_bytes = 0;
+    DevTemp<unsigned long long> keys, d_pos;
+    DevTemp<unsigned char> tmp;
+    DevTemp<double> d_os;
+};
+
+static int rank_window_checks(const std::string& who, uint64_t S64, const char* verb, int32_t n_pos, const int64_t* pos) {
+    if (S64 >= (1ull << 31))
+        return fail(who + ": the window holds " + std::to_string((unsigned long long)S64) + " values per coordinate; fewer than 2^31 can be " + verb);
+    for (int32_t j = 0; j < n_pos; ++j)
+        if (pos[j] < 0 || (uint64_t)pos[j] >= S64)
+            return fail(who + ": order statistic " + std::to_string((long long)pos[j]) + " is outside [0, " + std::to_string((unsigned long long)S64) + ")");
+    return 0;
+}
+
+// the batch: as many columns as the scratch budget holds (keys in | keys out | the sort's temporaries), batch * S < 2^31.
+// The sort gives a column of this length to ONE workgroup, so the columns of a batch are its whole parallelism: at cfg2's shape with 1000
+// generations a z fill takes 24.7 / 6.8 / 2.1 / 1.0 s with batches of 1 / 4 / 16 / 64 columns (profiles/rank_diagnostics_cfg2.txt).  Hence
+// the default budget: a quarter of the free memory.  BPM_RANK_SCRATCH_MB: the budget; BPM_RANK_BATCH_COLS: the batch itself (tests, A/B;
+// both read at every call)
+static int rank_batches_plan(RankBatches& rb, const std::string& who, bpm_sampler* src, uint32_t S, size_t mem_free, int32_t n_pos) {
+    const uint32_t dim = src->dim;
+    rb.S = S; rb.dim = dim; rb.n_pos = n_pos;
+    uint64_t budget = mem_free / 4;
+    if (const char* mb = getenv("BPM_RANK_SCRATCH_MB")) budget = (uint64_t)std::max(atoll(mb), 0ll) << 20;
+    const uint32_t bc_max = std::min<uint32_t>(dim, (uint32_t)(((1ull << 31) - 1) / S));
+    auto need_of = [&](uint32_t b, uint64_t* need) -> int {
+        size_t t = 0;
+        HIPCK(rank_sort(nullptr, &t, nullptr, nullptr, b, S, src->stream));
+        rb.tmp_bytes = t;
+        *need = 2ull * b * S * sizeof(unsigned long long) + t;
+        return 0;
+    };
+    uint64_t need = 0;
+    uint32_t bc = 0;
+    const char* forced = getenv("BPM_RANK_BATCH_COLS");
+    if (forced && atoi(forced) > 0) {
+        bc = std::min<uint32_t>((uint32_t)atoi(forced), bc_max);
+        CK(need_of(bc, &need));
+    } else {
+        bc = (uint32_t)std::min<uint64_t>(bc_max, std::max<uint64_t>(1, budget / (16ull * S)));
+        CK(need_of(bc, &need));
+        while (bc > 1 && need > budget) {
+            bc = std::max<uint32_t>(1, std::min<uint32_t>(bc - 1, (uint32_t)((uint64_t)bc * budget / need)));
+            CK(need_of(bc, &need));
+        }
+        if (need > budget)
+            return fail(who + ": sorting one column of " + std::to_string(S) + " keys needs " + std::to_string((unsigned long long)need) +
+                        " bytes of scratch (keys in, keys out and the sort's temporaries); the budget is " + std::to_string((unsigned long long)budget) +
+                        " bytes (BPM_RANK_SCRATCH_MB; by default a quarter of the free device memory: " + std::to_string(mem_free >> 20) +
+                        " MiB are free)");
+    }
+    rb.bc = bc;
+    const std::string what = "the scratch of " + std::to_string(bc) + " columns of " + std::to_string(S) + " keys";
+    CK(rb.keys.alloc(2 * (size_t)bc * S, who.c_str(), what + " (keys in, keys out)"));
+    CK(rb.tmp.alloc(std::max<size_t>(rb.tmp_bytes, 1), who.c_str(), what + " (the sort's temporaries)"));
+    if (n_pos > 0) {
+        CK(rb.d_os.alloc((size_t)n_pos * dim));
+        CK(rb.d_pos.alloc((size_t)n_pos));
+    }
+    return 0;
+}
+
+template <class Consume>
+static int rank_batches_run(RankBatches& rb, const std::string& who, bpm_sampler* src, const RkWindow& w, bool folded, const double* d_arg, const int64_t* pos,
+                            double* order_stats, Consume&& consume) {
+    const uint32_t S = rb.S, dim = rb.dim, bc = rb.bc;
+    const int32_t n_pos = rb.n_pos;
+    std::vector<unsigned long long> hpos((size_t)n_pos);
+    for (int32_t j = 0; j < n_pos; ++j) hpos[(size_t)j] = (unsigned long long)pos[j];
+    if (n_pos > 0) HIPCK(hipMemcpyAsync(rb.d_pos.p, hpos.data(), hpos.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, src->stream));
+    unsigned long long* k_in = rb.keys.p;
+    unsigned long long* k_out = rb.keys.p + (size_t)bc * S;
+    for (uint32_t k0 = 0; k0 < dim; k0 += bc) {
+        const uint32_t b = std::min(bc, dim - k0);
+        const uint32_t kw = std::min<uint32_t>(b, RK_THREADS), n_tiles = (b + kw - 1) / kw;
+        uint64_t nby = 1;
+        CK(rows_grid(w.S, n_tiles, (uint64_t)(RK_THREADS / kw) * RK_UNR, who.c_str(), &nby));
+        hipLaunchKernelGGL(rk_keys_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, src->ld, w, k0, b, kw,
+                           folded ? 1u : 0u, d_arg, k_in);
+        HIPCK(hipGetLastError());
+        size_t t = rb.tmp_bytes;      // (the temporaries of a full batch hold those of the last, partial one)
+        HIPCK(rank_sort(rb.tmp.p, &t, k_in, k_out, b, S, src->stream));
+        if (n_pos > 0) {
+            hipLaunchKernelGGL(rk_pick_kernel, dim3(((unsigned)n_pos * b + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, src->stream,
+                               (const unsigned long long*)k_out, w.S, k0, b, dim, (const unsigned long long*)rb.d_pos.p, (uint32_t)n_pos, rb.d_os.p);
+            HIPCK(hipGetLastError());
+        }
+        CK(consume(k0, b, kw, n_tiles, nby, (const unsigned long long*)k_out));
+    }
+    if (n_pos > 0) HIPCK(hipMemcpyAsync(order_stats, rb.d_os.p, (size_t)n_pos * dim * sizeof(double), hipMemcpyDeviceToHost, src->stream));
+    return 0;
+}
+
 // A RANKED HISTORY IS A HISTORY: a transform of the split rows of src's history rows [g_lo, g_hi) -- n = (g_hi - g_lo) / 2 rows from g_lo,
 // then n rows up to g_hi -- written into the history of `dst`, a second, ordinary handle as bpm_derive_history takes one, with src's dim.
 // kind RK_RANK: the average rank of a value among the S = 2 n n_local values of its coordinate; RK_Z: its normal score; RK_RANK_FOLDED,
-// RK_Z_FOLDED: the same of |x - arg[k]|; RK_INDICATOR: x <= arg[k].  order_stats[j * dim + k] (sorted kinds): the pos[j]-th smallest value.  dst
+// RK_Z_FOLDED: the same of |x - arg[k]|; RK_INDICATOR: x <= arg[k]; RK_SQDEV: (x - arg[k])^2 (the flat fills: no sort).  order_stats[j * dim + k] (sorted kinds): the pos[j]-th smallest value.  dst
 // comes out as bpm_set_history leaves a handle and may be filled again.  Every check and every allocation of scratch comes before any
 // launch; nothing src's sampler reads is written.
 extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
                                 const int64_t* pos, double* order_stats) {
     const std::string who = "bpm_rank_history";
     CK(second_handle_pair(who, src, dst, "the same dim"));
-    if (kind < RK_RANK || kind > RK_RANK_FOLDED) return fail(who + ": kind must be 0 (rank), 1 (z), 2 (folded z), 3 (indicator) or 4 (folded rank); got " + std::to_string(kind));
-    const bool sorted = kind != RK_INDICATOR;
-    if ((rk_folded(kind) || kind == RK_INDICATOR) && !arg) return fail(who + ": kind " + std::to_string(kind) + " needs arg (one value per coordinate)");
+    if (kind < RK_RANK || kind > RK_SQDEV)
+        return fail(who + ": kind must be 0 (rank), 1 (z), 2 (folded z), 3 (indicator), 4 (folded rank) or 5 (squared deviation); got " + std::to_string(kind));
+    const bool flat = kind == RK_INDICATOR || kind == RK_SQDEV, sorted = !flat;
+    if ((rk_folded(kind) || flat) && !arg) return fail(who + ": kind " + std::to_string(kind) + " needs arg (one value per coordinate)");
     if (n_pos < 0 || (n_pos > 0 && (!pos || !order_stats))) return fail(who + ": bad order-statistics arguments");
-    if (!sorted && n_pos != 0) return fail(who + ": the indicator sorts nothing and has no order statistics (n_pos must be 0)");
+    if (kind == RK_INDICATOR && n_pos != 0) return fail(who + ": the indicator sorts nothing and has no order statistics (n_pos must be 0)");
+    if (kind == RK_SQDEV && n_pos != 0) return fail(who + ": the squared deviation sorts nothing and has no order statistics (n_pos must be 0)");
     CK(require_resident_history(src, who.c_str()));
     CK(second_handle_single_rank(who, src, dst));
     if (g_lo < 0 || g_hi < g_lo || g_hi > src->hist_rows) return fail(who + ": generation range out of bounds");
@@ -4135,104 +4244,38 @@ extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo
                     " draws; at least 4 are needed");
     CK(second_handle_fits(who, src, dst, src->dim, "the source has"));
     const uint64_t S64 = 2ull * (uint64_t)n * src->n_local;
-    if (S64 >= (1ull << 31))
-        return fail(who + ": the window holds " + std::to_string((unsigned long long)S64) + " values per coordinate; fewer than 2^31 can be ranked");
+    CK(rank_window_checks(who, S64, "ranked", n_pos, pos));
     const uint32_t S = (uint32_t)S64, dim = src->dim, ld = src->ld;
-    for (int32_t j = 0; j < n_pos; ++j)
-        if (pos[j] < 0 || (uint64_t)pos[j] >= S64)
-            return fail(who + ": order statistic " + std::to_string((long long)pos[j]) + " is outside [0, " + std::to_string((unsigned long long)S64) + ")");
     size_t mem_free = 0, mem_total = 0;
     HIPCK(hipMemGetInfo(&mem_free, &mem_total));
     const int64_t rows = 2 * n;
     uint64_t hist_need = 0;
     CK(history_growth_bytes(dst, rows, who, "ranked", mem_free, &hist_need));
-    mem_free -= (size_t)hist_need;      // (the scratch budget below is what ensure_history will leave)
-    // the batch: as many columns as the scratch budget holds (keys in | keys out | the sort's temporaries), batch * S < 2^31.
-    // The sort gives a column of this length to ONE workgroup, so the columns of a batch are its whole parallelism: at cfg2's shape with 1000
-    // generations a z fill takes 24.7 / 6.8 / 2.1 / 1.0 s with batches of 1 / 4 / 16 / 64 columns (profiles/rank_diagnostics_cfg2.txt).  Hence
-    // the default budget: a quarter of the free memory.  BPM_RANK_SCRATCH_MB: the budget; BPM_RANK_BATCH_COLS: the batch itself (tests, A/B;
-    // both read at every call)
-    uint32_t bc = 0;
-    size_t tmp_bytes = 0;
-    DevTemp<unsigned long long> keys;
-    DevTemp<unsigned char> tmp;
-    DevTemp<double> d_arg, d_os;
-    DevTemp<unsigned long long> d_pos;
-    if (sorted) {
-        uint64_t budget = mem_free / 4;
-        if (const char* mb = getenv("BPM_RANK_SCRATCH_MB")) budget = (uint64_t)std::max(atoll(mb), 0ll) << 20;
-        const uint32_t bc_max = std::min<uint32_t>(dim, (uint32_t)(((1ull << 31) - 1) / S));
-        auto need_of = [&](uint32_t b, uint64_t* need) -> int {
-            size_t t = 0;
-            HIPCK(rank_sort(nullptr, &t, nullptr, nullptr, b, S, src->stream));
-            tmp_bytes = t;
-            *need = 2ull * b * S * sizeof(unsigned long long) + t;
-            return 0;
-        };
-        uint64_t need = 0;
-        const char* forced = getenv("BPM_RANK_BATCH_COLS");
-        if (forced && atoi(forced) > 0) {
-            bc = std::min<uint32_t>((uint32_t)atoi(forced), bc_max);
-            CK(need_of(bc, &need));
-        } else {
-            bc = (uint32_t)std::min<uint64_t>(bc_max, std::max<uint64_t>(1, budget / (16ull * S)));
-            CK(need_of(bc, &need));
-            while (bc > 1 && need > budget) {
-                bc = std::max<uint32_t>(1, std::min<uint32_t>(bc - 1, (uint32_t)((uint64_t)bc * budget / need)));
-                CK(need_of(bc, &need));
-            }
-            if (need > budget)
-                return fail(who + ": sorting one column of " + std::to_string(S) + " keys needs " + std::to_string((unsigned long long)need) +
-                            " bytes of scratch (keys in, keys out and the sort's temporaries); the budget is " + std::to_string((unsigned long long)budget) +
-                            " bytes (BPM_RANK_SCRATCH_MB; by default a quarter of the free device memory: " + std::to_string(mem_free >> 20) +
-                            " MiB are free)");
-        }
-        const std::string what = "the scratch of " + std::to_string(bc) + " columns of " + std::to_string(S) + " keys";
-        CK(keys.alloc(2 * (size_t)bc * S, who.c_str(), what + " (keys in, keys out)"));
-        CK(tmp.alloc(std::max<size_t>(tmp_bytes, 1), who.c_str(), what + " (the sort's temporaries)"));
-        if (n_pos > 0) {
-            CK(d_os.alloc((size_t)n_pos * dim));
-            CK(d_pos.alloc((size_t)n_pos));
-        }
-    }
-    if (rk_folded(kind) || kind == RK_INDICATOR) CK(d_arg.alloc(dim));
+    mem_free -= (size_t)hist_need;      // (the scratch budget is what ensure_history will leave)
+    RankBatches rb;
+    DevTemp<double> d_arg;
+    if (sorted) CK(rank_batches_plan(rb, who, src, S, mem_free, n_pos));
+    if (rk_folded(kind) || flat) CK(d_arg.alloc(dim));
     // ---- nothing was launched so far ----
     CK(normalize_history(src, g_lo, g_hi));
     CK(ensure_history(dst, rows));
     if (d_arg.p) HIPCK(hipMemcpyAsync(d_arg.p, arg, (size_t)dim * sizeof(double), hipMemcpyHostToDevice, src->stream));
     RkWindow w;
-    w.g_lo = (uint64_t)g_lo; w.g_up = (uint64_t)(g_hi - n); w.n = (uint64_t)n; w.n_local = src->n_local; w.S = S64;
+    w.g_lo = (uint64_t)g_lo; w.g_up = (uint64_t)(g_hi - n); w.n = (uint64_t)n; w.n_local = src->n_local; w.S = S64; w.e0 = 0;
     if (!sorted) {
         const uint64_t total = S64 * ld;
         const unsigned nb = (unsigned)std::min<uint64_t>(2048, (total + RK_THREADS - 1) / RK_THREADS);
-        hipLaunchKernelGGL(rk_indicator_kernel, dim3(nb), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, dim, w, (const double*)d_arg.p, dst->hist);
+        hipLaunchKernelGGL(rk_indicator_kernel, dim3(nb), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, dim, w, kind, (const double*)d_arg.p,
+                           dst->hist);
         HIPCK(hipGetLastError());
     } else {
-        std::vector<unsigned long long> hpos((size_t)n_pos);
-        for (int32_t j = 0; j < n_pos; ++j) hpos[(size_t)j] = (unsigned long long)pos[j];
-        if (n_pos > 0) HIPCK(hipMemcpyAsync(d_pos.p, hpos.data(), hpos.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, src->stream));
-        unsigned long long* k_in = keys.p;
-        unsigned long long* k_out = keys.p + (size_t)bc * S;
-        for (uint32_t k0 = 0; k0 < dim; k0 += bc) {
-            const uint32_t b = std::min(bc, dim - k0);
-            const uint32_t kw = std::min<uint32_t>(b, RK_THREADS), n_tiles = (b + kw - 1) / kw;
-            uint64_t nby = 1;
-            CK(rows_grid(S64, n_tiles, (uint64_t)(RK_THREADS / kw) * RK_UNR, who.c_str(), &nby));
-            hipLaunchKernelGGL(rk_keys_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, w, k0, b, kw,
-                               rk_folded(kind) ? 1u : 0u, (const double*)d_arg.p, k_in);
-            HIPCK(hipGetLastError());
-            size_t t = tmp_bytes;      // (the temporaries of a full batch hold those of the last, partial one)
-            HIPCK(rank_sort(tmp.p, &t, k_in, k_out, b, S, src->stream));
-            if (n_pos > 0) {
-                hipLaunchKernelGGL(rk_pick_kernel, dim3(((unsigned)n_pos * b + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, src->stream,
-                                   (const unsigned long long*)k_out, S64, k0, b, dim, (const unsigned long long*)d_pos.p, (uint32_t)n_pos, d_os.p);
-                HIPCK(hipGetLastError());
-            }
-            hipLaunchKernelGGL(rk_score_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld, dim, w, k0, b, kw,
-                               kind, (const double*)d_arg.p, (const unsigned long long*)k_out, dst->hist);
-            HIPCK(hipGetLastError());
-        }
-        if (n_pos > 0) HIPCK(hipMemcpyAsync(order_stats, d_os.p, (size_t)n_pos * dim * sizeof(double), hipMemcpyDeviceToHost, src->stream));
+        CK(rank_batches_run(rb, who, src, w, rk_folded(kind), (const double*)d_arg.p, pos, order_stats,
+                            [&](uint32_t k0, uint32_t b, uint32_t kw, uint32_t n_tiles, uint64_t nby, const unsigned long long* k_sorted) -> int {
+                                hipLaunchKernelGGL(rk_score_kernel, dim3(n_tiles, (unsigned)nby), dim3(RK_THREADS), 0, src->stream, (const double*)src->hist, ld,
+                                                   dim, w, k0, b, kw, kind, (const double*)d_arg.p, k_sorted, dst->hist);
+                                HIPCK(hipGetLastError());
+                                return 0;
+                            }));
     }
     // the ln-likes of the same generations, and what bpm_set_history + bpm_set_loglike leave behind: the state = the last row, its ln-likes
     const size_t half = (size_t)n * src->n_local, row_d = (size_t)dst->n_local * dst->ld;
@@ -4242,6 +4285,85 @@ extern "C" int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo
     HIPCK(hipMemcpyAsync(dst->ll, src->llhist + (size_t)(g_hi - 1) * src->n_local, (size_t)dst->n_local * sizeof(double), hipMemcpyDeviceToDevice, src->stream));
     history_installed(dst, rows);
     HIPCK(hipStreamSynchronize(src->stream));
+    return 0;
+}
+
+// THE HIGHEST-DENSITY INTERVAL of every coordinate over one window of s's history: per probability p, with m = min(floor(p S), S - 1) and the
+// window's S values sorted, the first i of [0, S - m) whose width sorted[i + m] - sorted[i] is NaN (inf - inf) if one is, else the first of
+// the smallest width, gives lo = sorted[i], hi = sorted[i + m] (ranks.h: rk_hdi_kernel over bpm_rank_history's sorted batches).  window 0:
+// the split rows of history rows [a, b), bpm_rank_history's; window 1: the super-chain rows >= a (b is not read), bpm_reduce_moments'
+// selection.  Every check and every allocation comes before any launch; s's history is only read, in chain order.
+extern "C" int bpm_hdi(bpm_handle_t s, int32_t window, int64_t a, int64_t b, int32_t n_prob, const double* prob, int32_t n_pos, const int64_t* pos,
+                       double* lo, double* hi, int64_t* n_nan, double* order_stats, int64_t* count) {
+    const std::string who = "bpm_hdi";
+    if (!s) return fail(who + ": null handle");
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!lo || !hi || !n_nan || !count) return fail(who + ": null argument");
+    if (window != 0 && window != 1) return fail(who + ": window must be 0 (the split rows of history rows [a, b)) or 1 (the super-chain rows >= a); got " + std::to_string(window));
+    if (n_prob < 1 || n_prob > RK_MAX_PROB)
+        return fail(who + ": n_prob = " + std::to_string(n_prob) + " is outside the supported 1 ... " + std::to_string(RK_MAX_PROB) + " probabilities per call");
+    if (!prob) return fail(who + ": null argument (prob)");
+    for (int32_t j = 0; j < n_prob; ++j)
+        if (!(prob[j] > 0.0 && prob[j] < 1.0)) return fail(who + ": probability " + std::to_string(prob[j]) + " is outside (0, 1)");
+    if (n_pos < 0 || (n_pos > 0 && (!pos || !order_stats))) return fail(who + ": bad order-statistics arguments");
+    CK(require_resident_history(s, who.c_str()));
+    if (s->world != 1) return fail(who + ": single rank only (world_size " + std::to_string(s->world) + ")");
+    RkWindow w;
+    int64_t r0 = 0, r1 = 0;      // the history rows the window reads
+    if (window == 0) {
+        if (a < 0 || b < a || b > s->hist_rows) return fail(who + ": generation range out of bounds");
+        const int64_t n = (b - a) / 2;
+        if (n < 1) return fail(who + ": the window is empty (" + std::to_string((long long)(b - a)) + " history rows give half-chains of no draws)");
+        w.g_lo = (uint64_t)a; w.g_up = (uint64_t)(b - n); w.n = (uint64_t)n; w.n_local = s->n_local; w.S = 2ull * (uint64_t)n * s->n_local; w.e0 = 0;
+        r0 = a; r1 = b;
+    } else {
+        uint64_t e_lo = 0, e_hi = 0;
+        int64_t partial_row = -1;
+        super_chain_bounds(s, a, &e_lo, &e_hi, &partial_row);
+        if (e_hi <= e_lo) return fail(who + ": the window is empty (n_burn = " + std::to_string((long long)a) + " is at or beyond the last super-chain row)");
+        w.g_lo = 0; w.g_up = 0; w.n = (uint64_t)s->hist_rows; w.n_local = s->n_local; w.S = e_hi - e_lo; w.e0 = e_lo;
+        r0 = (int64_t)(e_lo / s->n_local); r1 = s->hist_rows;
+    }
+    CK(rank_window_checks(who, w.S, "sorted", n_pos, pos));
+    const uint32_t S = (uint32_t)w.S, dim = s->dim;
+    RkHdiOffsets off;
+    for (int32_t j = 0; j < RK_MAX_PROB; ++j) off.m[j] = 0;
+    for (int32_t j = 0; j < n_prob; ++j) off.m[j] = std::min<uint64_t>((uint64_t)std::floor(prob[j] * (double)S), (uint64_t)S - 1u);
+    size_t mem_free = 0, mem_total = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    RankBatches rb;
+    CK(rank_batches_plan(rb, who, s, S, mem_free, n_pos));
+    uint64_t parts = 1;
+    CK(rows_grid(w.S, (uint64_t)rb.bc * (uint64_t)n_prob, (uint64_t)RK_THREADS * RK_UNR, who.c_str(), &parts));
+    DevTemp<double> part_w, d_lo, d_hi;
+    DevTemp<unsigned long long> part_i;
+    DevTemp<long long> d_nan;
+    const size_t n_part = (size_t)n_prob * rb.bc * (size_t)parts, n_res = (size_t)n_prob * dim;
+    CK(part_w.alloc(n_part));
+    CK(part_i.alloc(n_part));
+    CK(d_lo.alloc(n_res));
+    CK(d_hi.alloc(n_res));
+    CK(d_nan.alloc(dim));
+    // ---- nothing was launched so far ----
+    CK(normalize_history(s, r0, r1));
+    CK(rank_batches_run(rb, who, s, w, false, (const double*)nullptr, pos, order_stats,
+                        [&](uint32_t k0, uint32_t bw, uint32_t, uint32_t, uint64_t, const unsigned long long* k_sorted) -> int {
+                            hipLaunchKernelGGL(rk_hdi_kernel, dim3(bw, (unsigned)parts, (unsigned)n_prob), dim3(RK_THREADS), 0, s->stream, k_sorted, w.S, bw, off,
+                                               part_w.p, part_i.p);
+                            HIPCK(hipGetLastError());
+                            hipLaunchKernelGGL(rk_hdi_final_kernel, dim3(((unsigned)n_prob * bw + RK_THREADS - 1) / RK_THREADS), dim3(RK_THREADS), 0, s->stream,
+                                               k_sorted, w.S, k0, bw, dim, (uint32_t)n_prob, (uint32_t)parts, off, (const double*)part_w.p,
+                                               (const unsigned long long*)part_i.p, d_lo.p, d_hi.p, d_nan.p);
+                            HIPCK(hipGetLastError());
+                            return 0;
+                        }));
+    static_assert(sizeof(long long) == sizeof(int64_t), "n_nan is copied as it lies");
+    HIPCK(hipMemcpyAsync(lo, d_lo.p, n_res * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(hi, d_hi.p, n_res * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(n_nan, d_nan.p, (size_t)dim * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    *count = (int64_t)w.S;
     return 0;
 }
 

@@ -619,7 +619,7 @@ class HipEngine(object):
     def rank_history(self, g_lo, g_hi, kind, arg=None, positions=(), dst=None):
         """-> (HipEngine, order_stats (len(positions), dim)): a second, ordinary engine of this one's shape whose resident history is a
         transform of the split rows of history rows [g_lo, g_hi) -- kind 0 the pooled average ranks, 1 their normal scores, 2 those of
-        |x - arg[k]|, 4 the ranks of |x - arg[k]|, 3 the indicator x <= arg[k] -- and the `positions`-th smallest values of every coordinate
+        |x - arg[k]|, 4 the ranks of |x - arg[k]|, 3 the indicator x <= arg[k], 5 the squared deviation (x - arg[k])^2 -- and the `positions`-th smallest values of every coordinate
         (bpm_rank_history; bipymc_amd/rank_diagnostics.py).  dst: an engine an earlier call returned, to be filled again (None: a new one,
         closed when the call fails).  A snapshot; the caller closes it.  Single rank only."""
         if self.world_size != 1:
@@ -638,6 +638,25 @@ class HipEngine(object):
                 dst.close()
             raise
         return dst, out
+
+    def hdi(self, window, a, b, prob, positions=()):
+        """-> (lo (len(prob), dim), hi (len(prob), dim), n_nan (dim,) int64, S, order_stats (len(positions), dim)): the highest-density
+        intervals of every coordinate over `window` -- 0: the split rows of history rows [a, b) (rank_history's draws), 1: the super-chain rows
+        >= a (param_est's) -- and the `positions`-th smallest values from the same sorted columns (bpm_hdi; bipymc_amd/summary.py).  Single
+        rank only."""
+        if self.world_size != 1:
+            raise NotImplementedError("hdi: columns are sorted on a single rank only (world_size = %d)" % self.world_size)
+        p = np.ascontiguousarray(np.asarray(prob, dtype=np.float64).reshape(-1))
+        pos = np.ascontiguousarray(np.asarray(positions, dtype=np.int64).reshape(-1))
+        lo = np.empty((len(p), self.dim)); hi = np.empty((len(p), self.dim))
+        nn = np.empty(self.dim, dtype=np.int64)
+        out = np.empty((len(pos), self.dim), dtype=np.float64)
+        n = C.c_int64(0)
+        i64 = C.POINTER(C.c_int64)
+        self._ck(self.lib.bpm_hdi(self._h, int(window), int(a), int(b), len(p), _dptr(p) if len(p) else None, len(pos),
+                                  pos.ctypes.data_as(i64) if len(pos) else None, _dptr(lo), _dptr(hi), nn.ctypes.data_as(i64),
+                                  _dptr(out) if len(pos) else None, C.byref(n)))
+        return lo, hi, nn, int(n.value), out
 
     def set_adapt_state(self, p_cr=None, delta_m=None, n_cr_updates=None, t_abs=-1):
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None

@@ -28,7 +28,7 @@ import numpy as np
 from . import diagnostics as _diag
 from . import quantiles as _qs
 
-KIND_RANK, KIND_Z, KIND_Z_FOLDED, KIND_INDICATOR, KIND_RANK_FOLDED = 0, 1, 2, 3, 4      # (bipymc_amd/csrc/ranks.h)
+KIND_RANK, KIND_Z, KIND_Z_FOLDED, KIND_INDICATOR, KIND_RANK_FOLDED, KIND_SQDEV = 0, 1, 2, 3, 4, 5      # (bipymc_amd/csrc/ranks.h)
 DEFAULT_PROB = (0.05, 0.95)
 
 RankDiagnostics = collections.namedtuple(
@@ -87,10 +87,12 @@ def split_size(g0, g1, n_chains):
     return n, 2 * n * int(n_chains)
 
 
-def compute(engine, allgather, g0, g1, max_lag=None, prob=DEFAULT_PROB, who="convergence_diagnostics_rank"):
+def compute(engine, allgather, g0, g1, max_lag=None, prob=DEFAULT_PROB, who="convergence_diagnostics_rank", keep_scratch=False):
     """The driver.  engine.rank_history(g0, g1, kind, arg, positions, dst) -> (dst, order_stats): HipEngine.rank_history -- dst (None: a new
     one) an engine with diag_split_moments, diag_autocov and close, whose history is the transformed split rows; allgather(obj) -> [obj] (one
-    process).  Four fills into one dst, diagnostics.compute after each; dst is closed on every way out.  -> RankDiagnostics"""
+    process).  Four fills into one dst, diagnostics.compute after each; dst is closed on every way out.  -> RankDiagnostics.
+    keep_scratch=True: -> (RankDiagnostics, dst), dst still open for a further fill of the same window (summary.py's squared deviations) and
+    the caller's to close; an error closes it as before."""
     lo, hi = check_prob(who, prob)
     g0, g1 = int(g0), int(g1)
     n, S = split_size(g0, g1, engine.n_chains)
@@ -107,14 +109,18 @@ def compute(engine, allgather, g0, g1, max_lag=None, prob=DEFAULT_PROB, who="con
         folded = fill(KIND_Z_FOLDED, arg=med)[1]
         lower = fill(KIND_INDICATOR, arg=quant[0])[1]
         upper = fill(KIND_INDICATOR, arg=quant[1])[1]
+    except BaseException:
+        keep_scratch = False
+        raise
     finally:
-        if held[0] is not None:
+        if held[0] is not None and not keep_scratch:
             held[0].close()
-    return RankDiagnostics(
+    out = RankDiagnostics(
         r_hat=np.maximum(bulk.r_hat, folded.r_hat), r_hat_bulk=bulk.r_hat, r_hat_tail=folded.r_hat, ess_bulk=bulk.ess,
         ess_tail=np.minimum(lower.ess, upper.ess), ess_lower=lower.ess, ess_upper=upper.ess, median=med, quantiles=quant,
         ess_capped=bulk.ess_capped | folded.ess_capped | lower.ess_capped | upper.ess_capped, n_half_chains=bulk.n_half_chains,
         n_draws=bulk.n_draws, window=(g0, g1))
+    return (out, held[0]) if keep_scratch else out
 
 
 def ranked_engine(engine, g0, g1, scale="z", folded=False, who="rank_history"):

@@ -463,6 +463,32 @@ int bpm_derive_history(bpm_handle_t src, bpm_handle_t dst);
  * dst is an ordinary stride-1 history of them. */
 int bpm_rank_history(bpm_handle_t src, bpm_handle_t dst, int64_t g_lo, int64_t g_hi, int32_t kind, const double* arg, int32_t n_pos,
                      const int64_t* pos, double* order_stats);
+/* kind 5 of bpm_rank_history, the squared deviation: dst[e * ld + k] = (x - arg[k]) * (x - arg[k]) over the same split rows -- the two IEEE
+ * operations of NumPy's (x - c) ** 2, a flat fill without a sort like kind 3 (arg is needed, n_pos must be 0, the padding column of an odd
+ * dim is 0).  With arg = the window's mean, the classic ESS over dst is the ESS of the variance estimate: what the Monte Carlo standard error
+ * of a posterior standard deviation needs (bipymc_amd/summary.py). */
+/* THE HIGHEST-DENSITY INTERVAL of every coordinate: the shortest interval that holds a share p of the window's draws -- what Stan's, ArviZ's
+ * and the `posterior` package's summary tables print next to mean and sd (the reference stops at param_est's mean and standard deviation).
+ * Definition, per coordinate k over the S values of the window and per probability p = prob[j], 0 < p < 1:
+ *   s = the values sorted (NaN last; -0.0 and +0.0 are one value, +0.0);  m = min(floor(p * S), S - 1) in double arithmetic;
+ *   w[i] = s[i + m] - s[i], i in [0, S - m);  i* = the first i whose w[i] is NaN (inf - inf) if there is one, else the first i of the
+ *   smallest w (np.argmin's rule);  lo[j * dim + k] = s[i*], hi[j * dim + k] = s[i* + m].
+ * A coordinate whose window holds a NaN has lo = hi = NaN; n_nan[k] counts its NaNs.  *count = S.
+ * The window: window = 0, the split rows of history rows [a, b) -- n = (b - a) / 2 rows from a, then n rows up to b, S = 2 n n_local:
+ * bpm_rank_history's and bpm_diag_split_moments' draws (n >= 1 here); window = 1, the super-chain rows >= a (b is not read), a partial
+ * first generation counted by chain index: bpm_reduce_moments' selection, param_est(n_burn = a)'s rows.
+ * order_stats[j * dim + k], j < n_pos: the pos[j]-th smallest value (0-based, pos[j] < S), from the same sorted columns, as
+ * bpm_rank_history returns them (n_pos = 0: pos and order_stats are not read).
+ * The columns are sorted in bpm_rank_history's batches under its scratch budget (BPM_RANK_SCRATCH_MB, BPM_RANK_BATCH_COLS); one scan of a
+ * sorted column per probability.  The result depends neither on the batch nor on the launch shape: candidates are ordered by (width is NaN,
+ * width, index), a total order, and no atomics are used.  Every check and every allocation comes before any launch; s's history is only
+ * read (a history kept in position order is put into chain order first, as bpm_get_history does); every temporary is freed on return.
+ * Errors: a null handle or output, an unknown window, n_prob outside 1 ... 8, a probability outside (0, 1), a position outside [0, S), no
+ * resident history (keep_history = 0), a range out of bounds, an empty window, world_size != 1 (single rank only), S >= 2^31, one column's
+ * scratch beyond the budget or scratch beyond the free device memory (the message names the requirement).  A THINNED history: a, b count
+ * its stored rows. */
+int bpm_hdi(bpm_handle_t s, int32_t window, int64_t a, int64_t b, int32_t n_prob, const double* prob, int32_t n_pos, const int64_t* pos,
+            double* lo, double* hi, int64_t* n_nan, double* order_stats, int64_t* count);
 /* (the test surface -- bpm_debug_*, bpm_selftest_philox, bpm_set_trace / bpm_get_trace, bpm_local_group_step, bpm_step_profiled, the
  * BPM_TEST_PATHS kernel-path switches -- is NOT part of this library: it is compiled only into build_variants/libbipymc_test.so and declared
  * in include/bipymc_hip_test.h; the product's kernel-argument block has no trace fields) */
