@@ -16,6 +16,8 @@
 //   diag_autocov_final_kernel   the partials in a fixed order, divided by n
 //
 // No atomics: every result is a fixed-order function of the history and the grid, which depends on the shape only.
+// Non-finite values: a coordinate with a NaN or an inf in either half has NaN in every output; no other coordinate sees it
+// (tests/test_gpu_diagnostics_edges.py).
 #pragma once
 #include "kernels.h"
 
@@ -59,8 +61,13 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_split_moments_kernel(const 
     const double m0 = sa0 * inv, m1 = sa1 * inv;
     double2* om = reinterpret_cast<double2*>(mean + h * 2u * n_pairs) + p;
     double2* o2 = reinterpret_cast<double2*>(m2 + h * 2u * n_pairs) + p;
-    *om = make_double2(shx + m0, shy + m1);
-    *o2 = make_double2(fmax(sb0 - sa0 * m0, 0.0), fmax(sb1 - sa1 * m1, 0.0));
+    // A half-chain that holds a NaN or an inf has M2 = NaN (inf - inf at the latest) and, with it, mean = NaN: an inf met after the first row
+    // would leave mean = inf, one in the first row NaN.  So M2 is clamped at 0 with a comparison, not with fmax -- fmax(NaN, 0) is 0, a
+    // variance of zero for such a half-chain -- and every output of the coordinate is NaN wherever in the half the value lies.
+    const double v0 = sb0 - sa0 * m0, v1 = sb1 - sa1 * m1;
+    const double nan = __builtin_nan("");
+    *om = make_double2(v0 == v0 ? shx + m0 : nan, v1 == v1 ? shy + m1 : nan);
+    *o2 = make_double2(v0 < 0.0 ? 0.0 : v0, v1 < 0.0 ? 0.0 : v1);
 }
 
 // one workgroup per coordinate k < ld; m_half = 2 n_local half-chains at stride ld.  out: [0, ld) mean of the means, [ld, 2 ld) sum of
@@ -115,7 +122,9 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_autocov_kernel(const double
     for (uint32_t g = blockIdx.x; g * cpw < n_local; g += gridDim.x) {
         const uint32_t i = g * cpw + a;
         const bool ok = lane_ok && i < n_local;
-        const uint32_t off = ok ? i * ld + k : 0u;      // (a lane without a column reads column 0 and adds zeros)
+        // a lane without a column loads column 0 (so that the loads stay uniform) and uses none of it: its y AND its ring entries are zero,
+        // so it adds exactly zero whatever column 0 holds -- 0 x NaN or 0 x inf would be NaN, and red[] below sums every lane of a coordinate
+        const uint32_t off = ok ? i * ld + k : 0u;
         const double mu = mean[(uint64_t)h * n_local * ld + off];
         double ring[DIAG_T];
 #pragma unroll
@@ -140,7 +149,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_autocov_kernel(const double
                 for (int u = 0; u < DIAG_B; ++u) {
                     const int s = b + u;
                     const double y = ok ? xv[u] - mu : 0.0;
-                    ring[s] = zv[u] - mu;
+                    ring[s] = ok ? zv[u] - mu : 0.0;
 #pragma unroll
                     for (int l = 0; l < DIAG_T; ++l) acc[l] = fma(y, ring[(s - l + DIAG_T) % DIAG_T], acc[l]);
                 }

@@ -14,6 +14,8 @@ Definitions (per coordinate, window of history rows [g0, g1), g0 = ceil(n_burn /
   chains), written out in geyer() below;  tau = max(-1 + 2 sum_{t <= max_t} rho_t (+ rho_{max_t + 1} if kept), 1 / log10(m n));
   ess = m n / tau.
   W == 0 (a coordinate constant in every half-chain): r_hat = ess = tau = NaN.
+  A coordinate with a NaN or +-inf in either half: every part the device returns for it is NaN (the mean of the means too, whatever the
+  sign of an inf), so r_hat = ess = tau = NaN; the other coordinates are what they would be without that value, bit for bit.
 """
 from __future__ import division
 

@@ -9,7 +9,8 @@ Definitions (per coordinate, over the S values of the window):
       i* = the first i whose w[i] is NaN (inf - inf) if any is, else the first i of the smallest w (np.argmin's rule);  (s[i*], s[i* + m]).
       A coordinate whose window holds a NaN has (NaN, NaN); -0.0 and +0.0 are one value.
   mean, sd       the mean and np.std(ddof=1) of the values, from the split-chain moments (half-chain means and variances of equal length n:
-                 mean = mean of the half-chain means, (S - 1) sd^2 = (n - 1) sum_j s2_j + n sum_j (xbar_j - mean)^2)
+                 mean = mean of the half-chain means, (S - 1) sd^2 = (n - 1) sum_j s2_j + n sum_j (xbar_j - mean)^2); a coordinate with
+                 a NaN or an inf among the values has mean = sd = NaN, as all its split-chain moments are (np.mean's +-inf is not restored)
   mcse_mean      sd / sqrt(ess_mean),  ess_mean the classic ESS of the values (diagnostics.py)
   ess_sd         the classic ESS of d = (x - mean)^2
   mcse_sd        sqrt(((mean(d^2) - mean(d)^2) / ess_sd) / mean(d) / 4): the delta method on sqrt(mean(d)) -- sd / sqrt(2 S) for independent

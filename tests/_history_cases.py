@@ -1,5 +1,5 @@
 """What tests/test_gpu_{diagnostics,quantiles,covariance,histograms}.py share: the engine and the sampler whose history a statistic is taken
-over, the local group of ranks over the push exchange with its single-rank twin, and the launcher of rank processes (tests/_stats_worker.py).
+over, the statistics' host class over a bare engine (_over), the local group of ranks over the push exchange with its single-rank twin, and the launcher of rank processes (tests/_stats_worker.py).
 A plain module: the tests import what they use."""
 import ctypes as C
 import os
@@ -23,6 +23,21 @@ def _engine(N, d, G=None, **kw):
     from bipymc_amd.utils import d100_gauss
     tid, tp, _ = d100_gauss.Gauss_100D(rho=0.5, dim=d)._bpm_target_spec()
     return HipEngine(algo=L.ALGO_DREAM, n_chains=N, dim=d, target_id=tid, target_params=tp, seed=5, **kw)
+
+
+def _over(engine):
+    """the statistics' host class over a bare engine of one rank"""
+    from bipymc_amd._history_stats import HistoryStatistics
+    from bipymc_amd.comm import single_process_allgather
+
+    class Over(HistoryStatistics):
+        n_chains = engine.n_chains
+        _stats_allgather = staticmethod(single_process_allgather)
+
+        def _stats_engine(self, who):
+            return engine
+
+    return Over()
 
 
 def _dream_class(N, d, gens, shuffle=True, rho=0.5, n_burn=0):

@@ -19,6 +19,7 @@ for _p in (os.path.dirname(HERE), HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from _history_cases import _over  # noqa: E402,F401  (the statistics' host class over a bare engine; tests/test_gpu_history_thin.py takes it from here)
 
 
 def _free_device_memory():
@@ -33,22 +34,7 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _over(engine):
-    """the statistics' host class over a bare engine of one rank"""
-    from bipymc_amd._history_stats import HistoryStatistics
-    from bipymc_amd.comm import single_process_allgather
-
-    class Over(HistoryStatistics):
-        n_chains = engine.n_chains
-        _stats_allgather = staticmethod(single_process_allgather)
-
-        def _stats_engine(self, who):
-            return engine
-
-    return Over()
-
-
-N, D, G = 8, 3, 12          # d odd: ld = 4, one padding column
+N, D, G = 8, 3, 12         # d odd: ld = 4, one padding column
 DERIVE_SRC = """
 __device__ void derive(const double* x, int d, double ll, const double* p, double* out) {
     out[0] = x[0] + x[2];

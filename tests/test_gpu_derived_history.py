@@ -26,7 +26,7 @@ if HERE not in sys.path:
 import test_covariance_host as TC  # noqa: E402
 import test_histograms_host as TH  # noqa: E402
 import test_traces_host as TT  # noqa: E402
-from _history_cases import _dream_class, _engine  # noqa: E402
+from _history_cases import _dream_class, _engine, _over  # noqa: E402
 from test_diagnostics_host import reference  # noqa: E402
 from test_gpu_derived import (EXP_SRC, FIVE_SRC, WIDE_SRC, _bits_equal, _check, _five, _history_with_zero_denominators,  # noqa: E402
                               _layout)
@@ -47,21 +47,6 @@ def _pair():
             return np.stack([X[:, 1] + X[:, 3], X[:, 0] * p[0] + ll], axis=1)
 
     return HipFunction(PAIR_SRC, n_out=2, params=[0.5], python_fn=py)
-
-
-def _over(engine):
-    """the statistics' host class over a bare engine of one rank"""
-    from bipymc_amd._history_stats import HistoryStatistics
-    from bipymc_amd.comm import single_process_allgather
-
-    class Over(HistoryStatistics):
-        n_chains = engine.n_chains
-        _stats_allgather = staticmethod(single_process_allgather)
-
-        def _stats_engine(self, who):
-            return engine
-
-    return Over()
 
 
 def _values(s, fn):

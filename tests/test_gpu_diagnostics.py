@@ -1,6 +1,11 @@
 """Convergence diagnostics on the GPU (bpm_diag_split_moments / bpm_diag_autocov + bipymc_amd/diagnostics.py): split-chain R-hat and ESS
 of the resident history against the NumPy restatement of tests/test_diagnostics_host.py, on installed AR(1) histories with known answers,
-on sampler histories (position-ordered, snooker, wide rows, the serial class), at cfg2's size, across ranks; no side effects; errors."""
+on sampler histories (position-ordered, snooker, wide rows, the serial class), at cfg2's size, across ranks; no side effects; errors.
+
+These are large, well-conditioned, finite histories compared on the finished r_hat / ess.  What the two entry points return, at the sizes
+where the kernels' tiling changes, on badly conditioned columns and with non-finite values, is held to an exactly rounded reference in
+tests/test_gpu_diagnostics_edges.py (tests/_diag_exact.py, tests/test_diag_exact_host.py); that a non-finite value stays in its own
+coordinate, for every statistic of the history, in tests/test_gpu_statistics_isolation.py."""
 import os
 import sys
 

@@ -25,27 +25,12 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import _rank_restatement as RR  # noqa: E402
-from _history_cases import _dream_class, _engine  # noqa: E402
+from _history_cases import _dream_class, _engine, _over  # noqa: E402
 from test_diagnostics_host import _ar1  # noqa: E402
 
 Z_MEASURED = 8.882e-16     # (plain 8.882e-16 over 16473 distinct arguments, folded 7.772e-16 over 16548: four units of 2^-52)
 Z_RTOL = 4 * Z_MEASURED
 N, G, D = 64, 401, 5       # G odd: the middle row is dropped; d odd: ld = 6, one padding column
-
-
-def _over(engine):
-    """the statistics' host class over a bare engine of one rank"""
-    from bipymc_amd._history_stats import HistoryStatistics
-    from bipymc_amd.comm import single_process_allgather
-
-    class Over(HistoryStatistics):
-        n_chains = engine.n_chains
-        _stats_allgather = staticmethod(single_process_allgather)
-
-        def _stats_engine(self, who):
-            return engine
-
-    return Over()
 
 
 def _tied_history():
