@@ -95,6 +95,9 @@ SIGNATURES = {
     "bpm_refresh_device_loglike": (C.c_int, [_H]),
     "bpm_check_device_likelihood": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]),
     "bpm_get_device_likelihood_info": (C.c_int, [_H, C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
+    "bpm_set_device_likelihood_data": (C.c_int, [_H, C.c_char_p, C.POINTER(C.c_double), C.c_int32, _dp, C.c_int64, C.c_int32]),
+    "bpm_eval_device_likelihood": (C.c_int, [_H, _dp, C.c_int32, _dp]),
+    "bpm_data_likelihood_chunk": (C.c_int, []),
     "bpm_get_history": (C.c_int, [_H, C.c_int64, C.c_int64, _dp]),
     "bpm_get_loglike_history": (C.c_int, [_H, C.c_int64, C.c_int64, _dp]),
     "bpm_reserve_history": (C.c_int, [_H, C.c_int64]),
@@ -168,7 +171,7 @@ def load():
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
 _ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/accept_test.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/accept_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/device_memory.h", "csrc/user_likelihood.h", "csrc/derived.h",
-            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_target.h", "csrc/derive_rows.h",
+            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_eval_data.h", "csrc/user_target.h", "csrc/derive_rows.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

@@ -549,7 +549,13 @@ struct UserLikelihood {
         }
     } fused;
     std::string why;                         // why the fused form is not in use (bpm_get_device_likelihood_info)
-    void leak() { mod.leak(); params.leak(); fused.mod.leak(); }
+    // the PER-DATUM form (user_eval_data.h; bpm_set_device_likelihood_data): fn is bpm_user_eval_data, `fold` bpm_user_fold_data; the caller's data
+    // (n_data, w) and the chunk sums [row][chunk][K] of a batch of `batch_rows` rows are the likelihood's own.  n_data == 0: another form.
+    hipFunction_t fold = nullptr;
+    DevTemp<double> data, part;
+    int32_t n_data = 0, n_chunks = 0;
+    uint32_t batch_rows = 0;
+    void leak() { mod.leak(); params.leak(); fused.mod.leak(); data.leak(); part.leak(); }
 };
 // A caller's function of one sample, compiled around the window reduction of derived.h (bpm_set_device_function): kept until replaced or bpm_destroy
 struct DerivedFunction {
@@ -3769,6 +3775,26 @@ static int user_eval_launch(bpm_sampler* s, const double* rows, const int32_t* i
     HIPCK(ModuleLaunch<bpm::UserEvalKernel>::on(s->stream, s->like.fn, grid, block, lds, rows, ids, (int)n, (int)s->ld, (int)s->dim, s->like.params.p, out, rpb, ldp));
     return 0;
 }
+// The installed likelihood's kernel of its own on `n` rows (stride s->ld) -> out[n]: bpm_user_eval, or for the per-datum form a wavefront per
+// (row, chunk of the data) and, with more than one chunk, the fold of the chunk sums (user_eval_data.h).  The chunking is a function of n_data alone;
+// rows beyond the scratch's batch go in further launches, which changes no row's value.
+static int user_ll_launch(bpm_sampler* s, const double* rows, const int32_t* ids, uint32_t n, double* out) {
+    const UserLikelihood& u = s->like;
+    if (u.n_data == 0) return user_eval_launch(s, rows, ids, n, out);
+    for (uint32_t r0 = 0; r0 < n; r0 += u.batch_rows) {
+        const uint32_t nb = std::min(u.batch_rows, n - r0);
+        const uint64_t items = (uint64_t)nb * (uint64_t)u.n_chunks;      // (batch_rows keeps it below 2^31)
+        const double* rb = rows + (size_t)r0 * s->ld;
+        const int32_t* ib = ids ? ids + r0 : nullptr;
+        const unsigned grid = (unsigned)((items + bpm::USER_DATA_WAVES - 1) / bpm::USER_DATA_WAVES);
+        HIPCK(ModuleLaunch<bpm::UserEvalDataKernel>::on(s->stream, u.fn, grid, 64u * bpm::USER_DATA_WAVES, 0, rb, ib, (int)nb, (int)s->ld, (int)s->dim, u.params.p,
+                                                        u.data.p, (int)u.n_data, (int)u.n_chunks, out + r0, u.part.p));
+        if (u.n_chunks > 1)
+            HIPCK(ModuleLaunch<bpm::UserFoldDataKernel>::on(s->stream, u.fold, (nb + 63u) / 64u, 64u, 0, rb, ib, (int)nb, (int)s->ld, (int)s->dim, u.params.p, u.part.p,
+                                                            (int)u.n_data, (int)u.n_chunks, out + r0));
+    }
+    return 0;
+}
 // ln-like of the local chains' CURRENT states from the installed device likelihood (what bpm_set_loglike takes from the host)
 static int user_refresh_ll(bpm_sampler* s) {
     const double* X = s->G + (uint64_t)s->rank * s->L.blk;
@@ -3776,7 +3802,7 @@ static int user_refresh_ll(bpm_sampler* s) {
         HIPCK(ModuleLaunch<bpm::UserEvalLlKernel>::on(s->stream, s->like.fused.eval, grid_for(s->n_local, s->shape.lpc), s->like.fused.block, 0, X, s->n_local, s->ld,
                                                       s->dim, s->like.params.p, s->ll));
     } else {
-        CK(user_eval_launch(s, X, nullptr, s->n_local, s->ll));
+        CK(user_ll_launch(s, X, nullptr, s->n_local, s->ll));
     }
     if (last_row_is_state(s))
         HIPCK(hipMemcpyAsync(s->llhist + (size_t)(s->hist_rows - 1) * s->n_local, s->ll, s->n_local * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
@@ -3798,7 +3824,7 @@ static int run_generations_user(bpm_sampler* s, int64_t n_gens) {
                 act = 0;
                 for (uint32_t w = 0; w < a.n_items; ++w) act += s->h_ids[w] >= 0 ? 1 : 0;
             }
-            CK(user_eval_launch(s, s->prop_buf, s->world > 1 ? s->ids_buf : nullptr, a.n_items, s->aux_buf + s->n_local));
+            CK(user_ll_launch(s, s->prop_buf, s->world > 1 ? s->ids_buf : nullptr, a.n_items, s->aux_buf + s->n_local));
             s->proposed = true; s->prop_mode = 3; s->prop_chunks = 0;
             CK(commit_finish(s, act, false));
         }
@@ -3870,28 +3896,60 @@ static std::string build_user_fused(bpm_sampler* s, const char* hip_source, cons
     return "";
 }
 
-extern "C" int bpm_set_device_likelihood(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params) {
-    CK(check_handle(s));
-    CK(set_device(s));
-    if (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail("bpm_set_device_likelihood: the sampler has a shipped device target (create it with BPM_TARGET_HOST_CALLBACK)");
-    if (s->proposed) return fail("bpm_set_device_likelihood: a half generation is open (bpm_propose ... without its commit)");
-    if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_device_likelihood: bad argument");
+// One way in for every form.  data == nullptr: the plain and the per-coordinate form (bpm_set_device_likelihood); else the per-datum form, its data
+// (n_data, w) row-major copied into a buffer of the likelihood's own (bpm_set_device_likelihood_data).
+static int install_user_likelihood(bpm_sampler* s, const std::string& who, const char* hip_source, const double* params, int32_t n_params, const double* data,
+                                   int64_t n_data, int32_t w) {
+    if (s->cfg.target_id != BPM_TARGET_HOST_CALLBACK) return fail(who + ": the sampler has a shipped device target (create it with BPM_TARGET_HOST_CALLBACK)");
+    if (s->proposed) return fail(who + ": a half generation is open (bpm_propose ... without its commit)");
+    if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail(who + ": bad argument");
+    const bool has_data = bpm::user_source_has_data(hip_source);
+    if (!data && has_data) return fail(who + ": the source is in the per-datum form (BPM_LN_LIKE_DATA): give it its data with bpm_set_device_likelihood_data");
+    if (data && !has_data) return fail(who + ": the source does not define BPM_LN_LIKE_DATA and BPM_LN_LIKE_DATA_W (the per-datum form: user_eval_data.h)");
     hipDeviceProp_t prop;
     HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
     // the new likelihood is built beside the installed one, which stays whole until nothing can fail any more ...
     std::vector<char> code;
     const std::string why = bpm::compile_user_likelihood(hip_source, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
-    if (!why.empty()) return fail("bpm_set_device_likelihood: " + why);
+    if (!why.empty()) return fail(who + ": " + why);
     UserLikelihood next;
     HIPCK(next.mod.load(code));
-    next.fn = next.mod.function("bpm_user_eval");
-    if (!next.fn) return fail("bpm_set_device_likelihood: the compiled module has no bpm_user_eval kernel");
+    next.fn = next.mod.function(data ? "bpm_user_eval_data" : "bpm_user_eval");
+    if (!next.fn) return fail(who + ": the compiled module has no " + (data ? "bpm_user_eval_data" : "bpm_user_eval") + " kernel");
     CK(next.params.upload(params, n_params, s->stream));
+    if (data) {
+        next.fold = next.mod.function("bpm_user_fold_data");
+        const hipFunction_t info = next.mod.function("bpm_user_data_info");
+        if (!next.fold || !info) return fail(who + ": the compiled module has no bpm_user_fold_data kernel");
+        // the program's view of K, w, the chunk and the workgroup must be this call's and this library's
+        DevTemp<int> d_info;
+        int h_info[4] = {0, 0, 0, 0};
+        CK(d_info.alloc(4));
+        HIPCK(ModuleLaunch<bpm::UserDataInfoKernel>::on(s->stream, info, 1, 1, 0, d_info.p));
+        HIPCK(hipMemcpyAsync(h_info, d_info.p, sizeof(h_info), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        const int K = h_info[0];
+        if (K < 1 || K > 8 || h_info[2] != bpm::USER_DATA_CHUNK || h_info[3] != bpm::USER_DATA_WAVES) return fail(who + ": the compiled module's chunking differs from the library's");
+        if (h_info[1] != w)
+            return fail(who + ": the source was written for " + std::to_string(h_info[1]) + " values per datum (BPM_LN_LIKE_DATA_W), the data have " + std::to_string(w));
+        next.n_data = (int32_t)n_data;
+        next.n_chunks = (int32_t)((n_data + bpm::USER_DATA_CHUNK - 1) / bpm::USER_DATA_CHUNK);
+        // rows of one launch: what the scratch bound admits, but no more than this sampler's own launches need -- its n_local chains, or 256 rows for a small
+        // population, so that an evaluation of a few hundred given rows is still one launch.  bpm_eval_device_likelihood takes more rows in batches; no
+        // value depends on the batching (tests/test_gpu_data_likelihood.py evaluates 257 rows, across a batch boundary, for that reason)
+        const size_t row_bytes = (size_t)next.n_chunks * (size_t)K * sizeof(double);
+        next.batch_rows = (uint32_t)std::min<size_t>(std::max<size_t>(bpm::USER_DATA_SCRATCH_BYTES / row_bytes, 1), std::max<size_t>(s->n_local, 256));
+        next.batch_rows = (uint32_t)std::min<uint64_t>(next.batch_rows, (uint64_t)0x7fffffff / (uint64_t)next.n_chunks);
+        CK(next.data.alloc((size_t)n_data * (size_t)w, who.c_str(), "the data"));
+        HIPCK(hipMemcpyAsync(next.data.p, data, (size_t)n_data * (size_t)w * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        if (next.n_chunks > 1) CK(next.part.alloc((size_t)next.batch_rows * (size_t)next.n_chunks * (size_t)K, who.c_str(), "the chunk sums"));
+    }
     HIPCK(hipStreamSynchronize(s->stream));                      // (a previous likelihood's launches are done, the parameters are in place)
     // ... and replaces it in one step: the old update kernel leaves with the old likelihood
     s->like.fused.drop(s->dq);
     s->like = std::move(next);
     CK(user_refresh_ll(s));      // (by the kernel of its own; again below by the update kernel's arithmetic once that one is built)
+    if (data) { s->like.why = "the likelihood is summed over its data by kernels of its own (a wavefront per chunk of the data), not inside the update kernel"; return 0; }
     // the faster form.  Whatever goes wrong with it leaves the three-kernel form in place (bpm_get_device_likelihood_info says which is in use
     // and why).  BPM_USER_FUSED=0: not attempted (A/B, tests).
     const bool want_fused = !(getenv("BPM_USER_FUSED") && atoi(getenv("BPM_USER_FUSED")) == 0);      // (read at every call: a test switches it)
@@ -3902,6 +3960,47 @@ extern "C" int bpm_set_device_likelihood(bpm_handle_t s, const char* hip_source,
     if (!s->like.why.empty()) return 0;
     s->like.fused = std::move(fused);
     return user_refresh_ll(s);      // (again, now by the update kernel's own arithmetic: the per-coordinate form adds in the kernel's reduction order)
+}
+
+extern "C" int bpm_set_device_likelihood(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    return install_user_likelihood(s, "bpm_set_device_likelihood", hip_source, params, n_params, nullptr, 0, 0);
+}
+
+// The per-datum form (user_eval_data.h): `data` (n_data, w) float64 row-major, copied to the device here and kept until the likelihood is replaced or the
+// handle destroyed.  A single rank only: in a world the three-kernel path exchanges through RCCL.
+extern "C" int bpm_set_device_likelihood_data(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params, const double* data, int64_t n_data,
+                                              int32_t w) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (s->world > 1)
+        return fail("bpm_set_device_likelihood_data: a likelihood with data runs on a single rank only (" + std::to_string(s->world) + " ranks here)");
+    if (!data || n_data < 1 || n_data > (int64_t)0x7fffffff || w < 1 || w > bpm::USER_DATA_MAX_W)
+        return fail("bpm_set_device_likelihood_data: data must be (n_data, w) with 1 <= n_data < 2^31 and 1 <= w <= " + std::to_string(bpm::USER_DATA_MAX_W));
+    return install_user_likelihood(s, "bpm_set_device_likelihood_data", hip_source, params, n_params, data, n_data, w);
+}
+
+// the chunk of the data one wavefront sums in the per-datum form (user_eval_data.h: the order of the additions depends on it and on n_data alone)
+extern "C" int bpm_data_likelihood_chunk(void) { return bpm::USER_DATA_CHUNK; }
+
+// The installed device likelihood -- of any form -- on `n` given rows X (n, dim), by its kernel of its own (never the update kernel's arithmetic)
+extern "C" int bpm_eval_device_likelihood(bpm_handle_t s, const double* X, int32_t n, double* out) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!s->like.fn) return fail("bpm_eval_device_likelihood: no device likelihood installed (bpm_set_device_likelihood)");
+    if (s->proposed) return fail("bpm_eval_device_likelihood: a half generation is open (bpm_propose ... without its commit)");
+    if (n <= 0) return 0;
+    if (!X || !out) return fail("bpm_eval_device_likelihood: null argument");
+    DevTemp<double> bX, bO;
+    CK(bX.alloc((size_t)n * s->ld, "bpm_eval_device_likelihood", "the rows"));
+    CK(bO.alloc((size_t)n));
+    HIPCK(hipMemsetAsync(bX.p, 0, (size_t)n * s->ld * sizeof(double), s->stream));
+    HIPCK(hipMemcpy2DAsync(bX.p, s->ld * sizeof(double), X, s->dim * sizeof(double), s->dim * sizeof(double), n, hipMemcpyHostToDevice, s->stream));
+    CK(user_ll_launch(s, bX.p, nullptr, (uint32_t)n, bO.p));
+    HIPCK(hipMemcpyAsync(out, bO.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return 0;
 }
 
 // which form of the device likelihood runs: *fused = 1 the update kernel compiled around it (one launch per half generation), 0 the three-kernel form

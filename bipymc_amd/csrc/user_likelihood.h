@@ -35,11 +35,51 @@ inline void user_eval_tile(uint32_t d, int& rpb, int& ldp) {
 
 // user source + wrapper -> code object for `arch`.  -> "" and `code`, or the reason (compiler log included).  headers: the library's embedded
 // files, user_eval.h and user_ln_like.h among them (the latter derives ln_like for a source in the per-coordinate form).
-inline std::string compile_user_likelihood(const std::string& user_src, const std::string& arch, const RtcHeader* headers, size_t n_headers, std::vector<char>& code) {
-    const std::string src = std::string(RTC_PRELUDE) + "#line 1 \"ln_like.hip\"\n" + user_src + "\n#include \"user_eval.h\"\n";
-    return rtc_compile(src, "ln_like.hip", headers, n_headers, arch, {},
-                       "the likelihood source does not compile (it must define `__device__ double ln_like(const double* x, int d, const double* p)`):\n", code);
+// A source in the PER-DATUM form (it defines BPM_LN_LIKE_DATA: user_eval_data.h) gets that header's kernels instead -- a wavefront per (row, chunk of the data).
+// The form is read from the source's own directive: a line `# define BPM_LN_LIKE_DATA <K>` (any blanks or tabs where the preprocessor allows them); the
+// name inside a comment or as part of a longer one (BPM_LN_LIKE_DATA_W) is not it.
+inline bool user_source_has_data(const std::string& user_src) {
+    auto blank = [](char c) { return c == ' ' || c == '\t'; };
+    static const std::string def = "define", name = "BPM_LN_LIKE_DATA";
+    for (size_t at = 0; at < user_src.size();) {
+        size_t eol = user_src.find('\n', at);
+        if (eol == std::string::npos) eol = user_src.size();
+        size_t i = at;
+        while (i < eol && blank(user_src[i])) ++i;
+        if (i < eol && user_src[i] == '#') {
+            ++i;
+            while (i < eol && blank(user_src[i])) ++i;
+            if (user_src.compare(i, def.size(), def) == 0 && i + def.size() < eol && blank(user_src[i + def.size()])) {
+                i += def.size();
+                while (i < eol && blank(user_src[i])) ++i;
+                const size_t end = i + name.size();
+                if (user_src.compare(i, name.size(), name) == 0 && (end >= eol || blank(user_src[end]) || user_src[end] == '\r')) return true;
+            }
+        }
+        at = eol + 1;
+    }
+    return false;
 }
+inline std::string compile_user_likelihood(const std::string& user_src, const std::string& arch, const RtcHeader* headers, size_t n_headers, std::vector<char>& code) {
+    const bool data = user_source_has_data(user_src);
+    const std::string src = std::string(RTC_PRELUDE) + "#line 1 \"ln_like.hip\"\n" + user_src + (data ? "\n#include \"user_eval_data.h\"\n" : "\n#include \"user_eval.h\"\n");
+    return rtc_compile(src, "ln_like.hip", headers, n_headers, arch, {},
+                       data ? "the likelihood source does not compile (with data it must define `__device__ void ln_like_datum(const double* x, int d, const double* y, int i, "
+                              "const double* p, double* acc)` and `__device__ double ln_like_total(const double* x, int d, const double* acc, int n_data, const double* p)`):\n"
+                            : "the likelihood source does not compile (it must define `__device__ double ln_like(const double* x, int d, const double* p)`):\n", code);
+}
+
+// The per-datum kernels (user_eval_data.h) as the host launches them -- bpm_user_eval_data: rows, ids, n, ld, d, params, data, n_data, n_chunks, out, part;
+// bpm_user_fold_data: rows, ids, n, ld, d, params, part, n_data, n_chunks, out; bpm_user_data_info: what the program was compiled with.
+using UserEvalDataKernel = void(const double*, const int*, int, int, int, const double*, const double*, int, int, double*, double*);
+using UserFoldDataKernel = void(const double*, const int*, int, int, int, const double*, const double*, int, int, double*);
+using UserDataInfoKernel = void(int*);
+// The chunk of the data a wavefront sums (BPM_DATA_CHUNK of user_eval_data.h; the installed program reports its own and must agree) and the wavefronts of
+// a workgroup.  The chunk sums of a batch of rows [row][chunk][K] stay below USER_DATA_SCRATCH_BYTES: more rows go in several launches.
+constexpr int USER_DATA_CHUNK = 4096;
+constexpr int USER_DATA_WAVES = 4;
+constexpr size_t USER_DATA_SCRATCH_BYTES = (size_t)64 << 20;
+constexpr int USER_DATA_MAX_W = 64;
 
 // ---- the caller's likelihood INSIDE the update kernel ---------------------------------------------------------------------------------------------
 // The second, faster form: the library's own update kernel (kernels.h: phase_fused_kernel, the general instantiation) compiled at run time with the

@@ -77,6 +77,9 @@ class DeMcMpi(HistoryStatistics):
         varepsilon = np.asarray(varepsilon, dtype=np.float64)
         self.n_chains = int(n_chains)
         self.comm = _comm.wrap(mpi_comm)
+        from .device_likelihood import HipLikelihood
+        if isinstance(ln_like_fn, HipLikelihood) and ln_like_fn.data is not None and self.comm.size > 1:      # (before anything is created)
+            raise NotImplementedError("a likelihood with data runs on a single rank only (%d ranks here)" % self.comm.size)
         self.local_n_accepted = 0
         self.local_n_rejected = 1                              # demc.py:18
         self.n_accepted = 1                                    # samplers.py:30-31
@@ -160,7 +163,8 @@ class DeMcMpi(HistoryStatistics):
         self._hip_likelihood = None
         if isinstance(ln_like_fn, HipLikelihood) and not self.uses_device_target:
             if hasattr(self._engine, "set_device_likelihood"):
-                self._engine.set_device_likelihood(ln_like_fn.source, ln_like_fn.params)
+                from .samplers import _data_kw
+                self._engine.set_device_likelihood(ln_like_fn.source, ln_like_fn.params, **_data_kw(ln_like_fn))
                 self._hip_likelihood = ln_like_fn
             elif ln_like_fn.python_fn is None:
                 raise TypeError("HipLikelihood without python_fn on an engine that cannot compile it")

@@ -26,13 +26,42 @@ class HipLikelihood(object):
         __device__ double ln_like_finish(const double* acc, int d, const double* p)              // the value from the K sums
 
     instead of ln_like: inside the update kernel every lane of a chain adds the terms of its own coordinates and the sums meet in the kernel's reduction
-    tree -- the shape of the shipped targets, and their speed (the plain form runs on one lane per chain)."""
+    tree -- the shape of the shipped targets, and their speed (the plain form runs on one lane per chain).
 
-    def __init__(self, source, params=(), python_fn=None, terms=0):
+    data=(n_data, w) float64 with terms=K (1 ... 8): the PER-DATUM form for a likelihood that is a function of K sums over the DATA -- a fit of a model
+    with a few parameters to many data points, what every fitting script of the reference does.  `source` then defines
+
+        __device__ void ln_like_datum(const double* x, int d, const double* y, int i, const double* p, double* acc)     // adds datum i (its w values: y) into acc[0 .. K)
+        __device__ double ln_like_total(const double* x, int d, const double* acc, int n_data, const double* p)         // the value from the K sums; x: for a prior
+
+    The data are copied to the device once; a wavefront per (proposal, chunk of the data) adds the terms, in an order that depends on n_data alone: the
+    value of a point is a function of (x, data, params), bit for bit (csrc/user_eval_data.h).  A 1-D array is n_data values of w = 1.  Single rank."""
+
+    MAX_DATA_W = 64
+
+    def __init__(self, source, params=(), python_fn=None, terms=0, data=None):
         self.terms = int(terms)
         if not 0 <= self.terms <= 8:
             raise ValueError("terms must be 0 (plain ln_like) or 1 ... 8")
-        self.source = ("#define BPM_LN_LIKE_TERMS %d\n" % self.terms if self.terms else "") + str(source)
+        self.data = None
+        if data is not None:
+            if self.terms < 1:
+                raise ValueError("data needs terms=K (1 ... 8): the number of sums over the data")
+            arr = np.asarray(data)
+            if arr.dtype != np.float64:
+                raise ValueError("data must be float64 (got %s)" % arr.dtype)
+            if arr.ndim == 1:
+                arr = arr.reshape(-1, 1)
+            if arr.ndim != 2:
+                raise ValueError("data must have shape (n_data, w) or (n_data,) (got %r)" % (arr.shape,))
+            if not 1 <= arr.shape[0] < 2 ** 31:
+                raise ValueError("data must have 1 <= n_data < 2^31 rows (got %d)" % arr.shape[0])
+            if not 1 <= arr.shape[1] <= self.MAX_DATA_W:
+                raise ValueError("data must have 1 <= w <= %d values per datum (got %d)" % (self.MAX_DATA_W, arr.shape[1]))
+            self.data = np.ascontiguousarray(arr)
+            self.source = "#define BPM_LN_LIKE_DATA %d\n#define BPM_LN_LIKE_DATA_W %d\n" % (self.terms, self.data.shape[1]) + str(source)
+        else:
+            self.source = ("#define BPM_LN_LIKE_TERMS %d\n" % self.terms if self.terms else "") + str(source)
         self.params = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
         self.python_fn = python_fn
 

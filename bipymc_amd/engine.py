@@ -333,13 +333,36 @@ class HipEngine(object):
     def set_loglike_device(self, ll):
         self._ck(self.lib.bpm_set_loglike_device(self._h, C.c_void_p(_device_pointer(ll, self.n_local, "ln_like values"))))
 
-    def set_device_likelihood(self, source, params=()):
+    def set_device_likelihood(self, source, params=(), data=None):
         """ln_like_fn as HIP source (include/bipymc_hip.h: bpm_set_device_likelihood): compiled with hiprtc into a kernel that runs between the proposal
-        and the commit kernel; `step` then drives this host-callback sampler.  The current states are evaluated at once."""
+        and the commit kernel; `step` then drives this host-callback sampler.  The current states are evaluated at once.
+        data (n_data, w) float64: the per-datum form (bpm_set_device_likelihood_data) -- copied to the device once, summed a wavefront per chunk."""
         p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
         src = source.encode() if isinstance(source, str) else bytes(source)
-        self._ck(self.lib.bpm_set_device_likelihood(self._h, src, p.ctypes.data_as(C.POINTER(C.c_double)) if p.size else None, int(p.size)))
+        pp = p.ctypes.data_as(C.POINTER(C.c_double)) if p.size else None
+        if data is None:
+            self._ck(self.lib.bpm_set_device_likelihood(self._h, src, pp, int(p.size)))
+        else:
+            dat = np.asarray(data)
+            if dat.dtype != np.float64 or dat.ndim not in (1, 2) or dat.size == 0:
+                raise ValueError("data must be a non-empty float64 array of shape (n_data, w) or (n_data,)")
+            dat = np.ascontiguousarray(dat.reshape(dat.shape[0], -1))
+            self._ck(self.lib.bpm_set_device_likelihood_data(self._h, src, pp, int(p.size), _dptr(dat), dat.shape[0], dat.shape[1]))
         self.has_device_likelihood = True
+
+    def eval_device_likelihood(self, X):
+        """the installed device likelihood (any form) at the rows of X (n, dim), by its kernel of its own (bpm_eval_device_likelihood)"""
+        X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float64)
+        if X.shape[1] != self.dim:
+            raise ValueError("X must have %d columns (got %d)" % (self.dim, X.shape[1]))
+        out = np.empty(X.shape[0], dtype=np.float64)
+        self._ck(self.lib.bpm_eval_device_likelihood(self._h, _dptr(X), X.shape[0], _dptr(out)))
+        return out
+
+    @staticmethod
+    def data_likelihood_chunk():
+        """consecutive data points one wavefront sums in the per-datum form (bpm_data_likelihood_chunk)"""
+        return int(L.load().bpm_data_likelihood_chunk())
 
     def device_likelihood_info(self):
         """-> (fused, why): fused True -- the update kernel itself was compiled around the likelihood (one launch per half generation); False -- the

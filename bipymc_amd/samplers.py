@@ -17,6 +17,11 @@ from .comm import single_process_allgather
 from .utils import _target
 
 
+def _data_kw(ll):
+    """what a HipLikelihood's data add to engine.set_device_likelihood's arguments (nothing without data: an engine that predates them keeps working)"""
+    return {"data": ll.data} if ll.data is not None else {}
+
+
 class DeMc(HistoryStatistics):
     def __init__(self, log_like_fn, n_chains=8, ln_kwargs={}, **proposal_kwargs):
         assert n_chains >= 4                                         # samplers.py:249
@@ -64,8 +69,8 @@ class DeMc(HistoryStatistics):
         # ln_like_fn given as HIP source (device_likelihood.py): compiled into the generation loop, the sampler is stepped like one with a shipped target
         from .device_likelihood import HipLikelihood
         hip = isinstance(self.log_like_fn, HipLikelihood) and not self._device_target and hasattr(eng, "set_device_likelihood")
-        if hip:
-            eng.set_device_likelihood(self.log_like_fn.source, self.log_like_fn.params)      # (evaluates the jittered start states too)
+        if hip:      # (evaluates the jittered start states too; with data: the per-datum form)
+            eng.set_device_likelihood(self.log_like_fn.source, self.log_like_fn.params, **_data_kw(self.log_like_fn))
         elif not self._device_target:
             X = eng.get_state()
             eng.set_loglike(np.array([self._call(x) for x in X], dtype=np.float64))

@@ -272,6 +272,22 @@ int bpm_check_device_likelihood(const char* hip_source, const char* arch, char* 
  * The module's kernels are dispatched like the library's own (its AQL queue finds them by name).  Environment: BPM_USER_FUSED=0 does not attempt the
  * fused form, =2 launches it on the HIP stream (A/B). */
 int bpm_get_device_likelihood_info(bpm_handle_t h, int32_t* fused, char* why, int64_t why_cap);
+/* The PER-DATUM form (samplers.py:36-43 takes any callable; the reference's fitting scripts sum over their data points inside it): `hip_source` says
+ * `#define BPM_LN_LIKE_DATA K` (1 ... 8 sums) and `#define BPM_LN_LIKE_DATA_W w`, and defines
+ *     __device__ void ln_like_datum(const double* x, int d, const double* y, int i, const double* p, double* acc)      (y: the w values of datum i)
+ *     __device__ double ln_like_total(const double* x, int d, const double* acc, int n_data, const double* p)          (x: for a prior)
+ * (the form is recognised by the source's own directive line `#define BPM_LN_LIKE_DATA K`, blanks as the preprocessor allows them; the name in a comment
+ * does not count; bpm_set_device_likelihood refuses such a source, this entry refuses one without it)
+ * `data`: (n_data, w) row-major, 1 <= n_data < 2^31, 1 <= w <= 64, copied to the device here and kept until the likelihood is replaced or the handle
+ * destroyed.  A wavefront per (row, chunk of the data) adds the terms, in an order that depends on n_data alone: a row's value is a function of
+ * (x, data, params), bit for bit (bipymc_amd/csrc/user_eval_data.h).  Never fused (bpm_get_device_likelihood_info says so); a single rank only. */
+int bpm_set_device_likelihood_data(bpm_handle_t h, const char* hip_source, const double* params, int32_t n_params, const double* data, int64_t n_data,
+                                   int32_t w);
+/* samplers.py:36-43: ln_like_fn(theta) at n given points X (n, dim) -- the installed device likelihood of any form, by its kernel of its own
+ * (bpm_eval_loglike is the same for the shipped targets).  Error when none is installed. */
+int bpm_eval_device_likelihood(bpm_handle_t h, const double* X, int32_t n, double* out);
+/* samplers.py:36-43 (the per-datum form of ln_like_fn): the number of consecutive data points one wavefront sums; with n_data it fixes the order of the additions */
+int bpm_data_likelihood_chunk(void);
 
 /* history of this rank's chains: out[(g - g_lo) * n_local * dim + i * dim + j], g in [g_lo, g_hi) */
 int bpm_get_history(bpm_handle_t h, int64_t g_lo, int64_t g_hi, double* out);
