@@ -140,6 +140,16 @@ class HistoryStatistics(object):
         eng = self._stats_engine("param_est_fn")
         return _dv.compute(eng.derive, self._stats_allgather, fn, n_burn, self.n_chains, eng.history_rows(), values=values)
 
+    def param_est_waic(self, pw, n_burn=0, values=False):
+        """WAIC and the pointwise expected log predictive density: `pw` (a pointwise.HipPointwise: the log density of ONE datum as a few
+        lines of HIP, with the data) over param_est(n_burn)[2]'s rows -- per datum log mean exp, variance and mean of its log densities
+        over the draws, the totals elpd_waic, p_waic, lppd, se and waic, the counts of what is not finite, and with values=True the
+        (rows, n_data) matrix itself in super-chain order.  Independent of how the sampler's likelihood was given.  Two results over the
+        same data compare with pointwise.compare_waic.  -> pointwise.PosteriorWaic; str() of it is a short table"""
+        from . import pointwise as _pw
+        eng = self._stats_engine("param_est_waic")
+        return _pw.compute(eng.pointwise, self._stats_allgather, pw, n_burn, self.n_chains, eng.history_rows(), values=values)
+
     def derived_history(self, fn):
         """A derived history is a history: `fn` (a derived.HipFunction) over every resident row, kept on the device as the history of a
         second handle with dim = fn.n_out and this sampler's log-likelihoods -- so every method of this class answers about the derived

@@ -9,6 +9,30 @@ typedef unsigned int uint32_t; typedef unsigned long uint64_t;
 #include "trace_acc.h"
 typedef double bpm_d2 __attribute__((ext_vector_type(2)));
 
+// Step 1 of a tile (derived.h), all 256 threads of the workgroup: the nr rows from local row t0 on into LDS at row stride ldp (odd, >= d).  No barrier.
+// (pointwise_rows.h stages its rows with it too and takes nothing else of this file: BPM_STAGE_ROWS_ONLY.)
+__device__ __forceinline__ void bpm_stage_rows(double* lds, const double* H, unsigned int ld, int d, unsigned long long t0, unsigned int nr, unsigned int ldp) {
+    // pair k of the region -> row k / (ld / 2), 8 pairs per thread in flight
+    const unsigned int tid = threadIdx.x;
+    const bpm_d2* src = (const bpm_d2*)(H + t0 * ld);
+    const unsigned int h = ld >> 1, total = nr * h;
+    for (unsigned int k0 = 0; k0 < total; k0 += 256u * 8u) {
+        bpm_d2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const unsigned int k = k0 + u * 256u + tid; v[u] = src[k < total ? k : total - 1u]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const unsigned int k = k0 + u * 256u + tid;
+            if (k < total) {
+                const unsigned int r = k / h, j = 2u * (k - r * h);
+                if (j < (unsigned int)d) lds[r * ldp + j] = v[u].x;
+                if (j + 1u < (unsigned int)d) lds[r * ldp + j + 1u] = v[u].y;
+            }
+        }
+    }
+}
+
+#ifndef BPM_STAGE_ROWS_ONLY
 // Steps 1 and 2 of a tile (derived.h), all 256 threads of the workgroup: the nr <= R rows from local row t0 on into LDS (lds: the dynamic LDS,
 // [rows R x ldp | ln-likes R | outputs R x ldo]), a barrier, thread r < nr calls derive on row r, a barrier.  -> the output tile (row stride ldo).
 // The caller may read it until it calls this again.
@@ -18,25 +42,7 @@ __device__ __forceinline__ double* bpm_derive_tile(double* lds, const double* H,
     double* const s_ll = lds + (unsigned long long)R * ldp;
     double* const s_out = s_ll + R;
     const unsigned int tid = threadIdx.x;
-    if (ldp != 0u) {
-        // pair k of the region -> row k / (ld / 2), 8 pairs per thread in flight
-        const bpm_d2* src = (const bpm_d2*)(H + t0 * ld);
-        const unsigned int h = ld >> 1, total = nr * h;
-        for (unsigned int k0 = 0; k0 < total; k0 += 256u * 8u) {
-            bpm_d2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const unsigned int k = k0 + u * 256u + tid; v[u] = src[k < total ? k : total - 1u]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const unsigned int k = k0 + u * 256u + tid;
-                if (k < total) {
-                    const unsigned int r = k / h, j = 2u * (k - r * h);
-                    if (j < (unsigned int)d) lds[r * ldp + j] = v[u].x;
-                    if (j + 1u < (unsigned int)d) lds[r * ldp + j + 1u] = v[u].y;
-                }
-            }
-        }
-    }
+    if (ldp != 0u) bpm_stage_rows(lds, H, ld, d, t0, nr, ldp);
     if (tid < nr) s_ll[tid] = LL[t0 + tid];
     __syncthreads();
     if (tid < nr) {
@@ -114,3 +120,4 @@ extern "C" __global__ void __launch_bounds__(256) bpm_derive_fill(const double* 
         }
     }
 }
+#endif      // BPM_STAGE_ROWS_ONLY

@@ -54,6 +54,7 @@
 #include "aql_queue.h"
 #include "user_likelihood.h"
 #include "derived.h"
+#include "pointwise.h"
 #include "embedded_src.h"
 
 using namespace bpm;
@@ -568,6 +569,20 @@ struct DerivedFunction {
     void leak() { mod.leak(); params.leak(); }
 };
 
+// A caller's log density of one datum, compiled around the streaming reduction of pointwise_rows.h (bpm_set_pointwise), with the device copy of the
+// caller's data (n_data, w): kept until replaced or bpm_destroy
+struct PointwiseFunction {
+    Module mod;
+    hipFunction_t fn = nullptr;              // bpm_pointwise_rows of THIS module
+    std::string src;                         // the source bytes, w and the data the module and the copy were made from: the same again only
+    std::vector<double> data_h;              // re-upload the parameters
+    int32_t w = 0;
+    int64_t n_data = 0;
+    DevTemp<double> data;
+    DevParams params;
+    void leak() { mod.leak(); data.leak(); params.leak(); }
+};
+
 // ---- the sampler ------------------------------------------------------------------------
 struct bpm_sampler {
     bpm_config_t cfg{};
@@ -652,6 +667,7 @@ struct bpm_sampler {
     std::vector<uint8_t> prop_done;          // [prop_chunks] 1: the piece's ln-likes have been handed in
     UserLikelihood like;                     // the caller's ln_like_fn given as HIP source (bpm_set_device_likelihood)
     DerivedFunction derived;                 // the caller's function of one sample (bpm_set_device_function)
+    PointwiseFunction pointwise;             // the caller's log density of one datum and its data (bpm_set_pointwise)
     double* aux_buf = nullptr;
     int32_t* ids_buf = nullptr;
     int32_t* trace_i32 = nullptr;      // per-chain decision trace (bpm_set_trace: test variant only; always null in the product library)
@@ -1259,8 +1275,8 @@ extern "C" int bpm_destroy(bpm_handle_t s) {
     s->mem.free_all();
     for (hipEvent_t e : s->chunk_ev) if (e) (void)hipEventDestroy(e);
     // (the run-time modules and their parameter blocks go the way of the buffers)
-    if (free_buffers) { s->like.fused.drop(s->dq); s->like = UserLikelihood(); s->derived = DerivedFunction(); }
-    else { s->like.leak(); s->derived.leak(); }
+    if (free_buffers) { s->like.fused.drop(s->dq); s->like = UserLikelihood(); s->derived = DerivedFunction(); s->pointwise = PointwiseFunction(); }
+    else { s->like.leak(); s->derived.leak(); s->pointwise.leak(); }
     for (auto& B : s->tb)
         if (B.built) (void)hipEventDestroy(B.built);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -4135,6 +4151,116 @@ extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, doubl
         for (int f = 0; f < 2; ++f) std::memcpy(&counts[(size_t)f * n_out + m], &h[(size_t)count_f[f] * n_out + m], 8);
         for (int f = 0; f < 5; ++f) sums[(size_t)f * n_out + m] = h[(size_t)sum_f[f] * n_out + m];
     }
+    return 0;
+}
+
+// ---- WAIC's ingredients per datum of a caller's data (pointwise.h, pointwise_rows.h; bipymc_amd/pointwise.py merges the ranks and finishes) --------
+// The reference has no such statistic: its fitting scripts sum a log density over their data points inside ln_like_fn (examples/ex_line_fit.py:63-67);
+// here one term of that sum is the caller's, and its log-sum-exp and moments over the draws are taken where the history lives.
+static int check_pointwise_w(const char* who, int32_t w) {
+    if (w < 1 || w > bpm::PW_MAX_W) return fail(std::string(who) + ": w must be 1 ... " + std::to_string(bpm::PW_MAX_W) + " (got " + std::to_string(w) + ")");
+    return 0;
+}
+
+extern "C" int bpm_check_pointwise(const char* hip_source, int32_t w, const char* arch, char* log, int64_t log_cap) {
+    if (!hip_source) return fail("bpm_check_pointwise: null source");
+    CK(check_pointwise_w("bpm_check_pointwise", w));
+    std::vector<char> code;
+    const std::string why = bpm::compile_pointwise(hip_source, w, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
+    bpm::copy_text(why, log, log_cap);
+    return why.empty() ? 0 : fail("bpm_check_pointwise: " + why);
+}
+
+extern "C" int bpm_set_pointwise(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params, const double* data, int64_t n_data, int32_t w,
+                                 int32_t* reused) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_pointwise: bad argument");
+    CK(check_pointwise_w("bpm_set_pointwise", w));
+    if (!data || n_data < 1 || n_data > (int64_t)0x7fffffff) return fail("bpm_set_pointwise: data must be (n_data, w) with 1 <= n_data < 2^31");
+    const size_t n_val = (size_t)n_data * (size_t)w;
+    // built beside the installed function, which stays whole until nothing can fail any more; the same source bytes, w and data: the parameters only
+    PointwiseFunction& cur = s->pointwise;
+    const bool rebuild = !cur.fn || cur.w != w || cur.n_data != n_data || cur.src != hip_source || std::memcmp(cur.data_h.data(), data, n_val * sizeof(double)) != 0;
+    if (reused) *reused = rebuild ? 0 : 1;
+    PointwiseFunction next;
+    if (rebuild) {
+        hipDeviceProp_t prop;
+        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
+        std::vector<char> code;
+        const std::string why = bpm::compile_pointwise(hip_source, w, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
+        if (!why.empty()) return fail("bpm_set_pointwise: " + why);
+        HIPCK(next.mod.load(code));
+        next.fn = next.mod.function("bpm_pointwise_rows");
+        if (!next.fn) return fail("bpm_set_pointwise: the compiled module has no bpm_pointwise_rows kernel");
+        next.src = hip_source;
+        next.w = w;
+        next.n_data = n_data;
+        next.data_h.assign(data, data + n_val);
+        CK(next.data.alloc(n_val, "bpm_set_pointwise", "the data"));
+        HIPCK(hipMemcpyAsync(next.data.p, data, n_val * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
+    CK(next.params.upload(params, n_params, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));                          // (a previous function's launches are done; `params` and `data` are the caller's again)
+    if (rebuild) s->pointwise = std::move(next);
+    else s->pointwise.params = std::move(next.params);
+    return 0;
+}
+
+extern "C" int bpm_pointwise_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t* out) {
+    if (!out || d < 1 || n_rows < 0 || n_data < 1 || n_data > (int64_t)0x7fffffff) return fail("bpm_pointwise_layout: bad argument");
+    CK(check_pointwise_w("bpm_pointwise_layout", w));
+    const bpm::PointwiseLayout L = bpm::pointwise_layout((uint32_t)d, (uint64_t)n_rows, (uint64_t)n_data);
+    out[0] = bpm::PW_THREADS; out[1] = L.R; out[2] = (int64_t)L.parts; out[3] = (int64_t)L.chunk;
+    return 0;
+}
+
+// Over this rank's super-chain rows >= n_burn (bpm_reduce_moments' selection: a partial first generation by chain index), per datum i of the installed
+// function's data: records = [PW_FIELDS][n_data] (pointwise_rows.h), counts as 64-bit words.  *n_rows: the window's local rows, *n_first of them in a
+// partial first generation.  values (may be null): values[r * n_data + i] for the window's local rows r in order, at most values_cap doubles.
+// Keeps no state; every buffer but the function's own data and parameters is temporary.
+extern "C" int bpm_pointwise(bpm_handle_t s, int64_t n_burn, double* records, int64_t* n_rows, int64_t* n_first, double* values, int64_t values_cap) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!records || !n_rows || !n_first) return fail("bpm_pointwise: null argument");
+    if (n_burn < 0) return fail("bpm_pointwise: n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
+    if (!s->pointwise.fn) return fail("bpm_pointwise: no pointwise function installed (bpm_set_pointwise)");
+    CK(require_resident_history(s, "bpm_pointwise"));
+    uint64_t lo = 0, hi = 0;
+    CK(super_chain_window(s, n_burn, &lo, &hi));
+    const uint64_t rows = hi - lo, n_data = (uint64_t)s->pointwise.n_data;
+    *n_rows = (int64_t)rows;
+    *n_first = (int64_t)(rows % s->n_local);
+    std::memset(records, 0, (size_t)PW_FIELDS * n_data * sizeof(double));
+    if (rows == 0) return 0;
+    const uint64_t n_val = rows * n_data;
+    if (values) {
+        if (n_val >= (1ull << 31))
+            return fail("bpm_pointwise: the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string((unsigned long long)n_data) +
+                        " data points are " + std::to_string((unsigned long long)n_val) + " elements; fewer than 2^31 per rank can be returned");
+        if (values_cap < 0 || (uint64_t)values_cap < n_val)
+            return fail("bpm_pointwise: values holds " + std::to_string((long long)values_cap) + " doubles; the window needs " + std::to_string((unsigned long long)n_val));
+    }
+    const bpm::PointwiseLayout L = bpm::pointwise_layout(s->dim, rows, n_data);
+    if (L.parts * L.n_tiles >= (1ull << 31)) return fail("bpm_pointwise: window too large");
+    CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
+    // [part records | folded records]; with one part the part records are the folded ones
+    const uint64_t n_rec = L.parts * n_data;
+    const size_t o_fold = (size_t)PW_FIELDS * n_rec;
+    DevTemp<double> b, v;
+    CK(b.alloc(o_fold + (L.parts > 1 ? (size_t)PW_FIELDS * n_data : 0), "bpm_pointwise", "the part records of " + std::to_string((unsigned long long)L.parts) + " parts"));
+    if (values) CK(v.alloc((size_t)n_val, "bpm_pointwise", "the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string((unsigned long long)n_data) + " data points"));
+    HIPCK(ModuleLaunch<bpm::PointwiseRowsKernel>::on(s->stream, s->pointwise.fn, (unsigned)(L.parts * L.n_tiles), PW_THREADS, L.lds_bytes, s->hist, s->ld, (int)s->dim, lo, hi,
+                                                     L.chunk, (unsigned)L.n_tiles, s->pointwise.params.p, s->pointwise.data.p, (unsigned)n_data, L.R, L.ldp, b.p, n_rec, v.p));
+    const double* rec = b.p;
+    if (L.parts > 1) {
+        hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)L.n_tiles), dim3(PW_THREADS), 0, s->stream, (const double*)b.p, (uint32_t)L.parts, n_data, b.p + o_fold);
+        HIPCK(hipGetLastError());
+        rec = b.p + o_fold;
+    }
+    HIPCK(hipMemcpyAsync(records, rec, (size_t)PW_FIELDS * n_data * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (values) HIPCK(hipMemcpyAsync(values, v.p, (size_t)n_val * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }
 

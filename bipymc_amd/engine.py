@@ -619,6 +619,63 @@ class HipEngine(object):
         self.set_device_function(fn.source, fn.n_out, fn.params)
         return self.derive_rows(n_burn, values)
 
+    def set_pointwise(self, source, data, params=()):
+        """The log density of one datum as HIP source (include/bipymc_hip.h: bpm_set_pointwise): compiled around the streaming reduction of
+        bipymc_amd/csrc/pointwise_rows.h and kept on the handle with a device copy of `data` (n_data, w); the same source, w and data
+        again only copy `params`.  -> True when the loaded program and the data were kept"""
+        p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+        y = np.ascontiguousarray(data, dtype=np.float64)
+        src = source.encode() if isinstance(source, str) else bytes(source)
+        reused = C.c_int32(0)
+        self._ck(self.lib.bpm_set_pointwise(self._h, src, _dptr(p) if p.size else None, int(p.size), _dptr(y), int(y.shape[0]), int(y.shape[1]),
+                                            C.byref(reused)))
+        self._pointwise_n_data = int(y.shape[0])
+        return bool(reused.value)
+
+    def pointwise_window_rows(self, n_burn):
+        """this rank's rows of the window (super_chain_window's count: a partial first generation by chain index)"""
+        G = self.history_rows()
+        g0, first = n_burn // self.n_chains, min(max(n_burn % self.n_chains - self.lo, 0), self.n_local)
+        return max(0, (G - g0) * self.n_local - first) if g0 < G else 0
+
+    def pointwise_rows(self, n_burn, values=False):
+        """-> (counts (4, n_data) int64, sums (5, n_data), n_rows, n_first, values (n_rows, n_data) or None): the installed pointwise
+        function over this rank's super-chain rows >= n_burn -- per datum how many values are finite | NaN | +inf | -inf, and of the
+        finite ones a shift | the shifted sum | the shifted sum of squares | their maximum m | s = sum exp(l - m); n_first of the n_rows
+        rows lie in a partial first generation (bpm_pointwise)"""
+        nd = getattr(self, "_pointwise_n_data", 0)
+        n_burn = int(n_burn)
+        rec = np.zeros((L.PW_FIELDS, max(nd, 1)))
+        n_rows = C.c_int64(0); n_first = C.c_int64(0)
+        vals, cap = None, 0
+        if values and nd and n_burn >= 0:
+            cap = self.pointwise_window_rows(n_burn) * nd
+            vals = np.empty(max(cap, 1))
+        self._ck(self.lib.bpm_pointwise(self._h, n_burn, _dptr(rec), C.byref(n_rows), C.byref(n_first), None if vals is None else _dptr(vals), cap))
+        n = int(n_rows.value)
+        rec = rec[:, :nd]
+        counts = np.ascontiguousarray(rec[[L.PW_N, L.PW_NAN, L.PW_PINF, L.PW_NINF]]).view(np.int64)
+        sums = np.ascontiguousarray(rec[[L.PW_C, L.PW_S1, L.PW_S2, L.PW_M, L.PW_S]])
+        return counts, sums, n, int(n_first.value), None if vals is None else vals[:n * nd].reshape(n, nd)
+
+    def pointwise(self, pw, n_burn, values=False):
+        """pointwise.compute's per-rank call: installs `pw` (a pointwise.HipPointwise) and reduces (set_pointwise + pointwise_rows).  The
+        values of 2^31 elements or more are refused before anything is installed or allocated."""
+        if values and int(n_burn) >= 0:
+            rows = self.pointwise_window_rows(int(n_burn))
+            if rows * pw.n_data >= 1 << 31:
+                raise ValueError("param_est_waic: the values of %d rows x %d data points are %d elements; fewer than 2^31 per rank can be returned"
+                                 % (rows, pw.n_data, rows * pw.n_data))
+        self.set_pointwise(pw.source, pw.data, pw.params)
+        return self.pointwise_rows(n_burn, values)
+
+    def pointwise_layout(self, n_rows, n_data, w=1):
+        """-> (T, R, parts, rows per part): data per tile, rows per staged tile, row parts and the rows of a part (the last: what is left) of
+        a launch over n_rows rows of this engine's dim and n_data data (bpm_pointwise_layout: a function of these numbers alone)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.bpm_pointwise_layout(int(self.dim), int(w), int(n_rows), int(n_data), out))
+        return tuple(int(x) for x in out)
+
     def _second_engine(self, dim):
         """the destination of derive_history / rank_history: a history-keeping host-callback engine of this one's chains, library and device"""
         return HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=dim, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,

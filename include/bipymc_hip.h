@@ -436,6 +436,37 @@ int bpm_check_device_function(const char* hip_source, int32_t n_out, const char*
 int bpm_set_device_function(bpm_handle_t h, const char* hip_source, int32_t n_out, const double* params, int32_t n_params);
 int bpm_derive(bpm_handle_t h, int64_t n_burn, int64_t* counts, double* sums, int64_t* n_rows, int64_t* n_first, double* values,
                int64_t values_cap);
+/* WAIC AND THE POINTWISE LOG PREDICTIVE DENSITY on the device: which of two models predicts the data better.  The reference has no such
+ * statistic; its fitting scripts sum a log density over their data points inside ln_like_fn (examples/ex_line_fit.py:63-67).  Here ONE term of
+ * that sum is the caller's, `hip_source` defines
+ *     __device__ double ln_like_point(const double* x, int d, const double* y, int i, const double* p)
+ * (x: one super-chain row of d coordinates; y: the w values of datum i, 1 <= w <= 64; p: the caller's parameter block; device math functions,
+ * INFINITY, NAN and M_PI as for ln_like; compiled -O3 -ffp-contract=off), and the library compiles a streaming reduction around it with hiprtc
+ * whose parallel axis is the data (bipymc_amd/csrc/pointwise.h, pointwise_rows.h): a thread per datum meets the window's rows in ascending order
+ * and keeps, in registers, an online log-sum-exp and the shifted moments of its values l.
+ * bpm_check_pointwise compiles only (no sampler, no GPU needed; arch NULL = "gfx950"): 0 or -1 with the reason in `log` (and bpm_last_error).
+ * bpm_set_pointwise compiles for the handle's device, loads the module, copies `data` ((n_data, w) float64 row-major, 1 <= n_data < 2^31) to
+ * the device once and the n_params doubles of `params`; the handle owns all three until another function replaces them or bpm_destroy.  The
+ * same source bytes, w and data contents again keep module and data and only copy `params` (*reused, may be NULL: 1 then, else 0).  Any
+ * sampler may carry one, whatever its target or likelihood.
+ * bpm_pointwise: over this rank's super-chain rows >= n_burn (bpm_reduce_moments' selection), per datum i: records = [9][n_data], field f of
+ * datum i at records[f * n_data + i]: 0 the count n of finite l (64-bit word) | 1 a shift c (the first finite l) | 2 sum (l - c) | 3 sum
+ * (l - c)^2 over the finite l | 4, 5, 6 how many l are NaN, +inf, -inf (64-bit words) | 7 m, the largest finite l | 8 s = sum exp(l - m) over
+ * the finite l (their log-sum-exp is m + log s; m = -inf, s = 0 where n = 0).  *n_rows, *n_first, values (values[r * n_data + i]) and values_cap
+ * as bpm_derive's.  bpm_pointwise_layout: out[4] = T (data per tile, threads per workgroup) | R (rows per staged tile) | row parts | rows per
+ * part (the last part: what is left) of a launch over n_rows rows of d coordinates and n_data data -- a function of these numbers alone, not of
+ * the device, the free memory or the environment.  Every partial result is merged in a fixed order (a thread's rows ascending, the parts in
+ * index order) and there is no atomic: the bits are a function of (window, data, params).  An infinite or NaN l is counted and never reaches an
+ * exp: no inf - inf is formed.  bipymc_amd/pointwise.py merges the ranks by the same formulas and finishes lppd, p_waic and elpd.
+ * Nothing the samplers read is written (a history kept in position order is put into chain order first, as bpm_get_history does).  Errors: w
+ * or n_data out of range, a source that does not compile (the compiler's log in bpm_last_error), no function installed, n_burn < 0, no
+ * resident history (keep_history = 0), values beyond values_cap or of 2^31 elements or more, data, records or values larger than the free
+ * device memory (the message names the requirement). */
+int bpm_check_pointwise(const char* hip_source, int32_t w, const char* arch, char* log, int64_t log_cap);
+int bpm_set_pointwise(bpm_handle_t h, const char* hip_source, const double* params, int32_t n_params, const double* data, int64_t n_data, int32_t w,
+                      int32_t* reused);
+int bpm_pointwise(bpm_handle_t h, int64_t n_burn, double* records, int64_t* n_rows, int64_t* n_first, double* values, int64_t values_cap);
+int bpm_pointwise_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t* out);
 /* A DERIVED HISTORY IS A HISTORY: the installed function of `src` (bpm_set_device_function) over EVERY resident row of src, written into the
  * history of `dst` -- a second, ordinary handle made by bpm_create with the host-callback target, keep_history = 1, dim = n_out and src's
  * n_chains -- so that every statistic above (bpm_reduce_moments, bpm_diag_*, bpm_quantile_*, bpm_reduce_cov, bpm_hist_*, bpm_trace_*, bpm_derive
