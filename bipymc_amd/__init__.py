@@ -14,5 +14,5 @@ from .covariance import PosteriorCovariance  # noqa: F401
 from .histograms import PosteriorHistograms  # noqa: F401
 from .traces import PosteriorTrace  # noqa: F401
 from .derived import DerivedHistory, HipFunction, PosteriorDerived  # noqa: F401
-from .pointwise import HipPointwise, PosteriorWaic, compare_waic  # noqa: F401
+from .pointwise import HipPointwise, PosteriorLoo, PosteriorWaic, compare_loo, compare_waic  # noqa: F401
 from .summary import PosteriorHDI, PosteriorSummary  # noqa: F401

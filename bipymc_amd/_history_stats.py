@@ -150,6 +150,23 @@ class HistoryStatistics(object):
         eng = self._stats_engine("param_est_waic")
         return _pw.compute(eng.pointwise, self._stats_allgather, pw, n_burn, self.n_chains, eng.history_rows(), values=values)
 
+    def param_est_loo(self, pw, n_burn=0, r_eff=1.0, tails=False):
+        """PSIS-LOO, the leave-one-out expected log predictive density with its Pareto-k diagnostic per datum: `pw` (the HipPointwise of
+        param_est_waic) over param_est(n_burn)[2]'s rows -- per datum elpd_loo_i, pareto_k (above 0.7: the estimate for this datum cannot be
+        trusted; it is an outlier or has leverage), lppd_i (param_est_waic's bits), p_loo_i and tail_len, the totals elpd_loo, p_loo, se,
+        looic and n_bad_k; with tails=True each datum's kept values too.  r_eff: the relative efficiency of the draws, a scalar or one per
+        datum, > 0; it only sets the tail length M = ceil(min(S / 5, 3 sqrt(S / r_eff))).  1.0 is what ArviZ assumes when it is not told; a
+        DREAM or DE-MC population's draws are autocorrelated, and convergence_diagnostics(...).ess of derived_history(exp(l)) divided by
+        the draws n is a way to obtain it.  Each datum's tail is selected exactly on the device, in scratch of at most BPM_LOO_SCRATCH_MB
+        (by default a quarter of the free memory); kept sets that cannot fit are refused with advice.  Two results over the same data
+        compare with pointwise.compare_loo.  Single rank only.  -> pointwise.PosteriorLoo; str() of it is a short table"""
+        from . import pointwise as _pw
+        from . import rank_diagnostics as _rk
+        who = "param_est_loo"
+        _rk.check_single_rank(who, getattr(getattr(self, "comm", None), "size", 1))
+        eng = self._stats_engine(who)
+        return _pw.compute_loo(eng, self._stats_allgather, pw, n_burn, self.n_chains, r_eff=r_eff, tails=tails)
+
     def derived_history(self, fn):
         """A derived history is a history: `fn` (a derived.HipFunction) over every resident row, kept on the device as the history of a
         second handle with dim = fn.n_out and this sampler's log-likelihoods -- so every method of this class answers about the derived

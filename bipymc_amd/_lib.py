@@ -126,12 +126,17 @@ SIGNATURES = {
     "bpm_set_pointwise": (C.c_int, [_H, C.c_char_p, _dp, C.c_int32, _dp, C.c_int64, C.c_int32, _P(C.c_int32)]),
     "bpm_pointwise": (C.c_int, [_H, C.c_int64, _dp, _P(C.c_int64), _P(C.c_int64), _dp, C.c_int64]),
     "bpm_pointwise_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "bpm_loo_kept": (C.c_int64, [C.c_int64, C.c_double]),
+    "bpm_loo_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P(C.c_int64)]),
+    "bpm_loo": (C.c_int, [_H, C.c_int64, _dp, _dp, _dp, C.c_int64, _P(C.c_int64)]),
     "bpm_rank_history": (C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _P(C.c_int64), _dp]),
     "bpm_hdi": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _P(C.c_int64), _dp, _dp, _P(C.c_int64), _dp, _P(C.c_int64)]),
 }
 
 # fields of bpm_pointwise's records (bipymc_amd/csrc/pointwise_rows.h)
 PW_N, PW_C, PW_S1, PW_S2, PW_NAN, PW_PINF, PW_NINF, PW_M, PW_S, PW_FIELDS = range(10)
+# fields of bpm_loo's records (bipymc_amd/csrc/psis.h)
+LOO_ELPD, LOO_K, LOO_SIGMA, LOO_TAIL_LEN, LOO_KEPT, LOO_BODY_N, LOO_BODY_M, LOO_BODY_S, LOO_FIELDS = range(9)
 
 # include/bipymc_hip_test.h: exported by the test variant only
 TEST_SIGNATURES = {
@@ -178,7 +183,7 @@ def load():
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
 _ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/accept_test.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/accept_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/device_memory.h", "csrc/user_likelihood.h", "csrc/derived.h",
-            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_eval_data.h", "csrc/user_target.h", "csrc/derive_rows.h", "csrc/pointwise.h", "csrc/pointwise_rows.h",
+            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_eval_data.h", "csrc/user_target.h", "csrc/derive_rows.h", "csrc/pointwise.h", "csrc/pointwise_rows.h", "csrc/pointwise_tail.h", "csrc/psis.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 

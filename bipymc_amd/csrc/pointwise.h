@@ -59,6 +59,73 @@ inline std::string compile_pointwise(const std::string& user_src, int w, const s
                        "const double* p)`):\n", code);
 }
 
+// ---- PSIS-LOO's streaming stages (pointwise_tail.h states the kernels; psis.h fits and finishes) ------------------------------------------
+constexpr uint32_t PT_HIST_BYTES = 16 * 1024;    // the radix select's 16 counters per lane, behind the row tile in LDS
+
+// bpm_pointwise_tail: H, ld, d, lo, hi, chunk, n_tiles, tile0, params, data, n_data, R, ldp, lds_rows, keep, cap, buf, cnt, bad, compactions
+using PointwiseTailKernel = void(const double*, unsigned int, int, unsigned long long, unsigned long long, unsigned long long, unsigned int, unsigned int,
+                                 const double*, const double*, unsigned int, unsigned int, unsigned int, unsigned int, const unsigned int*, unsigned int,
+                                 unsigned long long*, unsigned int*, unsigned int*, unsigned int*);
+// bpm_pointwise_tail_final: n_tiles, tile0, parts, n_data, keep, cap, k_max, buf, cnt, bad, out, n_kept, n_bad
+using PointwiseTailFinalKernel = void(unsigned int, unsigned int, unsigned int, unsigned int, const unsigned int*, unsigned int, unsigned int, unsigned long long*,
+                                      const unsigned int*, const unsigned int*, unsigned long long*, unsigned int*, unsigned int*);
+// bpm_pointwise_body: H, ld, d, lo, hi, chunk, n_tiles, tile0, params, data, n_data, R, ldp, cut, rec, n_rec
+using PointwiseBodyKernel = void(const double*, unsigned int, int, unsigned long long, unsigned long long, unsigned long long, unsigned int, unsigned int,
+                                 const double*, const double*, unsigned int, unsigned int, unsigned int, const double*, double*, unsigned long long);
+
+// Stage A's launch: the data go in batches of `batch_tiles` tiles; a batch's rows in `parts` parts of `chunk` rows, each (tile, part) with a
+// candidate buffer of 256 columns of cap = 2 k_max keys.  Unlike pointwise_layout this one may depend on the scratch budget: selection is exact.
+struct LooLayout {
+    uint64_t batch_tiles = 0, batches = 0, parts = 0, chunk = 0, cap = 0;
+    uint64_t per_tile_bytes = 0;      // of one tile of a batch: its parts' buffers and counters, the final keys twice (the sort's in and out), the fit's work space, stage B's records
+    bool fits = false;
+    bool too_many_keys = false;       // one tile's final keys (256 k_max) are beyond the sort's 32-bit index: no budget helps
+};
+
+// Parts: as many as keep the device busy (PW_GRID / batch_tiles), none shorter than max(4 R, 8 k_max) rows -- a part must be long against its
+// buffer for the threshold to do its work -- none of 2^31 rows or more, and no more than the budget holds.  fits = false: not even one tile
+// with one part fits (per_tile_bytes says what that takes, the sort's temporaries not counted).
+inline LooLayout loo_layout(const PointwiseLayout& P, uint64_t n_rows, uint64_t k_max, uint64_t work_doubles, uint64_t budget) {
+    LooLayout L;
+    L.cap = 2 * k_max;
+    if (n_rows == 0 || P.n_tiles == 0 || k_max == 0) return L;
+    const uint64_t T = PW_THREADS;
+    const uint64_t part_bytes = T * L.cap * 8 + T * 8 + 4;                                      // buffer | cnt, bad | compactions
+    const uint64_t tile_fixed = 2 * T * k_max * 8 + T * 8 + T * work_doubles * 8 + T * 8 + 3 * P.parts * T * 8;      // keys in, out | n_kept, n_bad | work | cut | body records
+    const uint64_t shortest = 4ull * P.R > 8 * k_max ? 4ull * P.R : 8 * k_max;
+    uint64_t by_rows = n_rows / shortest > 1 ? n_rows / shortest : 1;
+    const uint64_t fewest = (n_rows >> 31) + 1;
+    by_rows = by_rows > fewest ? by_rows : fewest;
+    L.per_tile_bytes = fewest * part_bytes + tile_fixed;
+    if (L.per_tile_bytes > budget) return L;
+    L.fits = true;
+    uint64_t bt = budget / L.per_tile_bytes;
+    bt = bt < P.n_tiles ? bt : P.n_tiles;
+    const uint64_t most_keys = ((1ull << 31) - 1) / (T * k_max);      // (the segmented sort indexes a batch's keys with 32 bits)
+    bt = bt < most_keys ? bt : most_keys;
+    if (bt == 0) { L.fits = false; L.too_many_keys = true; return L; }
+    uint64_t parts = PW_GRID / bt > 1 ? PW_GRID / bt : 1;
+    parts = parts < by_rows ? parts : by_rows;
+    const uint64_t by_budget = (budget / bt - tile_fixed) / part_bytes;
+    parts = parts < by_budget ? parts : by_budget;
+    parts = parts > fewest ? parts : fewest;
+    L.chunk = (n_rows + parts - 1) / parts;
+    L.parts = (n_rows + L.chunk - 1) / L.chunk;
+    L.batch_tiles = bt;
+    L.batches = (P.n_tiles + bt - 1) / bt;
+    L.per_tile_bytes = L.parts * part_bytes + tile_fixed;
+    return L;
+}
+
+// caller's source + pointwise_tail.h -> code object for `arch` (the kernels of stages A and B).  -> "" and `code`, or the reason
+inline std::string compile_pointwise_tail(const std::string& user_src, int w, const std::string& arch, const RtcHeader* headers, size_t n_headers, std::vector<char>& code) {
+    const std::string src = std::string(RTC_PRELUDE) + "#define BPM_POINTWISE_W " + std::to_string(w) + "\n#line 1 \"ln_like_point.hip\"\n" + user_src +
+                            "\n#include \"pointwise_tail.h\"\n";
+    return rtc_compile(src, "ln_like_point.hip", headers, n_headers, arch, {},
+                       "the pointwise source does not compile (it must define `__device__ double ln_like_point(const double* x, int d, const double* y, int i, "
+                       "const double* p)`):\n", code);
+}
+
 #if defined(__HIPCC__)
 // The parts of every datum in index order -> one folded record per datum (pointwise_rows.h, step 4).  part: PW_FIELDS fields of parts * n_data
 // records; out: PW_FIELDS fields of n_data records.

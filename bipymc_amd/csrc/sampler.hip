@@ -55,6 +55,7 @@
 #include "user_likelihood.h"
 #include "derived.h"
 #include "pointwise.h"
+#include "psis.h"
 #include "embedded_src.h"
 
 using namespace bpm;
@@ -580,7 +581,9 @@ struct PointwiseFunction {
     int64_t n_data = 0;
     DevTemp<double> data;
     DevParams params;
-    void leak() { mod.leak(); data.leak(); params.leak(); }
+    Module tail_mod;                         // pointwise_tail.h around the same source (bpm_loo compiles it at its first call): stages A and B of PSIS-LOO
+    hipFunction_t tail_fn = nullptr, tail_final_fn = nullptr, body_fn = nullptr;
+    void leak() { mod.leak(); tail_mod.leak(); data.leak(); params.leak(); }
 };
 
 // ---- the sampler ------------------------------------------------------------------------
@@ -4340,6 +4343,181 @@ struct RankSegment {
 static hipError_t rank_sort(void* tmp, size_t* tmp_bytes, unsigned long long* in, unsigned long long* out, uint32_t bc, uint32_t S, hipStream_t st) {
     auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), RankSegment{S});
     return rocprim::segmented_radix_sort_keys(tmp, *tmp_bytes, in, out, bc * S, bc, seg, seg + 1, 0u, 64u, st);
+}
+
+// ---- PSIS-LOO per datum (pointwise_tail.h: the exact tail and the body's log-sum-exp; psis.h: fit and finish; bipymc_amd/pointwise.py) ------------
+// The reference has no such statistic.  bpm_loo_kept: the size K of a datum's kept set for a window of n_rows draws (psis.h: psis_kept).
+extern "C" int64_t bpm_loo_kept(int64_t n_rows, double r_eff) {
+    if (n_rows < 0 || !(r_eff > 0.0) || !std::isfinite(r_eff)) return -1;
+    return (int64_t)bpm::psis_kept((uint64_t)n_rows, r_eff);
+}
+
+// the scratch budget of a call: BPM_LOO_SCRATCH_MB, or a quarter of the free memory (read at every call)
+static uint64_t loo_budget(size_t mem_free) {
+    if (const char* mb = getenv("BPM_LOO_SCRATCH_MB")) return (uint64_t)std::max(atoll(mb), 0ll) << 20;
+    return (uint64_t)mem_free / 4;
+}
+static int loo_plan(const std::string& who, uint32_t d, uint64_t n_rows, uint64_t n_data, uint64_t k_max, uint64_t budget, bool from_env_or_free, size_t mem_free,
+                    bpm::PointwiseLayout* P, bpm::LooLayout* A) {
+    *P = bpm::pointwise_layout(d, n_rows, n_data);
+    *A = bpm::loo_layout(*P, n_rows, k_max, bpm::psis_work(k_max), budget);
+    if (n_rows > 0 && A->too_many_keys)
+        return fail(who + ": kept sets of " + std::to_string((unsigned long long)k_max) + " values are too large: one tile of " + std::to_string(bpm::PW_THREADS) +
+                    " data must hold fewer than 2^31 keys for the sort (raise r_eff towards 1, shorten the window with n_burn, or thin the history)");
+    if (n_rows > 0 && !A->fits)
+        return fail(who + ": the kept sets of one tile of " + std::to_string(bpm::PW_THREADS) + " data (" + std::to_string((unsigned long long)k_max) +
+                    " of " + std::to_string((unsigned long long)n_rows) + " draws each) need " + std::to_string((unsigned long long)A->per_tile_bytes) +
+                    " bytes of scratch; the budget is " + std::to_string((unsigned long long)budget) + " bytes" +
+                    (from_env_or_free ? " (BPM_LOO_SCRATCH_MB; by default a quarter of the free device memory: " + std::to_string(mem_free >> 20) + " MiB are free)" : std::string()) +
+                    ": raise r_eff towards 1, shorten the window with n_burn, or thin the history");
+    if (n_rows > 0 && (A->parts * A->batch_tiles >= (1ull << 31) || P->parts * A->batch_tiles >= (1ull << 31) || 2 * k_max >= (1ull << 32)))
+        return fail(who + ": window too large");
+    return 0;
+}
+
+extern "C" int bpm_loo_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t k_max, int64_t budget_bytes, int64_t* out) {
+    if (!out || d < 1 || n_rows < 0 || n_data < 1 || n_data > (int64_t)0x7fffffff || k_max < 1 || k_max > std::max<int64_t>(n_rows, 1) || budget_bytes < 0)
+        return fail("bpm_loo_layout: bad argument");
+    CK(check_pointwise_w("bpm_loo_layout", w));
+    bpm::PointwiseLayout P;
+    bpm::LooLayout A;
+    CK(loo_plan("bpm_loo_layout", (uint32_t)d, (uint64_t)n_rows, (uint64_t)n_data, (uint64_t)k_max, (uint64_t)budget_bytes, false, 0, &P, &A));
+    out[0] = bpm::PW_THREADS; out[1] = P.R; out[2] = (int64_t)A.parts; out[3] = (int64_t)A.chunk; out[4] = (int64_t)A.batch_tiles; out[5] = (int64_t)A.batches;
+    out[6] = (int64_t)P.parts; out[7] = (int64_t)P.chunk;
+    return 0;
+}
+
+// Over this rank's super-chain rows >= n_burn (bpm_pointwise's window; single rank), per datum i of the installed function's data with relative
+// efficiency r_eff[i]: records = [LOO_FIELDS][n_data] (psis.h).  tails (may be null): tails[i * k_max + j], j < kept_i, the kept values ascending, k_max the
+// largest kept set of the call (stats[1]).  stats[12]: rows | k_max | stage A's parts | data batches | the most compactions a workgroup of stage A made |
+// stage B's parts | stage B's rows per part | the scratch budget in bytes | the microseconds of stage A (selection, merge, sort), of B and of C on the
+// device, summed over the batches (event pairs on the stream) | 1 if this call compiled the module of stages A and B, 0 if it was kept.  Every check
+// and the plan come before this call compiles or allocates anything (the function installed by bpm_set_pointwise is there already).
+extern "C" int bpm_loo(bpm_handle_t s, int64_t n_burn, const double* r_eff, double* records, double* tails, int64_t tails_cap, int64_t* stats) {
+    const std::string who = "bpm_loo";
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (!r_eff || !records || !stats) return fail(who + ": null argument");
+    if (n_burn < 0) return fail(who + ": n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
+    if (s->world != 1) return fail(who + ": single rank only (world_size " + std::to_string(s->world) + ")");
+    PointwiseFunction& f = s->pointwise;
+    if (!f.fn) return fail(who + ": no pointwise function installed (bpm_set_pointwise)");
+    CK(require_resident_history(s, who.c_str()));
+    uint64_t lo = 0, hi = 0;
+    CK(super_chain_window(s, n_burn, &lo, &hi));
+    const uint64_t rows = hi - lo, n_data = (uint64_t)f.n_data;
+    std::memset(records, 0, (size_t)bpm::LOO_FIELDS * n_data * sizeof(double));
+    std::memset(stats, 0, 12 * sizeof(int64_t));
+    stats[0] = (int64_t)rows;
+    if (rows == 0) return 0;
+    std::vector<unsigned int> keep_h((size_t)n_data);
+    uint64_t k_max = 0;
+    for (uint64_t i = 0; i < n_data; ++i) {
+        if (!(r_eff[i] > 0.0) || !std::isfinite(r_eff[i])) return fail(who + ": r_eff must be finite and > 0 (datum " + std::to_string((unsigned long long)i) + ")");
+        const uint64_t K = bpm::psis_kept(rows, r_eff[i]);
+        if (K >= (1ull << 31)) return fail(who + ": window too large");
+        keep_h[(size_t)i] = (unsigned int)K;
+        k_max = std::max(k_max, K);
+    }
+    if (tails && (tails_cap < 0 || (uint64_t)tails_cap < n_data * k_max))
+        return fail(who + ": tails holds " + std::to_string((long long)tails_cap) + " doubles; " + std::to_string((unsigned long long)n_data) + " data x " +
+                    std::to_string((unsigned long long)k_max) + " kept values are needed");
+    size_t mem_free = 0, mem_total = 0;
+    HIPCK(hipMemGetInfo(&mem_free, &mem_total));
+    const uint64_t budget = loo_budget(mem_free);
+    bpm::PointwiseLayout P;
+    bpm::LooLayout A;
+    CK(loo_plan(who, s->dim, rows, n_data, k_max, budget, true, mem_free, &P, &A));
+    const uint64_t nbt = A.batch_tiles, n_cols = nbt * bpm::PW_THREADS, n_wg = A.parts * nbt, ws_stride = bpm::psis_work(k_max);
+    size_t sort_bytes = 0;
+    HIPCK(rank_sort(nullptr, &sort_bytes, nullptr, nullptr, (uint32_t)n_cols, (uint32_t)k_max, s->stream));
+    if (!f.tail_fn) {      // (the first call with this source: stages A and B are compiled around it)
+        hipDeviceProp_t prop;
+        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
+        std::vector<char> code;
+        const std::string why = bpm::compile_pointwise_tail(f.src, f.w, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
+        if (!why.empty()) return fail(who + ": " + why);
+        Module mod;
+        HIPCK(mod.load(code));
+        hipFunction_t a = mod.function("bpm_pointwise_tail"), b = mod.function("bpm_pointwise_tail_final"), c = mod.function("bpm_pointwise_body");
+        if (!a || !b || !c) return fail(who + ": the compiled module lacks a kernel of pointwise_tail.h");
+        f.tail_mod = std::move(mod);
+        f.tail_fn = a; f.tail_final_fn = b; f.body_fn = c;
+        stats[11] = 1;
+    }
+    DevTemp<unsigned int> d_keep, d_cnt, d_bad, d_ncomp, d_nkept, d_nbad;
+    DevTemp<unsigned long long> d_buf, d_keys;
+    DevTemp<double> d_ws, d_cut, d_body, d_out;
+    DevTemp<char> d_sort;
+    CK(d_keep.alloc((size_t)n_data, who.c_str(), "the kept-set sizes"));
+    CK(d_buf.alloc((size_t)(n_wg * A.cap * bpm::PW_THREADS), who.c_str(), "the candidate buffers of " + std::to_string((unsigned long long)n_wg) + " workgroups"));
+    CK(d_cnt.alloc((size_t)(n_wg * bpm::PW_THREADS)));
+    CK(d_bad.alloc((size_t)(n_wg * bpm::PW_THREADS)));
+    CK(d_ncomp.alloc((size_t)n_wg));
+    CK(d_nkept.alloc((size_t)n_cols));
+    CK(d_nbad.alloc((size_t)n_cols));
+    CK(d_keys.alloc((size_t)(2 * n_cols * k_max), who.c_str(), "the kept values of " + std::to_string((unsigned long long)n_cols) + " data (the sort's in and out)"));
+    CK(d_sort.alloc(std::max<size_t>(sort_bytes, 1), who.c_str(), "the sort's temporaries"));
+    CK(d_ws.alloc((size_t)(n_cols * ws_stride), who.c_str(), "the fit's work space"));
+    CK(d_cut.alloc((size_t)n_cols));
+    CK(d_body.alloc((size_t)(3 * P.parts * n_cols), who.c_str(), "the body records of " + std::to_string((unsigned long long)P.parts) + " parts"));
+    CK(d_out.alloc((size_t)bpm::LOO_FIELDS * n_data));
+    // ---- nothing was launched so far ----
+    CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
+    HIPCK(hipMemcpyAsync(d_keep.p, keep_h.data(), (size_t)n_data * sizeof(unsigned int), hipMemcpyHostToDevice, s->stream));
+    HIPCK(hipMemsetAsync(d_out.p, 0, (size_t)bpm::LOO_FIELDS * n_data * sizeof(double), s->stream));
+    unsigned long long* k_in = d_keys.p;
+    unsigned long long* k_out = d_keys.p + (size_t)(n_cols * k_max);
+    std::vector<unsigned int> ncomp_h((size_t)n_wg);
+    std::vector<double> tails_h;
+    unsigned int most = 0;
+    struct Events {      // (destroyed on every way out)
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    for (hipEvent_t& x : ev.e) HIPCK(hipEventCreate(&x));
+    double us[3] = {0.0, 0.0, 0.0};
+    for (uint64_t b = 0; b < A.batches; ++b) {
+        const uint64_t tile0 = b * nbt, nt = std::min<uint64_t>(nbt, P.n_tiles - tile0), cols = nt * bpm::PW_THREADS;
+        const uint64_t i0 = tile0 * bpm::PW_THREADS, n_live = std::min<uint64_t>(cols, n_data - i0);
+        HIPCK(hipEventRecord(ev.e[0], s->stream));
+        HIPCK(ModuleLaunch<bpm::PointwiseTailKernel>::on(s->stream, f.tail_fn, (unsigned)(A.parts * nt), bpm::PW_THREADS, P.lds_bytes + bpm::PT_HIST_BYTES, s->hist, s->ld,
+                                                         (int)s->dim, lo, hi, A.chunk, (unsigned)nt, (unsigned)tile0, f.params.p, f.data.p, (unsigned)n_data, P.R, P.ldp,
+                                                         P.lds_bytes / 8u, d_keep.p, (unsigned)A.cap, d_buf.p, d_cnt.p, d_bad.p, d_ncomp.p));
+        HIPCK(ModuleLaunch<bpm::PointwiseTailFinalKernel>::on(s->stream, f.tail_final_fn, (unsigned)nt, bpm::PW_THREADS, 0, (unsigned)nt, (unsigned)tile0, (unsigned)A.parts,
+                                                              (unsigned)n_data, d_keep.p, (unsigned)A.cap, (unsigned)k_max, d_buf.p, d_cnt.p, d_bad.p, k_in, d_nkept.p,
+                                                              d_nbad.p));
+        size_t t = sort_bytes;      // (the temporaries of a full batch hold those of the last, partial one)
+        HIPCK(rank_sort(d_sort.p, &t, k_in, k_out, (uint32_t)cols, (uint32_t)k_max, s->stream));
+        HIPCK(hipEventRecord(ev.e[1], s->stream));
+        hipLaunchKernelGGL(pw_tail_values_kernel, dim3((unsigned)cols), dim3(bpm::PSIS_THREADS), 0, s->stream, k_out, (uint32_t)k_max, cols, (const uint32_t*)d_nkept.p,
+                           (const uint32_t*)d_nbad.p, d_cut.p);
+        HIPCK(hipGetLastError());
+        const uint64_t n_rec = P.parts * cols;
+        HIPCK(ModuleLaunch<bpm::PointwiseBodyKernel>::on(s->stream, f.body_fn, (unsigned)(P.parts * nt), bpm::PW_THREADS, P.lds_bytes, s->hist, s->ld, (int)s->dim, lo, hi,
+                                                         P.chunk, (unsigned)nt, (unsigned)tile0, f.params.p, f.data.p, (unsigned)n_data, P.R, P.ldp, d_cut.p, d_body.p,
+                                                         n_rec));
+        HIPCK(hipEventRecord(ev.e[2], s->stream));
+        hipLaunchKernelGGL(pw_psis_kernel, dim3((unsigned)n_live), dim3(bpm::PSIS_THREADS), 0, s->stream, (const double*)k_out, (uint32_t)k_max, cols,
+                           (const uint32_t*)d_nkept.p, (const uint32_t*)d_nbad.p, (const double*)d_body.p, (uint32_t)P.parts, d_ws.p, ws_stride, i0, n_data, d_out.p);
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(ev.e[3], s->stream));
+        HIPCK(hipMemcpyAsync(ncomp_h.data(), d_ncomp.p, (size_t)(A.parts * nt) * sizeof(unsigned int), hipMemcpyDeviceToHost, s->stream));
+        if (tails) HIPCK(hipMemcpyAsync(tails + (size_t)(i0 * k_max), k_out, (size_t)(n_live * k_max) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        for (uint64_t q = 0; q < A.parts * nt; ++q) most = std::max(most, ncomp_h[(size_t)q]);
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            HIPCK(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+            us[k] += 1e3 * (double)ms;
+        }
+    }
+    HIPCK(hipMemcpyAsync(records, d_out.p, (size_t)bpm::LOO_FIELDS * n_data * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    stats[1] = (int64_t)k_max; stats[2] = (int64_t)A.parts; stats[3] = (int64_t)A.batches; stats[4] = (int64_t)most; stats[5] = (int64_t)P.parts;
+    stats[6] = (int64_t)P.chunk; stats[7] = (int64_t)budget;
+    for (int k = 0; k < 3; ++k) stats[8 + k] = (int64_t)(us[k] + 0.5);
+    return 0;
 }
 
 // ---- the one batch loop of whatever reads sorted columns: bpm_rank_history's sorted kinds (the consumer scores) and bpm_hdi (it scans) ---

@@ -676,6 +676,49 @@ class HipEngine(object):
         self._ck(self.lib.bpm_pointwise_layout(int(self.dim), int(w), int(n_rows), int(n_data), out))
         return tuple(int(x) for x in out)
 
+    def loo_kept(self, n_rows, r_eff):
+        """-> (n_data,) int64: the size K = min(ceil(min(S / 5, 3 sqrt(S / r_eff))) + 1, S) of each datum's kept set over a window of
+        S = n_rows draws (bpm_loo_kept)"""
+        return np.array([self.lib.bpm_loo_kept(int(n_rows), float(r)) for r in np.atleast_1d(r_eff)], dtype=np.int64)
+
+    def loo_layout(self, n_rows, n_data, k_max, w=1, budget_bytes=1 << 62):
+        """-> (T, R, stage A's row parts, its rows per part, tiles per data batch, data batches, stage B's parts, its rows per part) of
+        bpm_loo over n_rows rows of this engine's dim, n_data data and kept sets of at most k_max values under a scratch budget
+        (bpm_loo_layout; by default no budget to speak of: the layout the rows alone give)"""
+        out = (C.c_int64 * 8)()
+        self._ck(self.lib.bpm_loo_layout(int(self.dim), int(w), int(n_rows), int(n_data), int(k_max), int(budget_bytes), out))
+        return tuple(int(x) for x in out)
+
+    def loo(self, pw, n_burn, r_eff, tails=False):
+        """pointwise.compute_loo's device call: installs `pw`, selects, fits and finishes (set_pointwise + bpm_loo).  r_eff: (n_data,).
+        -> (records (LOO_FIELDS, n_data) float64 -- the count fields to be viewed as int64 --, stats dict, tails: None or a list of each
+        datum's kept values, ascending)"""
+        n_burn = int(n_burn)
+        r = np.ascontiguousarray(r_eff, dtype=np.float64)
+        nd = pw.n_data
+        rows = self.pointwise_window_rows(n_burn) if n_burn >= 0 else 0
+        buf, cap = None, 0
+        if tails and rows:
+            k_max = int(self.loo_kept(rows, r.min()).max())
+            cap = nd * k_max
+            if cap >= 1 << 31:
+                raise ValueError("param_est_loo: the tails of %d data x %d kept values are %d elements; fewer than 2^31 can be returned"
+                                 % (nd, k_max, cap))
+            buf = np.empty(max(cap, 1))
+        self.set_pointwise(pw.source, pw.data, pw.params)
+        rec = np.zeros((L.LOO_FIELDS, nd))
+        stats = (C.c_int64 * 12)()
+        self._ck(self.lib.bpm_loo(self._h, n_burn, _dptr(r), _dptr(rec), None if buf is None else _dptr(buf), cap, stats))
+        names = ("rows", "k_max", "tail_parts", "batches", "compactions", "body_parts", "body_rows_per_part", "budget_bytes", "tail_us", "body_us", "fit_us", "compiled")
+        st = dict(zip(names, (int(x) for x in stats)))
+        out = None
+        if buf is not None:
+            kept = rec[L.LOO_KEPT].view(np.int64)
+            out = [buf[i * st["k_max"]:i * st["k_max"] + int(kept[i])].copy() for i in range(nd)]
+        elif tails:
+            out = [np.empty(0) for _ in range(nd)]
+        return rec, st, out
+
     def _second_engine(self, dim):
         """the destination of derive_history / rank_history: a history-keeping host-callback engine of this one's chains, library and device"""
         return HipEngine(algo=L.ALGO_DEMC, n_chains=self.n_chains, dim=dim, target_id=L.TARGET_HOST_CALLBACK, target_params=None, seed=0,

@@ -29,7 +29,24 @@ parameters are to be compared.
 What is not finite follows NumPy / SciPy per datum and never crosses to another datum: some l_is = -inf leave lppd_i finite (p_waic_i is
 NaN and mean_i -inf, as np.var and np.mean say); all -inf give lppd_i = -inf; any +inf gives +inf; any NaN gives NaN in lppd_i, p_waic_i and
 mean_i.  The totals are plain np.sum of the per-datum arrays.  n_high_var counts the data with p_waic_i > 0.4, the condition under which
-ArviZ warns that WAIC is unreliable (PSIS-LOO, which it recommends then, is not provided).
+ArviZ warns that WAIC is unreliable and recommends PSIS-LOO: param_est_loo below.
+
+PSIS-LOO (Vehtari, Simpson, Gelman, Yao and Gabry, "Pareto smoothed importance sampling"; Vehtari, Gelman and Gabry 2017; what ArviZ's `loo`
+reports).  Leaving datum i out re-weights draw s by exp(-l_is); the largest of those ratios are replaced by quantiles of a generalised Pareto
+distribution fitted to them, whose shape pareto_k says whether the estimate can be trusted (k > 0.7: it cannot -- the datum is an outlier or
+has leverage).  Per datum, over the S draws of the window:
+
+    M = ceil(min(S / 5, 3 sqrt(S / r_eff_i)));  the kept set: the K = min(M + 1, S) smallest l;  the cutoff c: its largest;  the tail: the kept
+    values < c (ties with the cutoff belong to the body, so tail_len <= M);  tail_len <= 4: pareto_k = +inf, nothing is smoothed;  else the
+    fit of Zhang and Stephens with ArviZ's prior, and if k is finite the tail's log weights become log(gpinv((j - 0.5) / n, k, sigma) +
+    exp(-c - x_max)), truncated at 0;  elpd_loo_i = logsumexp(l + lw) - logsumexp(lw).
+
+    loo = sampler.param_est_loo(pw, n_burn=N * 500)        # -> PosteriorLoo; str(loo) is a short table
+    elpd_diff, se_diff = compare_loo(loo_a, loo_b)
+
+Nothing of size S x n_data exists anywhere: a thread per datum selects its kept set exactly while the rows stream by (csrc/pointwise_tail.h),
+a second pass takes the log-sum-exp of the rest, and a workgroup per datum fits and finishes (csrc/psis.h).  A datum with a value that is not
+finite gets NaN in pareto_k, elpd_loo_i and p_loo_i and tail_len 0; its lppd_i and the counters are param_est_waic's.  Single rank only.
 
 This module validates, merges the ranks in rank order -- the log-sum-exp by M = max(m_a, m_b), s = s_a exp(m_a - M) + s_b exp(m_b - M), the
 moments by traces.merge_moments, the formulas of the device's own fold -- and finishes.  Every rank runs the same arithmetic on the same
@@ -48,6 +65,8 @@ from .derived import rank_rows
 from .traces import finish, merge_moments
 
 WHO = "param_est_waic"
+WHO_LOO = "param_est_loo"
+BAD_K = 0.7
 MAX_DATA_W = 64
 HIGH_VAR = 0.4
 SIGNATURE = "__device__ double ln_like_point(const double* x, int d, const double* y, int i, const double* p)"
@@ -208,3 +227,93 @@ def compare_waic(a, b):
     with np.errstate(invalid="ignore"):
         diff = a.elpd_i - b.elpd_i
         return float(a.elpd_waic - b.elpd_waic), float(np.sqrt(len(diff) * np.var(diff)))
+
+
+class PosteriorLoo(collections.namedtuple("PosteriorLoo", [
+        "elpd_loo_i", "pareto_k", "lppd_i", "p_loo_i", "tail_len", "n_nan", "n_neg_inf", "n_pos_inf", "elpd_loo", "p_loo", "lppd", "se", "looic",
+        "n_bad_k", "n", "tails", "stats"])):
+    """Per datum, (n_data,): elpd_loo_i = logsumexp_s(l_is + lw_is) - logsumexp_s(lw_is) with lw the Pareto smoothed log weights; pareto_k:
+    the fitted shape (+inf: a tail of 4 or fewer draws, nothing smoothed); lppd_i: param_est_waic's, the same bits; p_loo_i = lppd_i -
+    elpd_loo_i; tail_len int64: how many draws were smoothed; n_nan, n_neg_inf, n_pos_inf int64.  Totals: elpd_loo, p_loo, lppd = np.sum of
+    those arrays; se = sqrt(n_data * np.var(elpd_loo_i)); looic = -2 elpd_loo; n_bad_k = how many pareto_k exceed 0.7; n: rows of the window;
+    tails: None, or a list of each datum's kept values (its K smallest l), ascending; stats: what the device call says about its launch
+    (k_max, stage A's row parts, data batches, the most compactions of a workgroup, stage B's parts and rows per part, the scratch budget, the
+    device's microseconds in the three stages: tail_us, body_us, fit_us) and,
+    per datum, body_n, body_m, body_s: the rows outside the tail and the log-sum-exp body_m + log(body_s) of their -l"""
+    __slots__ = ()
+
+    def __str__(self):
+        bad = [("NaN", self.n_nan), ("-inf", self.n_neg_inf), ("+inf", self.n_pos_inf)]
+        rows = [("elpd_loo", "%.6g" % self.elpd_loo), ("se", "%.6g" % self.se), ("p_loo", "%.6g" % self.p_loo), ("lppd", "%.6g" % self.lppd),
+                ("looic", "%.6g" % self.looic), ("n (draws)", "%d" % self.n), ("n_data", "%d" % len(self.lppd_i)),
+                ("data with pareto_k > %.1f" % BAD_K, "%d" % self.n_bad_k)]
+        worst = [int(i) for i in np.argsort(-np.nan_to_num(self.pareto_k, nan=-np.inf, posinf=np.inf)) if self.pareto_k[i] > BAD_K][:5]
+        if worst:
+            rows.append(("  the largest: datum (pareto_k)", ", ".join("%d (%.3g)" % (i, self.pareto_k[i]) for i in worst)))
+        rows += [("data with a %s value" % name, "%d" % int(np.count_nonzero(c))) for name, c in bad]
+        width = max(len(k) for k, _ in rows)
+        return "\n".join("%-*s  %s" % (width, k, v) for k, v in rows)
+
+
+def check_r_eff(who, r_eff, n_data):
+    """-> (n_data,) float64: r_eff, a scalar or one value per datum, finite and > 0"""
+    r = np.asarray(r_eff, dtype=np.float64)
+    if r.ndim == 0:
+        r = np.full(n_data, float(r))
+    if r.shape != (n_data,):
+        raise ValueError("%s: r_eff must be a scalar or have shape (%d,) (got %r)" % (who, n_data, r.shape))
+    if not (np.isfinite(r).all() and (r > 0).all()):
+        raise ValueError("%s: r_eff must be finite and > 0" % who)
+    return np.ascontiguousarray(r)
+
+
+def finish_loo(waic, rec, stats, tails):
+    """waic: the PosteriorWaic of the window (lppd_i and the counters); rec (LOO_FIELDS, n_data): bpm_loo's records -> PosteriorLoo"""
+    from . import _lib as L
+    bad = (waic.n_nan + waic.n_neg_inf + waic.n_pos_inf) > 0
+    elpd_i = np.where(bad, np.nan, rec[L.LOO_ELPD])
+    k = np.where(bad, np.nan, rec[L.LOO_K])
+    tail_len = np.where(bad, 0, np.ascontiguousarray(rec[L.LOO_TAIL_LEN]).view(np.int64))
+    lppd_i = waic.lppd_i
+    with np.errstate(invalid="ignore"):
+        p_i = lppd_i - elpd_i
+        elpd, p_loo, lppd = np.sum(elpd_i), np.sum(p_i), np.sum(lppd_i)
+        se = np.sqrt(len(elpd_i) * np.var(elpd_i))
+        n_bad = int(np.count_nonzero(k > BAD_K))
+    st = dict(stats)
+    st["body_n"] = np.ascontiguousarray(rec[L.LOO_BODY_N]).view(np.int64).copy()
+    st["body_m"], st["body_s"], st["sigma"] = rec[L.LOO_BODY_M].copy(), rec[L.LOO_BODY_S].copy(), rec[L.LOO_SIGMA].copy()
+    return PosteriorLoo(elpd_i, k, lppd_i, p_i, tail_len, waic.n_nan, waic.n_neg_inf, waic.n_pos_inf, float(elpd), float(p_loo), float(lppd),
+                        float(se), float(-2.0 * elpd), n_bad, int(waic.n), tails, st)
+
+
+def compute_loo(eng, allgather, pw, n_burn, n_chains, r_eff=1.0, tails=False):
+    """The driver of param_est_loo on one rank: eng.pointwise gives lppd_i and the counters exactly as param_est_waic has them, eng.loo the
+    rest.  -> PosteriorLoo"""
+    if not isinstance(pw, HipPointwise):
+        raise TypeError("%s: pw must be a HipPointwise (got %s)" % (WHO_LOO, type(pw).__name__))
+    from .rank_diagnostics import check_single_rank
+    check_single_rank(WHO_LOO, len(allgather(None)))
+    n_burn = check_n_burn(WHO_LOO, n_burn)
+    r = check_r_eff(WHO_LOO, r_eff, pw.n_data)
+    if eng.pointwise_window_rows(n_burn) == 0:
+        raise empty_window(WHO_LOO, n_burn)
+    rec, stats, tl = eng.loo(pw, n_burn, r, tails=bool(tails))       # (refuses a kept set beyond the budget before it compiles or allocates)
+    waic = compute(eng.pointwise, allgather, pw, n_burn, n_chains, eng.history_rows())
+    return finish_loo(waic, rec, stats, tl)
+
+
+def compare_loo(a, b):
+    """-> (elpd_diff, se_diff) of two PosteriorLoo over the same data and as many draws: elpd_diff = a.elpd_loo - b.elpd_loo (positive: a
+    predicts better), se_diff = sqrt(n_data * np.var(a.elpd_loo_i - b.elpd_loo_i)) (Vehtari, Gelman and Gabry 2017, eq. 24).  Host
+    arithmetic only."""
+    for x in (a, b):
+        if not isinstance(x, PosteriorLoo):
+            raise TypeError("compare_loo: both arguments must be PosteriorLoo (got %s)" % type(x).__name__)
+    if len(a.elpd_loo_i) != len(b.elpd_loo_i):
+        raise ValueError("compare_loo: the results are over %d and %d data points; both must be over the same data" % (len(a.elpd_loo_i), len(b.elpd_loo_i)))
+    if a.n != b.n or a.n <= 0:
+        raise ValueError("compare_loo: the results are over %d and %d draws; both must be over the same number, more than 0" % (a.n, b.n))
+    with np.errstate(invalid="ignore"):
+        diff = a.elpd_loo_i - b.elpd_loo_i
+        return float(a.elpd_loo - b.elpd_loo), float(np.sqrt(len(diff) * np.var(diff)))

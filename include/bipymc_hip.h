@@ -467,6 +467,29 @@ int bpm_set_pointwise(bpm_handle_t h, const char* hip_source, const double* para
                       int32_t* reused);
 int bpm_pointwise(bpm_handle_t h, int64_t n_burn, double* records, int64_t* n_rows, int64_t* n_first, double* values, int64_t values_cap);
 int bpm_pointwise_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t* out);
+/* PSIS-LOO PER DATUM (Vehtari, Simpson, Gelman, Yao and Gabry; Vehtari, Gelman and Gabry 2017) of the installed pointwise function, single rank.
+ * With S the rows of the window and l the S values of a datum: M = ceil(min(S / 5, 3 sqrt(S / r_eff))), the kept set is the K = min(M + 1, S)
+ * smallest l (bpm_loo_kept: K, or -1 for a bad argument), the cutoff c its largest, the tail the kept values < c.  Three stages per batch of
+ * data (bipymc_amd/csrc/pointwise_tail.h, psis.h): A, compiled around the caller's source at the first call, selects every datum's kept set
+ * exactly while the rows stream by (candidate columns in global scratch, a radix select when one fills); the library's segmented sort orders
+ * it; B streams once more for the log-sum-exp of -l over the rows with l >= c, on bpm_pointwise_layout's fixed layout; C fits the generalised
+ * Pareto distribution (Zhang and Stephens), smooths the tail and finishes, a workgroup per datum, every sum in a fixed order.
+ * bpm_loo: r_eff[n_data] (finite, > 0); records = [8][n_data], field f of datum i at records[f * n_data + i]: 0 elpd_loo_i | 1 pareto_k (+inf
+ * for a tail of 4 or fewer) | 2 sigma | 3 tail_len | 4 the kept values | 5 the body's rows (64-bit words) | 6, 7 (m, s): the body's
+ * log-sum-exp of -l is m + log s.  A datum with a value that is not finite has NaN in 0, 1, 2 and 0 in 3.  tails (may be NULL):
+ * tails[i * k_max + j], j < kept, ascending, at most tails_cap doubles, k_max = stats[1].  stats[12]: rows | k_max | stage A's row parts | data
+ * batches | the most compactions one workgroup of stage A made | stage B's parts | its rows per part | the scratch budget in bytes | the
+ * microseconds stages A (with the merge and the sort), B and C took on the device, summed over the batches | 1 if this call compiled the
+ * module of stages A and B, 0 if the handle had kept it.
+ * Selection is exact, so stage A's layout may depend on the budget: BPM_LOO_SCRATCH_MB, by default a quarter of the free device memory (read
+ * at every call); the bits of every result do not depend on it.  bpm_loo_layout: out[8] = T | R | stage A's parts | its rows per part | tiles
+ * per data batch | batches | stage B's parts | its rows per part for kept sets of k_max under a budget of budget_bytes.
+ * Errors: what bpm_pointwise refuses, more than one rank, an r_eff that is not finite and > 0, tails beyond tails_cap, and kept sets of which
+ * not even one tile of data fits the budget (refused before bpm_loo compiles or allocates anything -- the function bpm_set_pointwise
+ * installed stays --; the message names the requirement), or whose one tile exceeds the sort's 2^31 keys. */
+int64_t bpm_loo_kept(int64_t n_rows, double r_eff);
+int bpm_loo_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t k_max, int64_t budget_bytes, int64_t* out);
+int bpm_loo(bpm_handle_t h, int64_t n_burn, const double* r_eff, double* records, double* tails, int64_t tails_cap, int64_t* stats);
 /* A DERIVED HISTORY IS A HISTORY: the installed function of `src` (bpm_set_device_function) over EVERY resident row of src, written into the
  * history of `dst` -- a second, ordinary handle made by bpm_create with the host-callback target, keep_history = 1, dim = n_out and src's
  * n_chains -- so that every statistic above (bpm_reduce_moments, bpm_diag_*, bpm_quantile_*, bpm_reduce_cov, bpm_hist_*, bpm_trace_*, bpm_derive
