@@ -183,7 +183,7 @@ def load():
 
 # The files a library's build id is the SHA-256 of, in this order (bipymc_amd/csrc/Makefile: ID_SRCS)
 _ID_SRCS = ("csrc/sampler.hip", "csrc/kernels.h", "csrc/accept_test.h", "csrc/kernels_wide.h", "csrc/diagnostics.h", "csrc/quantiles.h", "csrc/covariance.h", "csrc/histograms.h", "csrc/traces.h", "csrc/ranks.h", "csrc/trace_acc.h", "csrc/philox.h", "csrc/rocrand_check.h", "csrc/accept_check.h", "csrc/aql_queue.h", "csrc/rtc.h", "csrc/device_memory.h", "csrc/user_likelihood.h", "csrc/derived.h",
-            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_eval_data.h", "csrc/user_target.h", "csrc/derive_rows.h", "csrc/pointwise.h", "csrc/pointwise_rows.h", "csrc/pointwise_tail.h", "csrc/psis.h",
+            "csrc/user_ln_like.h", "csrc/user_eval.h", "csrc/user_eval_data.h", "csrc/user_target.h", "csrc/derive_rows.h", "csrc/pointwise.h", "csrc/pointwise_datum.h", "csrc/pointwise_rows.h", "csrc/pointwise_tail.h", "csrc/psis.h",
             "../include/bipymc_hip.h", "../include/bipymc_hip_test.h", "csrc/Makefile")
 
 
@@ -255,6 +255,15 @@ def device_count():
     n = C.c_int32(0)
     check(load().bpm_device_count(C.byref(n)))
     return int(n.value)
+
+
+def check_source(entry, *args, arch=None):
+    """Compile only (no GPU needed), behind the check() of HipLikelihood, HipFunction and HipPointwise: entry(*args, arch, log, len(log)) of the
+    library (bpm_check_*) -> True; raises ValueError with the compiler's log when the source does not build for `arch` (default gfx950)."""
+    log = C.create_string_buffer(1 << 16)
+    if getattr(load(), entry)(*(args + (arch.encode() if arch else None, log, len(log)))) != 0:
+        raise ValueError(log.value.decode(errors="replace"))
+    return True
 
 
 def check(rc, lib=None):

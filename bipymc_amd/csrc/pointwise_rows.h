@@ -49,12 +49,7 @@ BPM_PW_HD void pw_merge_lse(unsigned long long n_a, double& m, double& s, unsign
 }
 
 #ifdef BPM_POINTWISE_W
-#if BPM_POINTWISE_W < 1 || BPM_POINTWISE_W > 64
-#error "BPM_POINTWISE_W (doubles per datum) must be 1 ... 64"
-#endif
-#define BPM_PW_W_REGS 8
-#define BPM_STAGE_ROWS_ONLY
-#include "derive_rows.h"      // the fixed-width typedefs, trace_acc.h, bpm_stage_rows
+#include "pointwise_datum.h"      // the opening of the pointwise kernels; through derive_rows.h the fixed-width typedefs, trace_acc.h, bpm_stage_rows
 
 extern "C" __global__ void __launch_bounds__(256) bpm_pointwise_rows(const double* H, unsigned int ld, int d, unsigned long long lo, unsigned long long hi,
                                                                      unsigned long long chunk, unsigned int n_tiles, const double* params, const double* data,
@@ -62,40 +57,21 @@ extern "C" __global__ void __launch_bounds__(256) bpm_pointwise_rows(const doubl
                                                                      unsigned long long n_rec, double* values) {
     using namespace bpm;
     extern __shared__ __attribute__((aligned(16))) double bpm_lds[];
-    const unsigned int tid = threadIdx.x, tile = blockIdx.x % n_tiles, part = blockIdx.x / n_tiles;
-    const unsigned long long i = (unsigned long long)tile * 256ull + tid;
-    const bool live = i < n_data;
-    unsigned long long r0 = lo + (unsigned long long)part * chunk;
-    r0 = r0 < hi ? r0 : hi;
-    const unsigned long long r1 = r0 + chunk < hi ? r0 + chunk : hi;
-#if BPM_POINTWISE_W <= BPM_PW_W_REGS
-    double yv[BPM_POINTWISE_W];
-#pragma unroll
-    for (int k = 0; k < BPM_POINTWISE_W; ++k) yv[k] = live ? data[i * BPM_POINTWISE_W + k] : 0.0;
-    const double* y = yv;
-#else
-    const double* y = data + (live ? i : 0ull) * BPM_POINTWISE_W;
-#endif
+    BPM_PW_OPEN(0u)
     TrAcc acc;
     tr_init(acc);
     double m = acc.mx, s = 0.0;      // (-inf, 0: nothing yet)
     unsigned int n_pinf = 0u, n_ninf = 0u;
     for (unsigned long long t0 = r0; t0 < r1; t0 += R) {
-        const unsigned int nr = (unsigned int)(r1 - t0 < R ? r1 - t0 : R);
-        if (ldp != 0u) {
-            __syncthreads();      // (the previous tile has been read by every thread)
-            bpm_stage_rows(bpm_lds, H, ld, d, t0, nr, ldp);
-            __syncthreads();
-        }
+        const unsigned int nr = bpm_pw_stage_tile(bpm_lds, H, ld, d, t0, r1, R, ldp);
         if (!live) continue;
         for (unsigned int r = 0; r < nr; ++r) {
             const double* x = ldp != 0u ? bpm_lds + r * ldp : H + (t0 + r) * ld;
             const double l = ln_like_point(x, d, y, (int)i, params);
             const bool first = acc.n == 0u;
             if (tr_add(acc, l)) {
-                if (first) { m = l; s = 1.0; }
-                else if (l > m) { s = s * exp(m - l) + 1.0; m = l; }
-                else s += exp(l - m);
+                const BpmPwLse ms = bpm_pw_lse_add(first, m, s, l);
+                m = ms.m; s = ms.s;
             } else if (l == l) {
                 if (l > 0.0) ++n_pinf; else ++n_ninf;
             }

@@ -31,14 +31,9 @@
 #ifndef BPM_POINTWISE_W
 #error "pointwise_tail.h is compiled around a caller's ln_like_point (BPM_POINTWISE_W: doubles per datum)"
 #endif
-#if BPM_POINTWISE_W < 1 || BPM_POINTWISE_W > 64
-#error "BPM_POINTWISE_W (doubles per datum) must be 1 ... 64"
-#endif
-#define BPM_PT_W_REGS 8
 #define BPM_PT_HIST_WORDS 4096      // 16 counters x 256 lanes
 #define BPM_PT_UNROLL 8u
-#define BPM_STAGE_ROWS_ONLY
-#include "derive_rows.h"      // the fixed-width typedefs, bpm_stage_rows
+#include "pointwise_datum.h"      // the opening of the pointwise kernels; through derive_rows.h the fixed-width typedefs, bpm_stage_rows
 
 __device__ __forceinline__ unsigned long long bpm_pt_key(double v) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
@@ -129,20 +124,7 @@ extern "C" __global__ void __launch_bounds__(256) bpm_pointwise_tail(const doubl
                                                                      unsigned int* compactions) {
     extern __shared__ __attribute__((aligned(16))) double bpm_lds[];
     unsigned int* const hist = reinterpret_cast<unsigned int*>(bpm_lds + lds_rows) + threadIdx.x;
-    const unsigned int tid = threadIdx.x, tile = blockIdx.x % n_tiles, part = blockIdx.x / n_tiles;
-    const unsigned long long i = ((unsigned long long)tile0 + tile) * 256ull + tid;
-    const bool live = i < n_data;
-    unsigned long long r0 = lo + (unsigned long long)part * chunk;
-    r0 = r0 < hi ? r0 : hi;
-    const unsigned long long r1 = r0 + chunk < hi ? r0 + chunk : hi;
-#if BPM_POINTWISE_W <= BPM_PT_W_REGS
-    double yv[BPM_POINTWISE_W];
-#pragma unroll
-    for (int k = 0; k < BPM_POINTWISE_W; ++k) yv[k] = live ? data[i * BPM_POINTWISE_W + k] : 0.0;
-    const double* y = yv;
-#else
-    const double* y = data + (live ? i : 0ull) * BPM_POINTWISE_W;
-#endif
+    BPM_PW_OPEN(tile0)
     BpmPtLane a;
     a.col = buf + (unsigned long long)blockIdx.x * cap * 256ull + tid;
     a.cnt = 0u;
@@ -150,12 +132,7 @@ extern "C" __global__ void __launch_bounds__(256) bpm_pointwise_tail(const doubl
     a.thr = ~0ull;
     unsigned int n_bad = 0u, n_compact = 0u;
     for (unsigned long long t0 = r0; t0 < r1; t0 += R) {
-        const unsigned int nr = (unsigned int)(r1 - t0 < R ? r1 - t0 : R);
-        if (ldp != 0u) {
-            __syncthreads();      // (the previous tile has been read by every thread)
-            bpm_stage_rows(bpm_lds, H, ld, d, t0, nr, ldp);
-            __syncthreads();
-        }
+        const unsigned int nr = bpm_pw_stage_tile(bpm_lds, H, ld, d, t0, r1, R, ldp);
         for (unsigned int r = 0; r < nr; ++r) {      // (every thread, live or not: the step below holds a barrier)
             double l = 0.0;
             bool fin = false;
@@ -222,40 +199,22 @@ extern "C" __global__ void __launch_bounds__(256) bpm_pointwise_body(const doubl
                                                                      const double* data, unsigned int n_data, unsigned int R, unsigned int ldp,
                                                                      const double* cut, double* rec, unsigned long long n_rec) {
     extern __shared__ __attribute__((aligned(16))) double bpm_lds[];
-    const unsigned int tid = threadIdx.x, tile = blockIdx.x % n_tiles, part = blockIdx.x / n_tiles;
-    const unsigned long long i = ((unsigned long long)tile0 + tile) * 256ull + tid;
-    const bool live = i < n_data;
-    unsigned long long r0 = lo + (unsigned long long)part * chunk;
-    r0 = r0 < hi ? r0 : hi;
-    const unsigned long long r1 = r0 + chunk < hi ? r0 + chunk : hi;
-#if BPM_POINTWISE_W <= BPM_PT_W_REGS
-    double yv[BPM_POINTWISE_W];
-#pragma unroll
-    for (int k = 0; k < BPM_POINTWISE_W; ++k) yv[k] = live ? data[i * BPM_POINTWISE_W + k] : 0.0;
-    const double* y = yv;
-#else
-    const double* y = data + (live ? i : 0ull) * BPM_POINTWISE_W;
-#endif
+    BPM_PW_OPEN(tile0)
     const unsigned long long q = (unsigned long long)tile * 256ull + tid, n_cols = (unsigned long long)n_tiles * 256ull;
     const double c = cut[q];
     unsigned long long n = 0ull;
     double m = 0.0, s = 0.0;
     for (unsigned long long t0 = r0; t0 < r1; t0 += R) {
-        const unsigned int nr = (unsigned int)(r1 - t0 < R ? r1 - t0 : R);
-        if (ldp != 0u) {
-            __syncthreads();
-            bpm_stage_rows(bpm_lds, H, ld, d, t0, nr, ldp);
-            __syncthreads();
-        }
+        const unsigned int nr = bpm_pw_stage_tile(bpm_lds, H, ld, d, t0, r1, R, ldp);
         if (!live) continue;
         for (unsigned int r = 0; r < nr; ++r) {
             const double* x = ldp != 0u ? bpm_lds + r * ldp : H + (t0 + r) * ld;
             const double l = ln_like_point(x, d, y, (int)i, params);
             if (!(bpm_pt_finite(l) && l >= c)) continue;
             const double v = -l;
-            if (n == 0ull) { m = v; s = 1.0; }
-            else if (v > m) { s = s * exp(m - v) + 1.0; m = v; }
-            else s += exp(v - m);
+            const bool first = n == 0ull;
+            const BpmPwLse ms = bpm_pw_lse_add(first, m, s, v);
+            m = ms.m; s = ms.s;
             ++n;
         }
     }

@@ -529,6 +529,57 @@ struct DevParams : DevTemp<double> {
         return 0;
     }
 };
+// ---- the one way a caller's source becomes an installed function (the likelihood, the derived function, the pointwise density, PSIS-LOO's stages) ----
+// the arch a run-time program is compiled for: the device's own
+static int device_arch(int device, std::string& arch) {
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    arch = prop.gcnArchName;
+    return 0;
+}
+// What a compile_* wrapper returned (`why`: "" or the reason, `code`) loaded into `mod` and its kernels looked up by name
+struct KernelSlot { const char* name; hipFunction_t* fn; };
+static int load_kernels(const std::string& who, const std::string& why, const std::vector<char>& code, Module& mod, std::initializer_list<KernelSlot> kernels) {
+    if (!why.empty()) return fail(who + ": " + why);
+    HIPCK(mod.load(code));
+    for (const KernelSlot& k : kernels)
+        if (!(*k.fn = mod.function(k.name))) return fail(who + ": the compiled module has no " + k.name + " kernel");
+    return 0;
+}
+// ... compiled for `device` first: compile(arch, code) -> "" or the reason
+template <class Compile>
+static int compile_and_load(const std::string& who, int device, Compile compile, Module& mod, std::initializer_list<KernelSlot> kernels) {
+    std::string arch;
+    std::vector<char> code;
+    CK(device_arch(device, arch));
+    return load_kernels(who, compile(arch, code), code, mod, kernels);
+}
+// Compile only, no device (bpm_check_*): the reason goes into `log` too.  args_ok(): the check of the entry point's other arguments (0 or its
+// fail()), made after the null source's.
+template <class ArgsOk, class Compile>
+static int check_source(const std::string& who, const char* hip_source, const char* arch, char* log, int64_t log_cap, ArgsOk args_ok, Compile compile) {
+    if (!hip_source) return fail(who + ": null source");
+    CK(args_ok());
+    std::vector<char> code;
+    const std::string why = compile((arch && *arch) ? arch : "gfx950", code);
+    bpm::copy_text(why, log, log_cap);
+    return why.empty() ? 0 : fail(who + ": " + why);
+}
+// THE INSTALL CONTRACT.  The new function is built beside the installed one (build(next): compile_and_load, whatever it owns on the device), its
+// parameters are uploaded and the stream is waited for -- a previous function's launches are done, the caller's arrays are its own again.  Only
+// then, when nothing can fail any more, does it take the installed one's place (retire(installed) first): an error on the way leaves the installed
+// function whole.  same: the installed one was built from this source and shape already -- the parameters only.
+template <class F, class Build, class Retire = void (*)(F&)>
+static int install_function(hipStream_t stream, F& installed, bool same, const double* params, int32_t n_params, Build build, Retire retire = [](F&) {}) {
+    F next;
+    if (!same) CK(build(next));
+    CK(next.params.upload(params, n_params, stream));
+    HIPCK(hipStreamSynchronize(stream));
+    if (same) { installed.params = std::move(next.params); return 0; }
+    retire(installed);
+    installed = std::move(next);
+    return 0;
+}
 // The caller's ln_like_fn as a kernel compiled from HIP source (user_likelihood.h; bpm_set_device_likelihood): bpm_step then drives a host-callback sampler ...
 struct UserLikelihood {
     Module mod;
@@ -1085,6 +1136,56 @@ static int super_chain_window(bpm_sampler* s, int64_t n_burn, uint64_t* lo, uint
     int64_t partial_row = -1;
     super_chain_bounds(s, n_burn, lo, hi, &partial_row);
     if (partial_row >= 0) CK(normalize_history(s, partial_row, partial_row + 1));
+    return 0;
+}
+
+// ---- the one frame of a statistic of an installed function over the window (bpm_derive, bpm_pointwise, bpm_loo) ----------------------------
+// This call's window: this rank's super-chain rows [lo, hi) at or after n_burn
+struct RowWindow { uint64_t lo = 0, hi = 0, rows = 0; };
+// Every refusal that comes before the window, in their order: the handle, the device, a null argument, n_burn, installed() -- 0, or the caller's
+// fail() when nothing is installed -- and the resident history; then the window itself.
+template <class Installed>
+static int open_window(bpm_handle_t s, const std::string& who, bool null_argument, int64_t n_burn, Installed installed, RowWindow& w) {
+    CK(check_handle(s));
+    CK(set_device(s));
+    if (null_argument) return fail(who + ": null argument");
+    if (n_burn < 0) return fail(who + ": n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
+    CK(installed());
+    CK(require_resident_history(s, who.c_str()));
+    CK(super_chain_window(s, n_burn, &w.lo, &w.hi));
+    w.rows = w.hi - w.lo;
+    return 0;
+}
+// The optional `values` return of a window, "<rows> rows x <per_row> <noun>" ...
+static std::string values_shape(const RowWindow& w, uint64_t per_row, const char* noun) {
+    return std::to_string((unsigned long long)w.rows) + " rows x " + std::to_string((unsigned long long)per_row) + " " + noun;
+}
+// ... can be returned, into the caller's values_cap doubles (values == nullptr: not asked for)
+static int check_values(const std::string& who, const double* values, int64_t values_cap, const RowWindow& w, uint64_t per_row, const char* noun) {
+    const std::string n_val = std::to_string((unsigned long long)(w.rows * per_row));
+    if (values && w.rows * per_row >= (1ull << 31))
+        return fail(who + ": the values of " + values_shape(w, per_row, noun) + " are " + n_val + " elements; fewer than 2^31 per rank can be returned");
+    if (values && (values_cap < 0 || (uint64_t)values_cap < w.rows * per_row))
+        return fail(who + ": values holds " + std::to_string((long long)values_cap) + " doubles; the window needs " + n_val);
+    return 0;
+}
+// One launch over the window's rows, brought into chain order first, into records of `fields` x per_row doubles: [part records | folded records] in
+// one buffer (with one part the part records are the folded ones).  launch(part records, n_rec, values on the device or null) fills the part records,
+// fold(part records, folded) enqueues the fold kernel -- only with parts > 1.  The folded records come back in out[fields * per_row], the values in `values`; waits.
+template <class Launch, class Fold>
+static int window_records(bpm_sampler* s, const std::string& who, const RowWindow& w, uint64_t parts, const char* part_noun, size_t fields, uint64_t per_row,
+                          const char* noun, double* values, Launch launch, Fold fold, double* out) {
+    const uint64_t n_rec = parts * per_row, n_val = w.rows * per_row;
+    const size_t o_fold = fields * n_rec;
+    CK(normalize_history(s, (int64_t)(w.lo / s->n_local), s->hist_rows));
+    DevTemp<double> b, v;
+    CK(b.alloc(o_fold + (parts > 1 ? fields * per_row : 0), who.c_str(), "the part records of " + std::to_string((unsigned long long)parts) + " " + part_noun));
+    if (values) CK(v.alloc((size_t)n_val, who.c_str(), "the values of " + values_shape(w, per_row, noun)));
+    HIPCK(launch(b.p, n_rec, v.p));
+    if (parts > 1) { fold((const double*)b.p, b.p + o_fold); HIPCK(hipGetLastError()); }
+    HIPCK(hipMemcpyAsync(out, b.p + (parts > 1 ? o_fold : 0), fields * per_row * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (values) HIPCK(hipMemcpyAsync(values, v.p, (size_t)n_val * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
     return 0;
 }
 
@@ -3852,11 +3953,8 @@ static int run_generations_user(bpm_sampler* s, int64_t n_gens) {
 }
 
 extern "C" int bpm_check_device_likelihood(const char* hip_source, const char* arch, char* log, int64_t log_cap) {
-    if (!hip_source) return fail("bpm_check_device_likelihood: null source");
-    std::vector<char> code;
-    const std::string why = bpm::compile_user_likelihood(hip_source, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
-    bpm::copy_text(why, log, log_cap);
-    return why.empty() ? 0 : fail("bpm_check_device_likelihood: " + why);
+    return check_source("bpm_check_device_likelihood", hip_source, arch, log, log_cap, [] { return 0; }, [&](const char* a, std::vector<char>& code) {
+        return bpm::compile_user_likelihood(hip_source, a, bpm_embedded, N_EMBEDDED, code); });
 }
 
 #ifdef BPM_TEST_HOOKS
@@ -3865,13 +3963,10 @@ static constexpr bool USER_FUSED_HOOKS = true;
 // and shape) compiled with no device in the machine; the reason comes back in `log` like bpm_check_device_likelihood's
 extern "C" int bpm_debug_check_user_fused(const char* hip_source, int32_t algo, int32_t lpc, int32_t dpl, int32_t np, int32_t dim, int32_t hot, const char* arch,
                                           char* log, int64_t log_cap) {
-    if (!hip_source) return fail("bpm_debug_check_user_fused: null source");
-    std::vector<char> code;
     std::string lowered[4];
-    const std::string why = bpm::compile_user_fused(hip_source, "v_user_check", (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED,
-                                                    algo == BPM_ALGO_DREAM ? ALGO_DREAM : ALGO_DEMC, lpc, dpl, np, (uint32_t)dim, USER_FUSED_HOOKS, hot, code, lowered);
-    bpm::copy_text(why, log, log_cap);
-    return why.empty() ? 0 : fail("bpm_debug_check_user_fused: " + why);
+    return check_source("bpm_debug_check_user_fused", hip_source, arch, log, log_cap, [] { return 0; }, [&](const char* a, std::vector<char>& code) {
+        return bpm::compile_user_fused(hip_source, "v_user_check", a, bpm_embedded, N_EMBEDDED, algo == BPM_ALGO_DREAM ? ALGO_DREAM : ALGO_DEMC, lpc, dpl, np,
+                                       (uint32_t)dim, USER_FUSED_HOOKS, hot, code, lowered); });
 }
 #else
 static constexpr bool USER_FUSED_HOOKS = false;
@@ -3925,21 +4020,14 @@ static int install_user_likelihood(bpm_sampler* s, const std::string& who, const
     const bool has_data = bpm::user_source_has_data(hip_source);
     if (!data && has_data) return fail(who + ": the source is in the per-datum form (BPM_LN_LIKE_DATA): give it its data with bpm_set_device_likelihood_data");
     if (data && !has_data) return fail(who + ": the source does not define BPM_LN_LIKE_DATA and BPM_LN_LIKE_DATA_W (the per-datum form: user_eval_data.h)");
-    hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
-    // the new likelihood is built beside the installed one, which stays whole until nothing can fail any more ...
-    std::vector<char> code;
-    const std::string why = bpm::compile_user_likelihood(hip_source, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
-    if (!why.empty()) return fail(who + ": " + why);
-    UserLikelihood next;
-    HIPCK(next.mod.load(code));
-    next.fn = next.mod.function(data ? "bpm_user_eval_data" : "bpm_user_eval");
-    if (!next.fn) return fail(who + ": the compiled module has no " + (data ? "bpm_user_eval_data" : "bpm_user_eval") + " kernel");
-    CK(next.params.upload(params, n_params, s->stream));
-    if (data) {
-        next.fold = next.mod.function("bpm_user_fold_data");
-        const hipFunction_t info = next.mod.function("bpm_user_data_info");
-        if (!next.fold || !info) return fail(who + ": the compiled module has no bpm_user_fold_data kernel");
+    std::string arch;
+    CK(device_arch(s->cfg.device, arch));
+    const auto build = [&](UserLikelihood& next) {
+        std::vector<char> code;
+        const std::string why = bpm::compile_user_likelihood(hip_source, arch, bpm_embedded, N_EMBEDDED, code);
+        if (!data) return load_kernels(who, why, code, next.mod, {{"bpm_user_eval", &next.fn}});
+        hipFunction_t info = nullptr;
+        CK(load_kernels(who, why, code, next.mod, {{"bpm_user_eval_data", &next.fn}, {"bpm_user_fold_data", &next.fold}, {"bpm_user_data_info", &info}}));
         // the program's view of K, w, the chunk and the workgroup must be this call's and this library's
         DevTemp<int> d_info;
         int h_info[4] = {0, 0, 0, 0};
@@ -3962,12 +4050,11 @@ static int install_user_likelihood(bpm_sampler* s, const std::string& who, const
         CK(next.data.alloc((size_t)n_data * (size_t)w, who.c_str(), "the data"));
         HIPCK(hipMemcpyAsync(next.data.p, data, (size_t)n_data * (size_t)w * sizeof(double), hipMemcpyHostToDevice, s->stream));
         if (next.n_chunks > 1) CK(next.part.alloc((size_t)next.batch_rows * (size_t)next.n_chunks * (size_t)K, who.c_str(), "the chunk sums"));
-    }
-    HIPCK(hipStreamSynchronize(s->stream));                      // (a previous likelihood's launches are done, the parameters are in place)
-    // ... and replaces it in one step: the old update kernel leaves with the old likelihood
-    s->like.fused.drop(s->dq);
-    s->like = std::move(next);
-    CK(user_refresh_ll(s));      // (by the kernel of its own; again below by the update kernel's arithmetic once that one is built)
+        return 0;
+    };
+    // (install_function: the installed likelihood stays whole until nothing can fail any more; the old update kernel leaves with it)
+    CK(install_function(s->stream, s->like, false, params, n_params, build, [&](UserLikelihood& old) { old.fused.drop(s->dq); }));
+    CK(user_refresh_ll(s));     // (by the kernel of its own; again below by the update kernel's arithmetic once that one is built)
     if (data) { s->like.why = "the likelihood is summed over its data by kernels of its own (a wavefront per chunk of the data), not inside the update kernel"; return 0; }
     // the faster form.  Whatever goes wrong with it leaves the three-kernel form in place (bpm_get_device_likelihood_info says which is in use
     // and why).  BPM_USER_FUSED=0: not attempted (A/B, tests).
@@ -3975,7 +4062,7 @@ static int install_user_likelihood(bpm_sampler* s, const std::string& who, const
     UserLikelihood::Fused fused;
     s->like.why = !want_fused ? "BPM_USER_FUSED=0"
                   : s->shape.idx == SHAPE_WIDE ? "rows wider than 512 coordinates run on the looped kernel, which has no run-time form"
-                                               : build_user_fused(s, hip_source, prop.gcnArchName, fused);
+                                               : build_user_fused(s, hip_source, arch.c_str(), fused);
     if (!s->like.why.empty()) return 0;
     s->like.fused = std::move(fused);
     return user_refresh_ll(s);      // (again, now by the update kernel's own arithmetic: the per-coordinate form adds in the kernel's reduction order)
@@ -4049,12 +4136,8 @@ static int check_n_out(const char* who, int32_t n_out) {
 }
 
 extern "C" int bpm_check_device_function(const char* hip_source, int32_t n_out, const char* arch, char* log, int64_t log_cap) {
-    if (!hip_source) return fail("bpm_check_device_function: null source");
-    CK(check_n_out("bpm_check_device_function", n_out));
-    std::vector<char> code;
-    const std::string why = bpm::compile_device_function(hip_source, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
-    bpm::copy_text(why, log, log_cap);
-    return why.empty() ? 0 : fail("bpm_check_device_function: " + why);
+    return check_source("bpm_check_device_function", hip_source, arch, log, log_cap, [&] { return check_n_out("bpm_check_device_function", n_out); },
+                        [&](const char* a, std::vector<char>& code) { return bpm::compile_device_function(hip_source, a, bpm_embedded, N_EMBEDDED, code); });
 }
 
 extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, int32_t n_out, const double* params, int32_t n_params) {
@@ -4062,28 +4145,15 @@ extern "C" int bpm_set_device_function(bpm_handle_t s, const char* hip_source, i
     CK(set_device(s));
     if (!hip_source || n_params < 0 || (n_params > 0 && !params)) return fail("bpm_set_device_function: bad argument");
     CK(check_n_out("bpm_set_device_function", n_out));
-    // built beside the installed function, which stays whole until nothing can fail any more; the same source bytes and n_out: the parameters only
-    const bool rebuild = !s->derived.fn || s->derived.n_out != n_out || s->derived.src != hip_source;
-    DerivedFunction next;
-    if (rebuild) {
-        hipDeviceProp_t prop;
-        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
-        std::vector<char> code;
-        const std::string why = bpm::compile_device_function(hip_source, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
-        if (!why.empty()) return fail("bpm_set_device_function: " + why);
-        HIPCK(next.mod.load(code));
-        next.fn = next.mod.function("bpm_derive_rows");
-        if (!next.fn) return fail("bpm_set_device_function: the compiled module has no bpm_derive_rows kernel");
-        next.fill = next.mod.function("bpm_derive_fill");
-        if (!next.fill) return fail("bpm_set_device_function: the compiled module has no bpm_derive_fill kernel");
+    // (install_function) the same source bytes and n_out: the parameters only
+    const bool same = s->derived.fn && s->derived.n_out == n_out && s->derived.src == hip_source;
+    return install_function(s->stream, s->derived, same, params, n_params, [&](DerivedFunction& next) {
+        CK(compile_and_load("bpm_set_device_function", s->cfg.device, [&](const std::string& arch, std::vector<char>& code) {
+            return bpm::compile_device_function(hip_source, arch, bpm_embedded, N_EMBEDDED, code); }, next.mod, {{"bpm_derive_rows", &next.fn}, {"bpm_derive_fill", &next.fill}}));
         next.src = hip_source;
         next.n_out = n_out;
-    }
-    CK(next.params.upload(params, n_params, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                          // (a previous function's launches are done, and `params` is the caller's again)
-    if (rebuild) s->derived = std::move(next);
-    else s->derived.params = std::move(next.params);
-    return 0;
+        return 0;
+    });
 }
 
 // tile and grid of a launch of the installed function's kernels over `rows` rows of s: rows per tile R, the LDS strides, the dynamic LDS, the workgroups
@@ -4101,54 +4171,30 @@ static int derive_launch_shape(const bpm_sampler* s, uint64_t rows, const char* 
 // null): values[r * n_out + m] for the window's local rows r in order, at most values_cap doubles.  Keeps no state; every buffer is temporary.
 extern "C" int bpm_derive(bpm_handle_t s, int64_t n_burn, int64_t* counts, double* sums, int64_t* n_rows, int64_t* n_first, double* values,
                           int64_t values_cap) {
-    CK(check_handle(s));
-    CK(set_device(s));
-    if (!counts || !sums || !n_rows || !n_first) return fail("bpm_derive: null argument");
-    if (n_burn < 0) return fail("bpm_derive: n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
-    if (!s->derived.fn) return fail("bpm_derive: no device function installed (bpm_set_device_function)");
-    CK(require_resident_history(s, "bpm_derive"));
-    uint64_t lo = 0, hi = 0;
-    CK(super_chain_window(s, n_burn, &lo, &hi));
-    const uint64_t rows = hi - lo;
+    const std::string who = "bpm_derive";
+    RowWindow w;
+    CK(open_window(s, who, !counts || !sums || !n_rows || !n_first, n_burn,
+                   [&] { return s->derived.fn ? 0 : fail(who + ": no device function installed (bpm_set_device_function)"); }, w));
     const uint32_t n_out = (uint32_t)s->derived.n_out;
-    *n_rows = (int64_t)rows;
-    *n_first = (int64_t)(rows % s->n_local);
+    *n_rows = (int64_t)w.rows;
+    *n_first = (int64_t)(w.rows % s->n_local);
     std::fill(counts, counts + 2 * (size_t)n_out, (int64_t)0);
     std::fill(sums, sums + 5 * (size_t)n_out, 0.0);
     std::fill(sums + 3 * (size_t)n_out, sums + 4 * (size_t)n_out, HUGE_VAL);
     std::fill(sums + 4 * (size_t)n_out, sums + 5 * (size_t)n_out, -HUGE_VAL);
-    if (rows == 0) return 0;
-    const uint64_t n_val = rows * n_out;
-    if (values) {
-        if (n_val >= (1ull << 31))
-            return fail("bpm_derive: the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string(n_out) + " outputs are " +
-                        std::to_string((unsigned long long)n_val) + " elements; fewer than 2^31 per rank can be returned");
-        if (values_cap < 0 || (uint64_t)values_cap < n_val)
-            return fail("bpm_derive: values holds " + std::to_string((long long)values_cap) + " doubles; the window needs " + std::to_string((unsigned long long)n_val));
-    }
-    CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
+    if (w.rows == 0) return 0;
+    CK(check_values(who, values, values_cap, w, n_out, "outputs"));
     uint32_t R = 0, ldp = 0, ldo = 0, lds = 0;
     uint64_t parts = 1;
-    CK(derive_launch_shape(s, rows, "bpm_derive", R, ldp, ldo, lds, &parts));
-    // [part records | folded records]; with one part the part records are the folded ones
-    const uint64_t n_rec = parts * n_out;
-    const size_t o_fold = (size_t)TR_F_BINS * n_rec;
-    DevTemp<double> b, v;
-    CK(b.alloc(o_fold + (parts > 1 ? (size_t)TR_F_BINS * n_out : 0), "bpm_derive", "the part records of " + std::to_string((unsigned long long)parts) + " workgroups"));
-    if (values) CK(v.alloc((size_t)n_val, "bpm_derive", "the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string(n_out) + " outputs"));
-    HIPCK(ModuleLaunch<bpm::DeriveRowsKernel>::on(s->stream, s->derived.fn, (unsigned)parts, DERIVE_THREADS, lds, s->hist, s->llhist, s->ld, (int)s->dim, lo, hi,
-                                                  s->derived.params.p, n_out, R, ldp, ldo, b.p, n_rec, v.p));
-    const double* rec = b.p;
-    if (parts > 1) {
-        hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((n_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream, (const double*)b.p,
-                           (uint32_t)parts, n_out, (uint64_t)n_out, (uint32_t)TR_F_BINS, b.p + o_fold);
-        HIPCK(hipGetLastError());
-        rec = b.p + o_fold;
-    }
+    CK(derive_launch_shape(s, w.rows, who.c_str(), R, ldp, ldo, lds, &parts));
+    const auto launch = [&](double* rec, uint64_t n_rec, double* v) {
+        return ModuleLaunch<bpm::DeriveRowsKernel>::on(s->stream, s->derived.fn, (unsigned)parts, DERIVE_THREADS, lds, s->hist, s->llhist, s->ld, (int)s->dim, w.lo, w.hi,
+                                                       s->derived.params.p, n_out, R, ldp, ldo, rec, n_rec, v); };
+    const auto fold = [&](const double* rec, double* folded) {
+        hipLaunchKernelGGL(tr_fold_kernel, dim3((unsigned)((n_out + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, s->stream, rec, (uint32_t)parts, n_out,
+                           (uint64_t)n_out, (uint32_t)TR_F_BINS, folded); };
     std::vector<double> h((size_t)TR_F_BINS * n_out);
-    HIPCK(hipMemcpyAsync(h.data(), rec, h.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (values) HIPCK(hipMemcpyAsync(values, v.p, (size_t)n_val * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
+    CK(window_records(s, who, w, parts, "workgroups", TR_F_BINS, n_out, "outputs", values, launch, fold, h.data()));
     const int count_f[2] = {TR_N, TR_NAN}, sum_f[5] = {TR_C, TR_S1, TR_S2, TR_MIN, TR_MAX};
     for (uint32_t m = 0; m < n_out; ++m) {
         for (int f = 0; f < 2; ++f) std::memcpy(&counts[(size_t)f * n_out + m], &h[(size_t)count_f[f] * n_out + m], 8);
@@ -4166,12 +4212,8 @@ static int check_pointwise_w(const char* who, int32_t w) {
 }
 
 extern "C" int bpm_check_pointwise(const char* hip_source, int32_t w, const char* arch, char* log, int64_t log_cap) {
-    if (!hip_source) return fail("bpm_check_pointwise: null source");
-    CK(check_pointwise_w("bpm_check_pointwise", w));
-    std::vector<char> code;
-    const std::string why = bpm::compile_pointwise(hip_source, w, (arch && *arch) ? arch : "gfx950", bpm_embedded, N_EMBEDDED, code);
-    bpm::copy_text(why, log, log_cap);
-    return why.empty() ? 0 : fail("bpm_check_pointwise: " + why);
+    return check_source("bpm_check_pointwise", hip_source, arch, log, log_cap, [&] { return check_pointwise_w("bpm_check_pointwise", w); },
+                        [&](const char* a, std::vector<char>& code) { return bpm::compile_pointwise(hip_source, w, a, bpm_embedded, N_EMBEDDED, code); });
 }
 
 extern "C" int bpm_set_pointwise(bpm_handle_t s, const char* hip_source, const double* params, int32_t n_params, const double* data, int64_t n_data, int32_t w,
@@ -4182,32 +4224,21 @@ extern "C" int bpm_set_pointwise(bpm_handle_t s, const char* hip_source, const d
     CK(check_pointwise_w("bpm_set_pointwise", w));
     if (!data || n_data < 1 || n_data > (int64_t)0x7fffffff) return fail("bpm_set_pointwise: data must be (n_data, w) with 1 <= n_data < 2^31");
     const size_t n_val = (size_t)n_data * (size_t)w;
-    // built beside the installed function, which stays whole until nothing can fail any more; the same source bytes, w and data: the parameters only
-    PointwiseFunction& cur = s->pointwise;
-    const bool rebuild = !cur.fn || cur.w != w || cur.n_data != n_data || cur.src != hip_source || std::memcmp(cur.data_h.data(), data, n_val * sizeof(double)) != 0;
-    if (reused) *reused = rebuild ? 0 : 1;
-    PointwiseFunction next;
-    if (rebuild) {
-        hipDeviceProp_t prop;
-        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
-        std::vector<char> code;
-        const std::string why = bpm::compile_pointwise(hip_source, w, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
-        if (!why.empty()) return fail("bpm_set_pointwise: " + why);
-        HIPCK(next.mod.load(code));
-        next.fn = next.mod.function("bpm_pointwise_rows");
-        if (!next.fn) return fail("bpm_set_pointwise: the compiled module has no bpm_pointwise_rows kernel");
+    // (install_function) the same source bytes, w and data: the parameters only -- and PSIS-LOO's module, which leaves with a rebuild, stays
+    const PointwiseFunction& cur = s->pointwise;
+    const bool same = cur.fn && cur.w == w && cur.n_data == n_data && cur.src == hip_source && std::memcmp(cur.data_h.data(), data, n_val * sizeof(double)) == 0;
+    if (reused) *reused = same ? 1 : 0;
+    return install_function(s->stream, s->pointwise, same, params, n_params, [&](PointwiseFunction& next) {
+        CK(compile_and_load("bpm_set_pointwise", s->cfg.device, [&](const std::string& arch, std::vector<char>& code) {
+            return bpm::compile_pointwise(hip_source, w, arch, bpm_embedded, N_EMBEDDED, code); }, next.mod, {{"bpm_pointwise_rows", &next.fn}}));
         next.src = hip_source;
         next.w = w;
         next.n_data = n_data;
         next.data_h.assign(data, data + n_val);
         CK(next.data.alloc(n_val, "bpm_set_pointwise", "the data"));
         HIPCK(hipMemcpyAsync(next.data.p, data, n_val * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    }
-    CK(next.params.upload(params, n_params, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                          // (a previous function's launches are done; `params` and `data` are the caller's again)
-    if (rebuild) s->pointwise = std::move(next);
-    else s->pointwise.params = std::move(next.params);
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int bpm_pointwise_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_data, int64_t* out) {
@@ -4223,48 +4254,25 @@ extern "C" int bpm_pointwise_layout(int32_t d, int32_t w, int64_t n_rows, int64_
 // partial first generation.  values (may be null): values[r * n_data + i] for the window's local rows r in order, at most values_cap doubles.
 // Keeps no state; every buffer but the function's own data and parameters is temporary.
 extern "C" int bpm_pointwise(bpm_handle_t s, int64_t n_burn, double* records, int64_t* n_rows, int64_t* n_first, double* values, int64_t values_cap) {
-    CK(check_handle(s));
-    CK(set_device(s));
-    if (!records || !n_rows || !n_first) return fail("bpm_pointwise: null argument");
-    if (n_burn < 0) return fail("bpm_pointwise: n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
-    if (!s->pointwise.fn) return fail("bpm_pointwise: no pointwise function installed (bpm_set_pointwise)");
-    CK(require_resident_history(s, "bpm_pointwise"));
-    uint64_t lo = 0, hi = 0;
-    CK(super_chain_window(s, n_burn, &lo, &hi));
-    const uint64_t rows = hi - lo, n_data = (uint64_t)s->pointwise.n_data;
-    *n_rows = (int64_t)rows;
-    *n_first = (int64_t)(rows % s->n_local);
+    const std::string who = "bpm_pointwise";
+    RowWindow w;
+    CK(open_window(s, who, !records || !n_rows || !n_first, n_burn,
+                   [&] { return s->pointwise.fn ? 0 : fail(who + ": no pointwise function installed (bpm_set_pointwise)"); }, w));
+    const PointwiseFunction& f = s->pointwise;
+    const uint64_t n_data = (uint64_t)f.n_data;
+    *n_rows = (int64_t)w.rows;
+    *n_first = (int64_t)(w.rows % s->n_local);
     std::memset(records, 0, (size_t)PW_FIELDS * n_data * sizeof(double));
-    if (rows == 0) return 0;
-    const uint64_t n_val = rows * n_data;
-    if (values) {
-        if (n_val >= (1ull << 31))
-            return fail("bpm_pointwise: the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string((unsigned long long)n_data) +
-                        " data points are " + std::to_string((unsigned long long)n_val) + " elements; fewer than 2^31 per rank can be returned");
-        if (values_cap < 0 || (uint64_t)values_cap < n_val)
-            return fail("bpm_pointwise: values holds " + std::to_string((long long)values_cap) + " doubles; the window needs " + std::to_string((unsigned long long)n_val));
-    }
-    const bpm::PointwiseLayout L = bpm::pointwise_layout(s->dim, rows, n_data);
-    if (L.parts * L.n_tiles >= (1ull << 31)) return fail("bpm_pointwise: window too large");
-    CK(normalize_history(s, (int64_t)(lo / s->n_local), s->hist_rows));
-    // [part records | folded records]; with one part the part records are the folded ones
-    const uint64_t n_rec = L.parts * n_data;
-    const size_t o_fold = (size_t)PW_FIELDS * n_rec;
-    DevTemp<double> b, v;
-    CK(b.alloc(o_fold + (L.parts > 1 ? (size_t)PW_FIELDS * n_data : 0), "bpm_pointwise", "the part records of " + std::to_string((unsigned long long)L.parts) + " parts"));
-    if (values) CK(v.alloc((size_t)n_val, "bpm_pointwise", "the values of " + std::to_string((unsigned long long)rows) + " rows x " + std::to_string((unsigned long long)n_data) + " data points"));
-    HIPCK(ModuleLaunch<bpm::PointwiseRowsKernel>::on(s->stream, s->pointwise.fn, (unsigned)(L.parts * L.n_tiles), PW_THREADS, L.lds_bytes, s->hist, s->ld, (int)s->dim, lo, hi,
-                                                     L.chunk, (unsigned)L.n_tiles, s->pointwise.params.p, s->pointwise.data.p, (unsigned)n_data, L.R, L.ldp, b.p, n_rec, v.p));
-    const double* rec = b.p;
-    if (L.parts > 1) {
-        hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)L.n_tiles), dim3(PW_THREADS), 0, s->stream, (const double*)b.p, (uint32_t)L.parts, n_data, b.p + o_fold);
-        HIPCK(hipGetLastError());
-        rec = b.p + o_fold;
-    }
-    HIPCK(hipMemcpyAsync(records, rec, (size_t)PW_FIELDS * n_data * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    if (values) HIPCK(hipMemcpyAsync(values, v.p, (size_t)n_val * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return 0;
+    if (w.rows == 0) return 0;
+    CK(check_values(who, values, values_cap, w, n_data, "data points"));
+    const bpm::PointwiseLayout L = bpm::pointwise_layout(s->dim, w.rows, n_data);
+    if (L.parts * L.n_tiles >= (1ull << 31)) return fail(who + ": window too large");
+    const auto launch = [&](double* rec, uint64_t n_rec, double* v) {
+        return ModuleLaunch<bpm::PointwiseRowsKernel>::on(s->stream, f.fn, (unsigned)(L.parts * L.n_tiles), PW_THREADS, L.lds_bytes, s->hist, s->ld, (int)s->dim, w.lo, w.hi,
+                                                          L.chunk, (unsigned)L.n_tiles, f.params.p, f.data.p, (unsigned)n_data, L.R, L.ldp, rec, n_rec, v); };
+    const auto fold = [&](const double* rec, double* folded) {
+        hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)L.n_tiles), dim3(PW_THREADS), 0, s->stream, rec, (uint32_t)L.parts, n_data, folded); };
+    return window_records(s, who, w, L.parts, "parts", PW_FIELDS, n_data, "data points", values, launch, fold, records);
 }
 
 // ---- a second handle as the destination of a history built from the first (bpm_derive_history, bpm_rank_history) -------------------------
@@ -4395,17 +4403,12 @@ extern "C" int bpm_loo_layout(int32_t d, int32_t w, int64_t n_rows, int64_t n_da
 // and the plan come before this call compiles or allocates anything (the function installed by bpm_set_pointwise is there already).
 extern "C" int bpm_loo(bpm_handle_t s, int64_t n_burn, const double* r_eff, double* records, double* tails, int64_t tails_cap, int64_t* stats) {
     const std::string who = "bpm_loo";
-    CK(check_handle(s));
-    CK(set_device(s));
-    if (!r_eff || !records || !stats) return fail(who + ": null argument");
-    if (n_burn < 0) return fail(who + ": n_burn must be >= 0 (got " + std::to_string((long long)n_burn) + ")");
-    if (s->world != 1) return fail(who + ": single rank only (world_size " + std::to_string(s->world) + ")");
+    RowWindow w;
+    CK(open_window(s, who, !r_eff || !records || !stats, n_burn, [&] {
+        if (s->world != 1) return fail(who + ": single rank only (world_size " + std::to_string(s->world) + ")");
+        return s->pointwise.fn ? 0 : fail(who + ": no pointwise function installed (bpm_set_pointwise)"); }, w));
     PointwiseFunction& f = s->pointwise;
-    if (!f.fn) return fail(who + ": no pointwise function installed (bpm_set_pointwise)");
-    CK(require_resident_history(s, who.c_str()));
-    uint64_t lo = 0, hi = 0;
-    CK(super_chain_window(s, n_burn, &lo, &hi));
-    const uint64_t rows = hi - lo, n_data = (uint64_t)f.n_data;
+    const uint64_t lo = w.lo, hi = w.hi, rows = w.rows, n_data = (uint64_t)f.n_data;
     std::memset(records, 0, (size_t)bpm::LOO_FIELDS * n_data * sizeof(double));
     std::memset(stats, 0, 12 * sizeof(int64_t));
     stats[0] = (int64_t)rows;
@@ -4432,15 +4435,11 @@ extern "C" int bpm_loo(bpm_handle_t s, int64_t n_burn, const double* r_eff, doub
     size_t sort_bytes = 0;
     HIPCK(rank_sort(nullptr, &sort_bytes, nullptr, nullptr, (uint32_t)n_cols, (uint32_t)k_max, s->stream));
     if (!f.tail_fn) {      // (the first call with this source: stages A and B are compiled around it)
-        hipDeviceProp_t prop;
-        HIPCK(hipGetDeviceProperties(&prop, s->cfg.device));
-        std::vector<char> code;
-        const std::string why = bpm::compile_pointwise_tail(f.src, f.w, prop.gcnArchName, bpm_embedded, N_EMBEDDED, code);
-        if (!why.empty()) return fail(who + ": " + why);
         Module mod;
-        HIPCK(mod.load(code));
-        hipFunction_t a = mod.function("bpm_pointwise_tail"), b = mod.function("bpm_pointwise_tail_final"), c = mod.function("bpm_pointwise_body");
-        if (!a || !b || !c) return fail(who + ": the compiled module lacks a kernel of pointwise_tail.h");
+        hipFunction_t a = nullptr, b = nullptr, c = nullptr;
+        CK(compile_and_load(who, s->cfg.device, [&](const std::string& arch, std::vector<char>& code) {
+            return bpm::compile_pointwise_tail(f.src, f.w, arch, bpm_embedded, N_EMBEDDED, code); }, mod,
+                            {{"bpm_pointwise_tail", &a}, {"bpm_pointwise_tail_final", &b}, {"bpm_pointwise_body", &c}}));
         f.tail_mod = std::move(mod);
         f.tail_fn = a; f.tail_final_fn = b; f.body_fn = c;
         stats[11] = 1;

@@ -33,7 +33,6 @@ statistic of _history_stats.HistoryStatistics over the derived quantities:
 from __future__ import division
 
 import collections
-import ctypes as C
 
 import numpy as np
 
@@ -85,45 +84,55 @@ class HipFunction(object):
 
     def check(self, arch=None):
         """Compile only (no GPU needed): raises ValueError with the compiler's log when the source does not build for `arch` (default gfx950)."""
-        from . import _lib as L
-        lib = L.load()
-        log = C.create_string_buffer(1 << 16)
-        if lib.bpm_check_device_function(self.source.encode(), self.n_out, arch.encode() if arch else None, log, len(log)) != 0:
-            raise ValueError(log.value.decode(errors="replace"))
-        return True
+        from ._lib import check_source
+        return check_source("bpm_check_device_function", self.source.encode(), self.n_out, arch=arch)
 
 
-def rank_rows(rank, n_ranks, n_chains, history_rows, n_rows, n_first):
+def rank_rows(rank, n_ranks, n_chains, history_rows, n_rows, n_first, who=WHO):
     """Super-chain rows (g * n_chains + i) of a rank's window in the rank's own order: n_first rows of a partial first generation (its last
     n_first local chains), then whole generations up to the last one"""
     n_local = n_chains // n_ranks
     whole, rest = divmod(n_rows - n_first, n_local)
     if rest or not 0 <= n_first < n_local or whole + (1 if n_first else 0) > history_rows:
         raise RuntimeError("%s: rank %d reports %d rows, %d of them in a partial generation, for %d local chains and %d generations"
-                           % (WHO, rank, n_rows, n_first, n_local, history_rows))
+                           % (who, rank, n_rows, n_first, n_local, history_rows))
     g0 = history_rows - whole
     head = (g0 - 1) * n_chains + rank * n_local + (n_local - n_first) + np.arange(n_first, dtype=np.int64)
     body = (np.arange(g0, history_rows, dtype=np.int64)[:, None] * n_chains + rank * n_local + np.arange(n_local, dtype=np.int64)[None, :])
     return np.concatenate([head, body.reshape(-1)])
 
 
+def gather_window(who, allgather, part, n_burn, n_chains, history_rows, k, m, values):
+    """The collective frame of a statistic over the window (compute below, pointwise.compute).  part: this rank's (counts (k, m), sums (5, m),
+    n_rows, n_first, values (n_rows, m) or None); allgather(obj) -> [obj of every rank] in rank order ([obj] for one process,
+    single_process_allgather).  -> (counts and sums of every rank, n: the window's rows, which must be the rows >= n_burn of the super chain,
+    values (n, m) in super-chain order or None)"""
+    n_chains, history_rows = int(n_chains), int(history_rows)
+    parts = allgather(part)
+    n = sum(int(p[2]) for p in parts)
+    if n == 0:
+        raise empty_window(who, n_burn)
+    if n != n_chains * history_rows - n_burn:
+        raise RuntimeError("%s: the ranks hold %d rows of the window; rows >= %d of %d generations of %d chains are %d"
+                           % (who, n, n_burn, history_rows, n_chains, n_chains * history_rows - n_burn))
+    vals = None
+    if values:
+        vals = np.empty((n, m))
+        for r, p in enumerate(parts):
+            rows = rank_rows(r, len(parts), n_chains, history_rows, int(p[2]), int(p[3]), who)
+            vals[rows - n_burn] = np.asarray(p[4], dtype=np.float64).reshape(len(rows), m)
+    counts = [np.asarray(p[0], dtype=np.int64).reshape(k, m) for p in parts]
+    sums = [np.asarray(p[1], dtype=np.float64).reshape(5, m) for p in parts]
+    return counts, sums, n, vals
+
+
 def compute(derive, allgather, fn, n_burn, n_chains, history_rows, values=False):
     """The collective driver.  derive(fn, n_burn, values) -> (counts (2, n_out), sums (5, n_out), n_rows, n_first, values (n_rows, n_out) or
-    None) of this rank's rows (HipEngine.derive); allgather(obj) -> [obj of every rank] in rank order ([obj] for one process,
-    single_process_allgather).  -> PosteriorDerived, the same bits on every rank"""
+    None) of this rank's rows (HipEngine.derive).  -> PosteriorDerived, the same bits on every rank"""
     if not isinstance(fn, HipFunction):
         raise TypeError("%s: fn must be a HipFunction (got %s)" % (WHO, type(fn).__name__))
     n_burn = check_n_burn(WHO, n_burn)
-    n_chains, history_rows, m = int(n_chains), int(history_rows), fn.n_out
-    parts = allgather(derive(fn, n_burn, bool(values)))
-    n = sum(int(p[2]) for p in parts)
-    if n == 0:
-        raise empty_window(WHO, n_burn)
-    if n != n_chains * history_rows - n_burn:
-        raise RuntimeError("%s: the ranks hold %d rows of the window; rows >= %d of %d generations of %d chains are %d"
-                           % (WHO, n, n_burn, history_rows, n_chains, n_chains * history_rows - n_burn))
-    counts = [np.asarray(p[0], dtype=np.int64).reshape(2, m) for p in parts]
-    sums = [np.asarray(p[1], dtype=np.float64).reshape(5, m) for p in parts]
+    counts, sums, n, vals = gather_window(WHO, allgather, derive(fn, n_burn, bool(values)), n_burn, n_chains, history_rows, 2, fn.n_out, values)
     n_nan = np.sum([c[1] for c in counts], axis=0)
     mn = np.min([s[3] for s in sums], axis=0)
     mx = np.max([s[4] for s in sums], axis=0)
@@ -131,12 +140,6 @@ def compute(derive, allgather, fn, n_burn, n_chains, history_rows, values=False)
     mean, sd = finish(nf, mean, m2, n_nan, mx == np.inf, mn == -np.inf)
     some = (n - n_nan) > 0
     mn, mx = np.where(some, mn, np.nan), np.where(some, mx, np.nan)
-    vals = None
-    if values:
-        vals = np.empty((n, m))
-        for r, p in enumerate(parts):
-            rows = rank_rows(r, len(parts), n_chains, history_rows, int(p[2]), int(p[3]))
-            vals[rows - n_burn] = np.asarray(p[4], dtype=np.float64).reshape(len(rows), m)
     return PosteriorDerived(mean, sd, mn, mx, n_nan, n, vals)
 
 

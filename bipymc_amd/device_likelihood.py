@@ -14,8 +14,6 @@ construction (hiprtc, about two seconds; include/bipymc_hip.h: bpm_set_device_li
     sampler = DreamMpi(ll, theta_0, n_chains=8192, ...)        # run_mcmc / param_est as ever
 
 `python_fn` (optional): the same function for the host -- `ll(theta)` then works like any ln_like_fn (and the CPU test engine uses it)."""
-import ctypes as C
-
 import numpy as np
 
 
@@ -72,9 +70,5 @@ class HipLikelihood(object):
 
     def check(self, arch=None):
         """Compile only (no GPU needed): raises ValueError with the compiler's log when the source does not build for `arch` (default gfx950)."""
-        from . import _lib as L
-        lib = L.load()
-        log = C.create_string_buffer(1 << 16)
-        if lib.bpm_check_device_likelihood(self.source.encode(), arch.encode() if arch else None, log, len(log)) != 0:
-            raise ValueError(log.value.decode(errors="replace"))
-        return True
+        from ._lib import check_source
+        return check_source("bpm_check_device_likelihood", self.source.encode(), arch=arch)

@@ -590,6 +590,21 @@ class HipEngine(object):
         self._ck(self.lib.bpm_set_device_function(self._h, src, int(n_out), _dptr(p) if p.size else None, int(p.size)))
         self._derive_n_out = int(n_out)
 
+    def window_rows(self, n_burn):
+        """this rank's rows of the window at or after n_burn >= 0 (super_chain_window's count: a partial first generation by chain index)"""
+        G = self.history_rows()
+        g0, first = n_burn // self.n_chains, min(max(n_burn % self.n_chains - self.lo, 0), self.n_local)
+        return max(0, (G - g0) * self.n_local - first) if g0 < G else 0
+
+    def _values_cap(self, who, n_burn, per_row, noun):
+        """-> the elements of the `values` a statistic returns over that window, per_row of them a row (0 for a negative n_burn: the library
+        refuses it); 2^31 or more are refused -- here, before anything is installed or allocated"""
+        rows = self.window_rows(n_burn) if n_burn >= 0 else 0
+        if rows * per_row >= 1 << 31:
+            raise ValueError("%s: the values of %d rows x %d %s are %d elements; fewer than 2^31 per rank can be returned"
+                             % (who, rows, per_row, noun, rows * per_row))
+        return rows * per_row
+
     def derive_rows(self, n_burn, values=False):
         """-> (counts (2, n_out) int64, sums (5, n_out), n_rows, n_first, values (n_rows, n_out) or None): the installed function over this
         rank's super-chain rows >= n_burn -- per output how many values are finite | NaN, and a shift | the shifted sum | the shifted sum of
@@ -600,13 +615,7 @@ class HipEngine(object):
         n_rows = C.c_int64(0); n_first = C.c_int64(0)
         vals, cap = None, 0
         if values and m and n_burn >= 0:
-            # this rank's rows of the window (super_chain_window's count: a partial first generation by chain index)
-            G = self.history_rows()
-            g0, first = n_burn // self.n_chains, min(max(n_burn % self.n_chains - self.lo, 0), self.n_local)
-            cap = max(0, (G - g0) * self.n_local - first) * m if g0 < G else 0
-            if cap >= 1 << 31:
-                raise ValueError("param_est_fn: the values of %d rows x %d outputs are %d elements; fewer than 2^31 per rank can be returned"
-                                 % (cap // m, m, cap))
+            cap = self._values_cap("param_est_fn", n_burn, m, "outputs")
             vals = np.empty(max(cap, 1))
         i64 = C.POINTER(C.c_int64)
         self._ck(self.lib.bpm_derive(self._h, n_burn, counts.ctypes.data_as(i64), _dptr(sums), C.byref(n_rows), C.byref(n_first),
@@ -615,7 +624,10 @@ class HipEngine(object):
         return counts[:, :m], sums[:, :m], n, int(n_first.value), None if vals is None else vals[:n * m].reshape(n, m)
 
     def derive(self, fn, n_burn, values=False):
-        """derived.compute's per-rank call: installs `fn` (a derived.HipFunction) and reduces (set_device_function + derive_rows)"""
+        """derived.compute's per-rank call: installs `fn` (a derived.HipFunction) and reduces (set_device_function + derive_rows).  The
+        values of 2^31 elements or more are refused before anything is installed or allocated."""
+        if values:
+            self._values_cap("param_est_fn", int(n_burn), fn.n_out, "outputs")
         self.set_device_function(fn.source, fn.n_out, fn.params)
         return self.derive_rows(n_burn, values)
 
@@ -632,12 +644,6 @@ class HipEngine(object):
         self._pointwise_n_data = int(y.shape[0])
         return bool(reused.value)
 
-    def pointwise_window_rows(self, n_burn):
-        """this rank's rows of the window (super_chain_window's count: a partial first generation by chain index)"""
-        G = self.history_rows()
-        g0, first = n_burn // self.n_chains, min(max(n_burn % self.n_chains - self.lo, 0), self.n_local)
-        return max(0, (G - g0) * self.n_local - first) if g0 < G else 0
-
     def pointwise_rows(self, n_burn, values=False):
         """-> (counts (4, n_data) int64, sums (5, n_data), n_rows, n_first, values (n_rows, n_data) or None): the installed pointwise
         function over this rank's super-chain rows >= n_burn -- per datum how many values are finite | NaN | +inf | -inf, and of the
@@ -649,7 +655,7 @@ class HipEngine(object):
         n_rows = C.c_int64(0); n_first = C.c_int64(0)
         vals, cap = None, 0
         if values and nd and n_burn >= 0:
-            cap = self.pointwise_window_rows(n_burn) * nd
+            cap = self.window_rows(n_burn) * nd      # (called directly, 2^31 or more are the library's to refuse: pointwise() has refused them)
             vals = np.empty(max(cap, 1))
         self._ck(self.lib.bpm_pointwise(self._h, n_burn, _dptr(rec), C.byref(n_rows), C.byref(n_first), None if vals is None else _dptr(vals), cap))
         n = int(n_rows.value)
@@ -661,11 +667,8 @@ class HipEngine(object):
     def pointwise(self, pw, n_burn, values=False):
         """pointwise.compute's per-rank call: installs `pw` (a pointwise.HipPointwise) and reduces (set_pointwise + pointwise_rows).  The
         values of 2^31 elements or more are refused before anything is installed or allocated."""
-        if values and int(n_burn) >= 0:
-            rows = self.pointwise_window_rows(int(n_burn))
-            if rows * pw.n_data >= 1 << 31:
-                raise ValueError("param_est_waic: the values of %d rows x %d data points are %d elements; fewer than 2^31 per rank can be returned"
-                                 % (rows, pw.n_data, rows * pw.n_data))
+        if values:
+            self._values_cap("param_est_waic", int(n_burn), pw.n_data, "data points")
         self.set_pointwise(pw.source, pw.data, pw.params)
         return self.pointwise_rows(n_burn, values)
 
@@ -696,7 +699,7 @@ class HipEngine(object):
         n_burn = int(n_burn)
         r = np.ascontiguousarray(r_eff, dtype=np.float64)
         nd = pw.n_data
-        rows = self.pointwise_window_rows(n_burn) if n_burn >= 0 else 0
+        rows = self.window_rows(n_burn) if n_burn >= 0 else 0
         buf, cap = None, 0
         if tails and rows:
             k_max = int(self.loo_kept(rows, r.min()).max())

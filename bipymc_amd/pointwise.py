@@ -55,13 +55,12 @@ gathered parts: every rank returns the same bits.
 from __future__ import division
 
 import collections
-import ctypes as C
 
 import numpy as np
 
 from ._history_stats import check_n_burn, empty_window
 from .comm import single_process_allgather  # noqa: F401  (for callers without a communicator)
-from .derived import rank_rows
+from .derived import gather_window
 from .traces import finish, merge_moments
 
 WHO = "param_est_waic"
@@ -130,12 +129,8 @@ class HipPointwise(object):
 
     def check(self, arch=None):
         """Compile only (no GPU needed): raises ValueError with the compiler's log when the source does not build for `arch` (default gfx950)."""
-        from . import _lib as L
-        lib = L.load()
-        log = C.create_string_buffer(1 << 16)
-        if lib.bpm_check_pointwise(self.source.encode(), self.w, arch.encode() if arch else None, log, len(log)) != 0:
-            raise ValueError(log.value.decode(errors="replace"))
-        return True
+        from ._lib import check_source
+        return check_source("bpm_check_pointwise", self.source.encode(), self.w, arch=arch)
 
 
 def merge_lse(parts):
@@ -191,25 +186,10 @@ def compute(pointwise, allgather, pw, n_burn, n_chains, history_rows, values=Fal
     if not isinstance(pw, HipPointwise):
         raise TypeError("%s: pw must be a HipPointwise (got %s)" % (WHO, type(pw).__name__))
     n_burn = check_n_burn(WHO, n_burn)
-    n_chains, history_rows, nd = int(n_chains), int(history_rows), pw.n_data
-    parts = allgather(pointwise(pw, n_burn, bool(values)))
-    n = sum(int(p[2]) for p in parts)
-    if n == 0:
-        raise empty_window(WHO, n_burn)
-    if n != n_chains * history_rows - n_burn:
-        raise RuntimeError("%s: the ranks hold %d rows of the window; rows >= %d of %d generations of %d chains are %d"
-                           % (WHO, n, n_burn, history_rows, n_chains, n_chains * history_rows - n_burn))
-    counts = [np.asarray(p[0], dtype=np.int64).reshape(4, nd) for p in parts]
-    sums = [np.asarray(p[1], dtype=np.float64).reshape(5, nd) for p in parts]
+    counts, sums, n, vals = gather_window(WHO, allgather, pointwise(pw, n_burn, bool(values)), n_burn, n_chains, history_rows, 4, pw.n_data, values)
     _, m, s = merge_lse([(c[0], sm[3], sm[4]) for c, sm in zip(counts, sums)])
     nf, mean, m2 = merge_moments([(c[0], sm[0], sm[1], sm[2]) for c, sm in zip(counts, sums)])
     total = np.sum(counts, axis=0)
-    vals = None
-    if values:
-        vals = np.empty((n, nd))
-        for r, p in enumerate(parts):
-            rows = rank_rows(r, len(parts), n_chains, history_rows, int(p[2]), int(p[3]))
-            vals[rows - n_burn] = np.asarray(p[4], dtype=np.float64).reshape(len(rows), nd)
     return finish_waic((nf, total[1], total[2], total[3]), m, s, mean, m2, n, vals)
 
 
@@ -296,7 +276,7 @@ def compute_loo(eng, allgather, pw, n_burn, n_chains, r_eff=1.0, tails=False):
     check_single_rank(WHO_LOO, len(allgather(None)))
     n_burn = check_n_burn(WHO_LOO, n_burn)
     r = check_r_eff(WHO_LOO, r_eff, pw.n_data)
-    if eng.pointwise_window_rows(n_burn) == 0:
+    if eng.window_rows(n_burn) == 0:
         raise empty_window(WHO_LOO, n_burn)
     rec, stats, tl = eng.loo(pw, n_burn, r, tails=bool(tails))       # (refuses a kept set beyond the budget before it compiles or allocates)
     waic = compute(eng.pointwise, allgather, pw, n_burn, n_chains, eng.history_rows())
